@@ -13,10 +13,23 @@ gradient all-reduce (N > 1) with each bucket's Adam update behind it, weight re-
 Weak scaling: per-GPU batch fixed.  Launch: ``python bench.py`` (1 GPU) or
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
 
+A plain run does what the headline figure needs and nothing else: set up, warm up, time
+``--steps`` steps, print the JSON line.  ``--full`` adds every other measurement named below
+(the HPO records; at N > 1 the DP-off and RCCL-path comparison re-runs).  The model seed is
+fixed, so the same arguments train on the same weights, data and dropout masks in every run.
+
+``--dump-outputs DIR`` writes what the last timed step left a caller of the timed path
+(``train_steps``) with -- every trained weight, and the mean loss / accuracy / sample count
+``read_metrics`` returns -- as ``DIR/<name>.npy`` (float32 / float64).  The clock-settle
+replays then run on a twin model, so the dumped state is a fixed number of steps (warmup,
+graph capture, one settle replay, timed) from the seeded initialisation, whatever the clock
+did.  At most 64 MB: a larger array is written as a fixed seeded sample of its elements.
+
 Self-check at N > 1 (the multi-GPU path is never run by the builder; the run proves
 itself): the line reports the rank count the RCCL communicator reports, the gradient
 bucket sizes, per-rank step-time p50/max, a cross-rank checksum of the trained weights
-and the exposed communication time (the same step without DP, same N, timed right after);
+and, with ``--full``, the exposed communication time (the same step without DP, same N, timed
+right after);
 the process exits with status 3 if the checksums differ or RCCL saw the wrong rank count.
 Before the timed run, unless ``INTML_XGMI`` / ``INTML_BUCKET_BYTES`` pin it, a short probe
 times the full DP step on each data plane (fused xGMI kernel, one RCCL all-reduce, forked
@@ -26,7 +39,8 @@ probe numbers and the choice are in the self-check).
 ``--via-fit`` times what users run instead: ``apps.rpv.train_model(...)`` epochs
 (Keras fit loop, Horovod callbacks, optional ``--lr-warmup-epochs``), training images only.
 
-HPO trials/hour (BASELINE.json's second metric) rides on the same JSON line as ``"hpo"``:
+With ``--full``, HPO trials/hour (BASELINE.json's second metric) rides on the same JSON line
+as ``"hpo"``:
 rank 0 starts a task farm on every visible GPU BEFORE anything touches the GPU (engines are
 child processes; nothing is forked from a GPU-initialised process), the training bench runs
 and is timed while the engines idle, the data-parallel group shuts down, and then the farm
@@ -34,7 +48,8 @@ runs the DistHPO_mnist random search (``DistHPO_mnist.ipynb:137-255``: 64 trials
 60k samples, valid_frac 0.17, batch 128, load-balanced over the engines), capped at
 ``--hpo-budget`` seconds including engine start-up (a capped run reports the trials it
 finished), and then BASELINE config 5 as ``"hpo_rpv"``: DistWidgetHPO_rpv's 8 concurrent RPV
-trials monitored live by the dashboard model (``InlineHpo``).  ``--no-hpo`` skips both.
+trials monitored live by the dashboard model (``InlineHpo``).  ``--no-hpo`` skips both in a
+``--full`` run.
 """
 from __future__ import annotations
 
@@ -94,20 +109,10 @@ def synthetic(n, shape, ncls, ex, dev, g):
     return synth.synth_device("rpv" if ncls == 1 else "mnist", n, shape, ncls, ex.in_Cs, seed, dev)
 
 
-def time_steps(model, data, B, steps, warmup, chunk, g, dev, settle_ms=0.0, info=None):
-    """Warmup (captures every graph the timed loop replays), then time `steps` full training
-    steps as graph replays of `chunk` steps.  Returns (elapsed seconds on this rank, per-step
-    ms of each replay from HIP events).
-
-    settle_ms > 0: before the timed region, replay the timed graph back to back (no host sync
-    between replays) until the GPU has run it for ~settle_ms.  The chip's power management
-    holds a lower clock until it has been under sustained load for ~10-15 ms; the driver's
-    short command (--steps 20 --warmup 5: ~3 ms of work before its timed region) otherwise
-    times the ramp, not the step -- every kernel of the step runs 3-5 % slower in it and an
-    idle gap of 200 ms puts it back (profiles/r5_driver_gap.txt).  The settle steps are
-    reported on the JSON line (``settle_steps`` / ``settle_ms``), never folded into ``warmup``."""
+def _stepper(model, data, B, g, dev):
+    """run(k): the next k training steps of `model` over the epoch permutation (drawn from `g`,
+    re-drawn when it is used up)."""
     import torch
-    from cori_intml_examples_amd.parallel import hvd
     ex = model._executor
     n = data.n
     state = {"pos": 0, "perm": torch.randperm(n, device=dev, generator=g)}
@@ -119,24 +124,56 @@ def time_steps(model, data, B, steps, warmup, chunk, g, dev, settle_ms=0.0, info
         ex.train_steps(data, state["perm"], state["pos"], B, k)
         state["pos"] += k * B
 
+    return run
+
+
+def time_steps(model, data, B, steps, warmup, chunk, g, dev, settle_ms=0.0, info=None, settle_model=None):
+    """Warmup (captures every graph the timed loop replays), then time `steps` full training
+    steps as graph replays of `chunk` steps.  Returns (elapsed seconds on this rank, per-step
+    ms of each replay from HIP events).
+
+    settle_ms > 0: before the timed region, replay the timed graph back to back (no host sync
+    between replays) until the GPU has run it for ~settle_ms.  The chip's power management
+    holds a lower clock until it has been under sustained load for ~10-15 ms; the driver's
+    short command (--steps 20 --warmup 5: ~3 ms of work before its timed region) otherwise
+    times the ramp, not the step -- every kernel of the step runs 3-5 % slower in it and an
+    idle gap of 200 ms puts it back (profiles/r5_driver_gap.txt).  The settle steps are
+    reported on the JSON line (``settle_steps`` / ``settle_ms``), never folded into ``warmup``.
+
+    settle_model: a twin of `model` (same geometry, so the same kernels) whose graph the settle
+    replays instead, but for one last replay of `model`'s own (its buffers are cold after the
+    twin's).  How many settle replays run depends on the clock; on the twin they leave `model`
+    a number of steps from its initialisation that the arguments alone decide."""
+    import torch
+    from cori_intml_examples_amd.parallel import hvd
+    ex = model._executor
+    run = _stepper(model, data, B, g, dev)
+
     def chunks(total):
         return [chunk] * (total // chunk) + ([total % chunk] if total % chunk else [])
 
     ex.reset_metrics()
     timed = chunks(steps)
+    spin = run
+    if settle_model is not None and settle_ms > 0 and timed:
+        spin = _stepper(settle_model, data, B, torch.Generator(device=dev).manual_seed(4321), dev)
+        spin(max(timed))                   # captures the twin's graph
     for k in chunks(warmup) + sorted(set(timed)):
         run(k)
     if settle_ms > 0 and timed:
         k = max(timed)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        run(k)
+        spin(k)
         e1.record()
         torch.cuda.synchronize()
         reps = max(1, int(-(-settle_ms // max(e0.elapsed_time(e1), 1e-3))))
         t0 = time.perf_counter()
         for _ in range(reps):
-            run(k)
+            spin(k)
+        if spin is not run:
+            run(k)                         # one replay back on the model's own buffers (caches, TLB)
+            reps += 1
         torch.cuda.synchronize()
         if info is not None:
             info["settle_steps"] = (reps + 1) * k
@@ -160,6 +197,30 @@ def weight_checksum(model):
     import torch
     m = model.store.master[:model.store.numel].double()
     return [float(m.sum()), float(m.abs().sum()), float((m * m).sum())]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(model, out_dir):
+    """What the last timed step left its caller with, as ``out_dir/<name>.npy``: every weight
+    (``<layer>_<kernel|bias>``, float32) and ``metrics`` (float64: mean loss, accuracy and
+    sample count since the warmup began, as ``read_metrics`` returns them).  Over
+    DUMP_BUDGET_BYTES in all, each array keeps the same fraction of its elements: a sorted
+    sample drawn with a fixed seed, written flat."""
+    import numpy as np
+    arrays = {"metrics": np.array(model._executor.read_metrics(), dtype=np.float64)}
+    for s, w in zip(model.store.specs, model.store.get_weights()):
+        arrays["%s_%s" % (s.layer.name, s.short)] = np.ascontiguousarray(w, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState(1234)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES and a.size > 1024:
+            keep = max(1024, int(a.size * (DUMP_BUDGET_BYTES * 0.9 / total)))
+            a = a.reshape(-1)[np.sort(rs.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), a)
+    return sorted(arrays)
 
 
 def probe_data_planes(args, size, dev, g, B, chunk):
@@ -491,8 +552,14 @@ def main():
                     help="before the timed steps, replay the timed graph back to back for ~this long so the "
                          "GPU clock has left its power-management ramp (reported as settle_steps / settle_ms; "
                          "0 = off; profiles/r5_driver_gap.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the inline HPO records "
+                         "('hpo', 'hpo_rpv') and, on the data-parallel path, the DP-off and RCCL-path re-runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the trained weights and the metrics the last step "
+                         "left as DIR/<name>.npy (rank 0; at most 64 MB)")
     ap.add_argument("--no-dp-delta", action="store_true",
-                    help="skip the DP-off re-run that measures the exposed communication time")
+                    help="with --full: skip the DP-off re-run that measures the exposed communication time")
     ap.add_argument("--via-fit", action="store_true", help="time apps.rpv.train_model epochs (Keras fit path)")
     ap.add_argument("--fit-epochs", type=int, default=4)
     ap.add_argument("--lr-warmup-epochs", type=int, default=0)
@@ -502,7 +569,8 @@ def main():
                          "rpv = DistWidgetHPO_rpv-style 8 concurrent RPV trials, cray = genetic search over "
                          "2-rank DP train_rpv evaluations; extra flags after -- go to benchmarks/hpo_throughput.py")
     ap.add_argument("--no-hpo", action="store_true",
-                    help="skip the DistHPO_mnist trials/hour measurement reported as 'hpo' on the JSON line")
+                    help="with --full: skip the DistHPO_mnist trials/hour measurement reported as 'hpo' on "
+                         "the JSON line")
     ap.add_argument("--hpo-budget", type=float, default=90.0, help="seconds for the inline HPO, start-up included")
     ap.add_argument("--hpo-engines-per-gpu", type=int, default=4)
     args, extra = ap.parse_known_args()
@@ -514,7 +582,7 @@ def main():
         os.environ["INTML_GRAPHS"] = "0"
     # rank 0 starts the HPO farm now, before this process initialises the GPU
     inline_hpo = None
-    if not args.no_hpo and not args.via_fit and int(os.environ.get("RANK", "0")) == 0:
+    if args.full and not args.no_hpo and not args.via_fit and int(os.environ.get("RANK", "0")) == 0:
         try:
             inline_hpo = InlineHpo(args.hpo_engines_per_gpu, args.hpo_budget)
             import atexit
@@ -537,6 +605,9 @@ def main():
     dp = size > 1 or os.environ.get("INTML_DP_FORCE", "0") not in ("0", "")
     chunk = max(1, args.steps_per_graph)
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    # every model's seed (initial weights, dropout masks) follows from this one
+    from cori_intml_examples_amd.utils import set_random_seed
+    set_random_seed(1234 + rank)
     plane_probe = probe_data_planes(args, size, dev, g, B, chunk) if dp else None
     model, shape, ncls, cfg_name, metric, baseline = build(args, size, dp, dev)
     ex = model._executor
@@ -548,11 +619,17 @@ def main():
         data = synthetic(max(args.samples, B * 4), shape, ncls, ex, dev, g)
         hvd.broadcast_global_variables(0, model=model)
         settle = {}
+        twin = None
+        if args.dump_outputs and args.settle_ms > 0:
+            twin = build(args, size, dp, dev)[0]
+            hvd.broadcast_global_variables(0, model=twin)
         elapsed, per_step = time_steps(model, data, B, args.steps, args.warmup, chunk, g, dev,
-                                       settle_ms=args.settle_ms, info=settle)
+                                       settle_ms=args.settle_ms, info=settle, settle_model=twin)
         steps = args.steps
         warmup_note = args.warmup
     loss = ex.read_metrics()[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
 
     # ---------------------------------------------------------------- self-check (DP)
     selfcheck, ok = None, True
@@ -586,7 +663,7 @@ def main():
             "plane_probe_ms_per_step": plane_probe,
         }
         ok = selfcheck["weights_identical"] and (comm is None or selfcheck["rccl_nranks"] == size)
-        if not args.no_dp_delta and not args.via_fit:
+        if args.full and not args.no_dp_delta and not args.via_fit:
             # the same step without the data-parallel machinery, same N, right after
             ref, *_ = build(args, size, False, dev)
             data2 = synthetic(max(args.samples, B * 4), shape, ncls, ref._executor, dev, g)

@@ -112,6 +112,36 @@ def test_probe_respects_pinned_plane(probe_env, monkeypatch):
     assert bench.probe_data_planes(args, 1, None, None, 128, 8) is None
 
 
+def test_dump_outputs_names_dtypes_and_budget(monkeypatch, tmp_path):
+    """--dump-outputs: one float32 .npy per weight plus the float64 metrics; over the budget
+    every large array becomes the same seeded sample in every run and the total stays under it."""
+    import numpy as np
+    rs = np.random.RandomState(0)
+    weights = [rs.rand(3, 3, 4, 8).astype(np.float32), rs.rand(8).astype(np.float32),
+               rs.rand(5000, 4).astype(np.float32)]
+    specs = [types.SimpleNamespace(layer=types.SimpleNamespace(name=n), short=s)
+             for n, s in (("conv2d_1", "kernel"), ("conv2d_1", "bias"), ("dense_1", "kernel"))]
+    model = types.SimpleNamespace(
+        _executor=types.SimpleNamespace(read_metrics=lambda: (0.25, 0.75, 2560)),
+        store=types.SimpleNamespace(specs=specs, get_weights=lambda: weights))
+    names = bench.dump_outputs(model, str(tmp_path / "a"))
+    assert names == ["conv2d_1_bias", "conv2d_1_kernel", "dense_1_kernel", "metrics"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["metrics"].dtype == np.float64 and got["metrics"].tolist() == [0.25, 0.75, 2560.0]
+    for n, w in zip(("conv2d_1_kernel", "conv2d_1_bias", "dense_1_kernel"), weights):
+        assert got[n].dtype == np.float32 and np.array_equal(got[n], w)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 16384)
+    for d in ("b", "c"):
+        bench.dump_outputs(model, str(tmp_path / d))
+    small = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert sum(a.nbytes for a in small.values()) <= 16384
+    assert np.array_equal(small["conv2d_1_kernel"], weights[0])          # small arrays stay whole
+    assert small["dense_1_kernel"].ndim == 1 and 1024 <= small["dense_1_kernel"].size < 20000
+    assert np.isin(small["dense_1_kernel"], weights[2]).all()
+    for n in names:
+        assert np.array_equal(small[n], np.load(tmp_path / "c" / (n + ".npy")))
+
+
 def test_inline_hpo_record_on_cpu(monkeypatch):
     """bench.py's inline HPO (the 'hpo' record of the JSON line): the farm starts before the
     training bench, runs the DistHPO_mnist trials after it and reports trials/hour.  CPU

@@ -21,7 +21,9 @@ spec.loader.exec_module(mod)
 sys.modules["cori_intml_examples_amd._h5lite"] = mod
 import cori_intml_examples_amd.io.h5 as h5
 import pytest
-rc = pytest.main([sys.argv[2], "-q", "-x", "-p", "no:cacheprovider", "-m", "not gpu",
+# collection starts at the repository, never at a directory above it and this scratch cwd
+rc = pytest.main([sys.argv[2], "--rootdir=" + sys.argv[3], "--confcutdir=" + sys.argv[3],
+                  "-q", "-x", "-p", "no:cacheprovider", "-m", "not gpu",
                   "-k", "h5lite or rpv_files or save or load or checkpoint or strings"])
 assert getattr(h5, "_MOD", mod) is mod, "the tests did not use the sanitized module"
 print("SANITIZED_MODULE", mod.__file__)
@@ -54,7 +56,7 @@ def test_h5lite_under_asan_ubsan(tmp_path):
     env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1:halt_on_error=1"
     env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1"
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, "-c", CHILD, so, os.path.join(ROOT, "tests", "test_io.py")],
+    r = subprocess.run([sys.executable, "-c", CHILD, so, os.path.join(ROOT, "tests", "test_io.py"), ROOT],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     out = r.stdout + r.stderr
     assert "ERROR: AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
