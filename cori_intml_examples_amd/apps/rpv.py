@@ -52,10 +52,12 @@ def build_model(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5
 
 def train_model(model, train_input, train_labels, valid_input, valid_labels, batch_size, n_epochs,
                 lr_warmup_epochs=0, lr_reduce_patience=8, checkpoint_file=None, use_horovod=False,
-                verbose=2, callbacks: Optional[List] = None):
+                verbose=2, callbacks: Optional[List] = None, train_weights=None, valid_weights=None):
     """``rpv.py:74-106``: Horovod Broadcast(0) / MetricAverage / LR warmup first (so
     ReduceLROnPlateau sees rank-averaged ``val_loss``), then ReduceLROnPlateau(patience),
-    then an optional whole-model checkpoint each epoch."""
+    then an optional whole-model checkpoint each epoch.  ``train_weights`` / ``valid_weights``:
+    the per-event weights (``all_events/weight``) as ``sample_weight`` of the training loss
+    and of ``val_loss`` (the ``use_weights`` switch of ``Train_rpv.ipynb``)."""
     cbs = list(callbacks or [])
     if use_horovod:
         from ..parallel import hvd
@@ -70,8 +72,9 @@ def train_model(model, train_input, train_labels, valid_input, valid_labels, bat
             rank0 = hvd.rank() == 0
         if rank0:
             cbs.append(_cb.ModelCheckpoint(checkpoint_file))
+    valid = (valid_input, valid_labels) if valid_weights is None else (valid_input, valid_labels, valid_weights)
     return model.fit(x=train_input, y=train_labels, batch_size=batch_size, epochs=n_epochs,
-                     validation_data=(valid_input, valid_labels), callbacks=cbs, verbose=verbose)
+                     validation_data=valid, callbacks=cbs, verbose=verbose, sample_weight=train_weights)
 
 
 def classification_report(labels, outputs, weights=None, threshold=0.5):

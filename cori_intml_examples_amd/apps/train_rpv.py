@@ -10,7 +10,8 @@ One rank per GPU:
 
 Extra flags (not in the reference): ``--synthetic`` (auto-enabled when ``--input-dir``
 has no ``train.h5``: synthetic events of the RPV schema), ``--channels``, ``--seed``,
-``--verbose``, ``--shard`` / ``--replicate`` (data-parallel sampling: each rank reads a
+``--verbose``, ``--use-weights`` (the per-event weights as ``sample_weight`` of the training
+and validation loss; default off), ``--shard`` / ``--replicate`` (data-parallel sampling: each rank reads a
 disjoint shard, or -- the reference's semantics -- the full dataset with its own shuffle).
 """
 from __future__ import annotations
@@ -45,6 +46,8 @@ def build_parser():
     p.add_argument("--channels", type=int, default=1)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--verbose", type=int, default=2)
+    p.add_argument("--use-weights", action="store_true",
+                   help="weight the training and validation loss by the per-event weights")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--shard", dest="shard", action="store_true", default=None)
     g.add_argument("--replicate", dest="shard", action="store_false")
@@ -69,8 +72,8 @@ def main(argv=None):
         print("input dir %s has no train.h5: using synthetic RPV events" % args.input_dir)
     train_data, valid_data, test_data = load_dataset(args.input_dir, args.n_train, args.n_valid, args.n_test,
                                                      synthetic=synthetic, channels=args.channels)
-    train_input, train_labels, _ = train_data
-    valid_input, valid_labels, _ = valid_data
+    train_input, train_labels, train_weights = train_data
+    valid_input, valid_labels, valid_weights = valid_data
     test_input, test_labels, _ = test_data
     print("train shape:", train_input.shape, "Mean label:", train_labels.mean())
     print("valid shape:", valid_input.shape, "Mean label:", valid_labels.mean())
@@ -86,7 +89,9 @@ def main(argv=None):
     print("[train_rpv] %d epochs, batch %d per rank, lr %g" % (args.n_epochs, args.batch_size, lr))
     history = train_model(model, train_input=train_input, train_labels=train_labels, valid_input=valid_input,
                           valid_labels=valid_labels, batch_size=args.batch_size, n_epochs=args.n_epochs,
-                          verbose=args.verbose, use_horovod=True)
+                          verbose=args.verbose, use_horovod=True,
+                          train_weights=train_weights if args.use_weights else None,
+                          valid_weights=valid_weights if args.use_weights else None)
     if hvd.rank() == 0 and getattr(history, "data_plane", None):
         print("[train_rpv] gradient reducer %s" % history.data_plane)
     if args.fom in ("best", "last"):

@@ -291,6 +291,9 @@ struct HeadArgs {
   // A/B + tests: 1 = the generic serial epilogue / loss path even where the fast paths apply
   // (bit-identical results: tests/test_hip_model.py::test_head_fast_paths_bit_identical)
   int generic = 0;
+  // wb != null: the weighted loss (head_kernel<.., true>).  Row m's sample weight is wb[m] (the
+  // batch gathered by the prologue) or, with yidx, dataset row yidx[m] of st->data_w
+  const float* wb = nullptr;
 };
 
 struct GatherArgs {
@@ -302,6 +305,7 @@ struct GatherArgs {
   bf16* xb = nullptr;
   float* yb = nullptr;
   int skip_x = 0;                // images read straight from the dataset by the conv stack
+  float* wb = nullptr;           // [bs] sample weights copied from st->data_w (null: unweighted plan)
 };
 
 

@@ -163,14 +163,14 @@ PYBIND11_MODULE(_kernels, m) {
       RW(HeadArgs, flat_C) RW(HeadArgs, flat_Cs) PTR(HeadArgs, w) PTR(HeadArgs, bias) PTR(HeadArgs, y)
       RW(HeadArgs, act) RW(HeadArgs, training) RW(HeadArgs, inv_bs) PTR(HeadArgs, st) PTR(HeadArgs, probs)
       PTR(HeadArgs, wslab) PTR(HeadArgs, bslab) RW(HeadArgs, bt) RW(HeadArgs, epi) PTR(HeadArgs, ts)
-      PTR(HeadArgs, yidx) RW(HeadArgs, generic);
+      PTR(HeadArgs, yidx) RW(HeadArgs, generic) PTR(HeadArgs, wb);
 
 
   py::class_<GatherArgs>(m, "GatherArgs")
       .def(py::init<>())
       PTR(GatherArgs, xs) PTR(GatherArgs, ys) PTR(GatherArgs, perm) PTR(GatherArgs, st)
       RW(GatherArgs, bs) RW(GatherArgs, R) RW(GatherArgs, C) RW(GatherArgs, Nd) PTR(GatherArgs, xb)
-      PTR(GatherArgs, yb) RW(GatherArgs, skip_x);
+      PTR(GatherArgs, yb) RW(GatherArgs, skip_x) PTR(GatherArgs, wb);
 
   py::class_<StepBeginArgs>(m, "StepBeginArgs")
       .def(py::init<>())
@@ -348,6 +348,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("STEP_STATE_WARM_OFFSET") = (int)offsetof(StepState, warm_t0);
   m.attr("STEP_STATE_DATA_OFFSET") = (int)offsetof(StepState, data_x);
   m.attr("STEP_STATE_DATAN_OFFSET") = (int)offsetof(StepState, data_n);
+  m.attr("STEP_STATE_DATAW_OFFSET") = (int)offsetof(StepState, data_w);
 
   m.def("wgrad_lds_bytes", &wgrad_lds_bytes);
   m.def("conv_halo_lds_bytes", &conv_halo_lds_bytes);

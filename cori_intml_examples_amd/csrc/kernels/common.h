@@ -187,6 +187,9 @@ struct StepState {
   // metric accumulators spread over METRIC_SLOTS slots (workgroup b adds to slot b % 16):
   // [slot][loss_sum * 2^32, correct_sum, count, spare]; the host sums the slots
   long long metric_slots[16][4];
+  // bound dataset's per-sample loss weights [n] fp32 (0 = unweighted), host-written with
+  // data_x / data_y; appended here so every exported field offset above keeps its value
+  unsigned long long data_w;
 };
 
 enum OptKind { OPT_SGD = 0, OPT_RMSPROP = 1, OPT_ADADELTA = 2, OPT_ADAM = 3, OPT_NADAM = 4 };

@@ -92,10 +92,11 @@ __device__ __forceinline__ void grp16_argmax(float& v, int& i) {
 
 // Softmax + Keras categorical_crossentropy (clip of the renormalised probabilities) and its
 // gradient, lane n = class n.  Same formulas as the serial head path; sums are 16-lane trees.
-template <int NM>
+// WT: the row's loss and gradient scaled by its weight factor wf (head_kernel).
+template <int NM, bool WT>
 __device__ __forceinline__ void softmax_cce_lanes(const HeadArgs& a, const float (&z)[NM], int lane, int row,
                                                   int rw, int N, const float* ysh_row, const float* bsh,
-                                                  float* dz_row, float* met_row) {
+                                                  float* dz_row, float* met_row, float wf) {
   const bool live = row < a.M;
   const int n = lane & 15;
   const bool cls = live && lane < 16 && n < N;
@@ -131,7 +132,13 @@ __device__ __forceinline__ void softmax_cce_lanes(const HeadArgs& a, const float
     grp16_argmax(ymx, ay);
     correct = (live && am == ay) ? 1.f : 0.f;
   }
-  if (lane < NM) dz_row[lane] = dzn * a.inv_bs;
+  if constexpr (WT) {
+    dzn = dzn * a.inv_bs * wf;
+    loss *= wf;
+  } else {
+    dzn = dzn * a.inv_bs;
+  }
+  if (lane < NM) dz_row[lane] = dzn;
   if (lane == 0) {
     met_row[0] = live ? loss : 0.f;
     met_row[1] = correct;
@@ -141,7 +148,13 @@ __device__ __forceinline__ void softmax_cce_lanes(const HeadArgs& a, const float
 #define HEAD_STAMP(i)                                                                 \
   if (a.ts && threadIdx.x == 0) a.ts[(size_t)blockIdx.x * 8 + (i)] = wall_clock64();
 
-template <int RB, int NM>
+// WT: the sample-weighted loss (Keras weighted_masked_objective).  With w the rows' weights
+// and nnz the batch's count of non-zero weights, row i's loss and dz are scaled by
+// wf_i = w_i * (M / nnz): the batch loss is sum(w l) / nnz and the metric accumulator receives
+// M * L_batch per batch (Keras' BaseLogger epoch mean).  nnz is clamped to 1, so a batch of
+// all-zero weights gives zero loss and gradient instead of 0/0.  All weights 1 -> wf = 1.0f
+// exactly: bit-identical to the unweighted instance.  Accuracy and the row count are unweighted.
+template <int RB, int NM, bool WT>
 __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
   __shared__ float dz_s[RB][NM];
   __shared__ float met[RB][2];
@@ -173,6 +186,23 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     const float* yr = a.yidx ? reinterpret_cast<const float*>(a.st->data_y) + (size_t)a.yidx[ok ? m : 0] * a.st->data_C
                              : a.y + (size_t)m * a.N;
     ysh[rl][n] = ok ? yr[n] : 0.f;
+  }
+  // the rows' weights, and nnz counted by every workgroup itself over all M weights (ballot +
+  // popcount: an exact integer, the same in every workgroup; no float atomics, no
+  // cross-workgroup wait).  Read after the barriers below.
+  __shared__ float wrow[RB];
+  __shared__ int nnz_s[4];
+  if constexpr (WT) {
+    const float* dw = a.yidx ? reinterpret_cast<const float*>(a.st->data_w) : a.wb;
+    int cnt = 0;
+    for (int m0 = 0; m0 < a.M; m0 += 256) {
+      const int m = m0 + tid;
+      float wv = 0.f;
+      if (m < a.M) wv = !dw ? 1.f : (a.yidx ? dw[a.yidx[m]] : dw[m]);
+      cnt += __popcll(__ballot(wv != 0.f));
+      if (m >= row0 && m < row0 + RB) wrow[m - row0] = wv;   // (rows >= M: 0)
+    }
+    if (lane == 0) nnz_s[wave] = cnt;
   }
   bool done_epi = false;
   if constexpr (RB == 1) {
@@ -279,6 +309,11 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 
   HEAD_STAMP(1);
   if (!fused) __syncthreads();   // (the fused path's barriers already cover wsh / ysh / bsh)
+  float wf = 1.f;                // this wave's row factor w_i * (M / nnz)
+  if constexpr (WT) {
+    const int nnz = max((nnz_s[0] + nnz_s[1]) + (nnz_s[2] + nnz_s[3]), 1);
+    wf = wrow[rw] * ((float)a.M / (float)nnz);
+  }
   float z[NM];
 #pragma unroll
   for (int n = 0; n < NM; ++n) z[n] = 0.f;
@@ -318,7 +353,9 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
           const float pc = clip_nan(p, eps, 1.f - eps);
           dz = ((p >= eps) && (p <= 1.f - eps)) ? (pc - ysh[0][0]) : 0.f;
         }
-        dz_s[0][0] = dz * a.inv_bs;
+        dz = dz * a.inv_bs;
+        if constexpr (WT) dz *= wf;
+        dz_s[0][0] = dz;
       }
       HEAD_STAMP(2);
       __syncthreads();
@@ -329,7 +366,8 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
           const float yv = ysh[0][0];
           const float pc = clip_nan(p, eps, 1.f - eps);
           const float lg = logf(pc / (1.f - pc));
-          const float ls = fmaxf(lg, 0.f) - lg * yv + log1pf(expf(-fabsf(lg)));
+          float ls = fmaxf(lg, 0.f) - lg * yv + log1pf(expf(-fabsf(lg)));
+          if constexpr (WT) ls *= wf;
           const float cs = (rintf(p) == yv) ? 1.f : 0.f;
           long long* slot = a.st->metric_slots[blockIdx.x & 15];
           const bool loss_ok = isfinite(ls) && fabsf(ls) < 1073741824.f;
@@ -371,7 +409,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
       // softmax + categorical cross-entropy, one class per lane (lanes 0..15 of the row's
       // wave; every lane holds all logits after the reduction above).  The serial lane-0
       // version spent ~5 us per row in dependent exp / log / divide chains.
-      softmax_cce_lanes<NM>(a, z, lane, row, rw, N, &ysh[rw][0], bsh, &dz_s[rw][0], &met[rw][0]);
+      softmax_cce_lanes<NM, WT>(a, z, lane, row, rw, N, &ysh[rw][0], bsh, &dz_s[rw][0], &met[rw][0], wf);
     }
   }
   if (lane == 0 && row_wave && (NM == 1 || a.act != 2)) {
@@ -437,7 +475,12 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
         }
       }
     }
-    for (int n = 0; n < NM; ++n) dz_s[rw][n] = dz[n] * a.inv_bs;
+    if constexpr (WT) {
+      for (int n = 0; n < NM; ++n) dz_s[rw][n] = dz[n] * a.inv_bs * wf;
+      loss *= wf;
+    } else {
+      for (int n = 0; n < NM; ++n) dz_s[rw][n] = dz[n] * a.inv_bs;
+    }
     met[rw][0] = loss;
     met[rw][1] = correct;
   }
@@ -519,14 +562,20 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 int head_rows_per_block(bool fused) { return fused ? 1 : HEAD_RB; }
 
 // NM: class-count bound (1 = the binary sigmoid head: no per-class loops or arrays)
-void launch_head(const HeadArgs& a, hipStream_t s) {
+template <bool WT>
+static void launch_head_wt(const HeadArgs& a, hipStream_t s) {
   const dim3 g1(a.M), g4((a.M + HEAD_RB - 1) / HEAD_RB);
   if (a.N == 1) {
-    if (a.epi.part != nullptr) hipLaunchKernelGGL((head_kernel<1, 1>), g1, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((head_kernel<HEAD_RB, 1>), g4, dim3(256), 0, s, a);
+    if (a.epi.part != nullptr) hipLaunchKernelGGL((head_kernel<1, 1, WT>), g1, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((head_kernel<HEAD_RB, 1, WT>), g4, dim3(256), 0, s, a);
   } else {
-    if (a.epi.part != nullptr) hipLaunchKernelGGL((head_kernel<1, 16>), g1, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((head_kernel<HEAD_RB, 16>), g4, dim3(256), 0, s, a);
+    if (a.epi.part != nullptr) hipLaunchKernelGGL((head_kernel<1, 16, WT>), g1, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((head_kernel<HEAD_RB, 16, WT>), g4, dim3(256), 0, s, a);
   }
+}
+// a non-null weight pointer selects the weighted instances (targets required: no loss otherwise)
+void launch_head(const HeadArgs& a, hipStream_t s) {
+  if (a.wb != nullptr && a.y != nullptr) launch_head_wt<true>(a, s);
+  else launch_head_wt<false>(a, s);
 }
 int head_epi_max() { return HEAD_EPI_MAX; }

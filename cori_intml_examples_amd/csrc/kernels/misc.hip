@@ -37,6 +37,10 @@ __device__ __forceinline__ void gather_block(const GatherArgs& a, const StepStat
   }
   if (bx == 0 && a.yb && ys)
     for (int c = threadIdx.x; c < C; c += 256) a.yb[(size_t)row * C + c] = ys[(size_t)src * C + c];
+  if (bx == 0 && a.wb && threadIdx.x == 0) {
+    const float* ws = reinterpret_cast<const float*>(st->data_w);
+    a.wb[row] = ws ? ws[src] : 1.f;
+  }
 }
 
 __global__ __launch_bounds__(256) void slab_reduce_kernel(float* __restrict__ grad, const RedTable tab) {

@@ -142,7 +142,9 @@ def split(data, frac: float):
     validation set (views, no copy)."""
     from ..models.executor_base import DeviceData
     s = int(data.n * (1.0 - frac))
-    return (DeviceData(data.x[:s], data.y[:s], s), DeviceData(data.x[s:], data.y[s:], data.n - s))
+    w = data.w
+    return (DeviceData(data.x[:s], data.y[:s], s, None if w is None else w[:s]),
+            DeviceData(data.x[s:], data.y[s:], data.n - s, None if w is None else w[s:]))
 
 
 S_FLIP, S_RELABEL = 12, 13

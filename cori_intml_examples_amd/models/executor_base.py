@@ -16,6 +16,7 @@ class DeviceData:
     x: torch.Tensor          # executor-specific layout
     y: torch.Tensor          # [N, C] fp32 targets (one-hot for categorical)
     n: int
+    w: Optional[torch.Tensor] = None   # [N] fp32 per-sample loss weights (None = unweighted)
 
 
 def prepare_targets(y: np.ndarray, plan: Plan) -> np.ndarray:
@@ -32,6 +33,41 @@ def prepare_targets(y: np.ndarray, plan: Plan) -> np.ndarray:
     if y.shape[1] != head.N:
         raise ValueError("targets have %d columns, model outputs %d" % (y.shape[1], head.N))
     return np.ascontiguousarray(y)
+
+
+def standardize_weights(y, n: int, sample_weight=None, class_weight=None) -> Optional[np.ndarray]:
+    """Per-sample loss weights [n] fp32 from Keras' ``sample_weight`` / ``class_weight``
+    (Keras 2.2.4 ``standardize_weights``), or None when neither is given.
+
+    ``sample_weight``: 1-D, one entry per sample.  ``class_weight``: dict class -> weight; a
+    row's class is the argmax of a multi-column target or int(y) of a one-column one, and every
+    class present in ``y`` must be in the dict.  Both given: the product."""
+    w = None
+    if sample_weight is not None:
+        w = np.asarray(sample_weight, dtype=np.float32)
+        if w.ndim != 1:
+            raise ValueError("sample_weight must be 1-D (one weight per sample), got shape %s" % (w.shape,))
+        if w.shape[0] != n:
+            raise ValueError("sample_weight has %d entries for %d samples" % (w.shape[0], n))
+    if class_weight is not None:
+        if not isinstance(class_weight, dict):
+            raise ValueError("class_weight must be a dict {class: weight}")
+        if y is None:
+            raise ValueError("class_weight needs targets")
+        ya = np.asarray(y)
+        if ya.ndim > 2:
+            raise ValueError("class_weight not supported for %d-D targets" % ya.ndim)
+        cls = ya.argmax(axis=1) if (ya.ndim == 2 and ya.shape[1] > 1) else ya.reshape(-1).astype(np.int64)
+        if cls.shape[0] != n:
+            raise ValueError("targets have %d rows for %d samples" % (cls.shape[0], n))
+        missing = set(np.unique(cls).tolist()) - set(int(k) for k in class_weight.keys())
+        if missing:
+            raise ValueError("class_weight must contain all classes in the data; the classes %s exist in the "
+                             "data but not in class_weight" % sorted(missing))
+        lut = {int(k): float(v) for k, v in class_weight.items()}
+        cw = np.asarray([lut[int(c)] for c in cls], dtype=np.float32)
+        w = cw if w is None else w * cw
+    return None if w is None else np.ascontiguousarray(w, dtype=np.float32)
 
 
 def warmup_lr(g: int, spe: int, size: int, epochs: float, base: float) -> float:
@@ -72,7 +108,8 @@ class Executor:
         return host_lr
 
     # data ---------------------------------------------------------------------------------
-    def upload(self, x: np.ndarray, y: Optional[np.ndarray]) -> DeviceData:
+    def upload(self, x: np.ndarray, y: Optional[np.ndarray], w: Optional[np.ndarray] = None) -> DeviceData:
+        """``w``: per-sample loss weights [N] (standardize_weights), None = unweighted."""
         raise NotImplementedError
 
     # steps --------------------------------------------------------------------------------

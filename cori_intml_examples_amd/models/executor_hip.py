@@ -202,6 +202,7 @@ class HipExecutor(Executor):
         self._expected_pos = None
         self._bound_data = None
         self._bound_ref = None
+        self._bound_w = 0
         self._use_perm = None
         self._perm_obj = None
         self._perm_buf = None
@@ -408,7 +409,7 @@ class HipExecutor(Executor):
             self._lr_host = lr
 
     # ------------------------------------------------------------------ data
-    def upload(self, x, y):
+    def upload(self, x, y, w=None):
         if x is None:
             return None
         x = np.asarray(x)
@@ -425,11 +426,17 @@ class HipExecutor(Executor):
             yt = torch.as_tensor(prepare_targets(y, self.plan)).to(self.device)
         else:
             yt = torch.zeros(n, self.plan.head.N, dtype=torch.float32, device=self.device)
-        return DeviceData(xs.reshape(n, -1), yt, n)
+        wt = None
+        if w is not None:
+            wt = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).reshape(-1).to(self.device)
+            if wt.shape[0] != n:
+                raise ValueError("sample weights have %d entries for %d samples" % (wt.shape[0], n))
+        return DeviceData(xs.reshape(n, -1), yt, n, wt)
 
     def _bind_data(self, data: DeviceData, perm: Optional[torch.Tensor]):
         K = self.K
-        key = (id(data), data.x.data_ptr(), data.y.data_ptr())
+        w_ptr = data.w.data_ptr() if data.w is not None else 0
+        key = (id(data), data.x.data_ptr(), data.y.data_ptr(), w_ptr)
         if self._bound_data != key or self._bound_ref is not data:
             self._bound_ref = data     # keep alive: its id / memory must not be recycled while bound
             o = K.STEP_STATE_DATA_OFFSET // 8
@@ -439,6 +446,11 @@ class HipExecutor(Executor):
             self._st_i32[on] = data.n
             self._st_i32[on + 1] = data.x.shape[1]
             self._st_i32[on + 2] = data.y.shape[1]
+            # the weights' pointer is per-data-set state like x / y (0 = unweighted); which head
+            # instance runs is the plan's (keyed on weighted data, _plan_for)
+            if w_ptr != self._bound_w:
+                self._st_i64[K.STEP_STATE_DATAW_OFFSET // 8] = w_ptr
+                self._bound_w = w_ptr
             self._bound_data = key
             self._perm_obj = None
         if perm is not None and perm is not self._perm_obj:
@@ -455,11 +467,13 @@ class HipExecutor(Executor):
             self._use_perm = use
 
     # ------------------------------------------------------------------ steps
-    def _plan_for(self, bs: int, mode: str) -> "BatchPlan":
-        key = (bs, mode)
+    def _plan_for(self, bs: int, mode: str, weighted: bool = False) -> "BatchPlan":
+        # weighted data runs a plan of its own (the weighted head instances, the weight gather):
+        # a plan is never shared between weighted and unweighted data sets
+        key = (bs, mode, "w") if weighted else (bs, mode)
         bp = self._plans.get(key)
         if bp is None:
-            bp = BatchPlan(self, bs, mode)
+            bp = BatchPlan(self, bs, mode, weighted)
             self._plans[key] = bp
         return bp
 
@@ -473,7 +487,7 @@ class HipExecutor(Executor):
         self._bind_data(data, perm)
         if self._expected_pos != pos:
             self._st_i32[1] = pos
-        bp = self._plan_for(bs, "train")
+        bp = self._plan_for(bs, "train", data.w is not None)
         bp.run(k)
         self._expected_pos = pos + k * bs
         self.opt.iterations += k
@@ -486,7 +500,7 @@ class HipExecutor(Executor):
     def eval_step(self, data, pos, bs):
         self._bind_data(data, None)
         self._set_eval_pos(pos, bs)
-        self._plan_for(bs, "eval").run()
+        self._plan_for(bs, "eval", data.w is not None).run()
 
     def predict_step(self, data, pos, bs):
         self._bind_data(data, None)
@@ -532,8 +546,9 @@ class BatchPlan(GeometryMixin):
     """Buffers + prepared kernel argument structs for one (batch size, mode); records the
     launch sequence and replays it from a HIP graph."""
 
-    def __init__(self, ex: HipExecutor, bs: int, mode: str):
+    def __init__(self, ex: HipExecutor, bs: int, mode: str, weighted: bool = False):
         self.ex, self.bs, self.mode = ex, bs, mode
+        self.weighted = bool(weighted) and mode != "predict"
         self.training = mode == "train"
         K = ex.K
         dev = ex.device
@@ -561,6 +576,7 @@ class BatchPlan(GeometryMixin):
         z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=dev)
         self.xb = z(bs, ex.in_H * ex.in_W * ex.in_Cs)
         self.yb = z(bs, ex.plan.head.N, dt=torch.float32)
+        self.wb = z(max(bs, 1), dt=torch.float32) if self.weighted else None   # gathered sample weights
         self.conv_out, self.conv_code, self.conv_dy = [], [], []
         for g in ex.convs:
             self.conv_out.append(z(bs, g.Hp, g.Wp, g.Cs_out))
@@ -668,6 +684,8 @@ class BatchPlan(GeometryMixin):
         ga.R = self.xb.shape[1]
         ga.xb = self.xb.data_ptr()
         ga.yb = self.yb.data_ptr()
+        if self.weighted:
+            ga.wb = self.wb.data_ptr()
         # one prologue launch: gather + the previous update's weight re-pack (training: always,
         # except with per-bucket optimizers that pack themselves; eval/predict: only if an
         # optimizer ran since the last pack) + the step bookkeeping
@@ -777,6 +795,10 @@ class BatchPlan(GeometryMixin):
         h.y = self.yb.data_ptr() if self.mode != "predict" else 0
         if self.pro_free and h.y:
             h.yidx = self.srcidx.data_ptr()      # targets straight from the dataset rows
+        if self.weighted and h.y:
+            # the weighted head instances; the rows' weights from the gathered batch, or with
+            # yidx from the bound data set's weights (StepState::data_w) like the targets
+            h.wb = self.wb.data_ptr()
         h.act = ex.head_act
         if head_epi is not None:
             h.epi = head_epi

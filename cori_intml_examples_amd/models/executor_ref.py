@@ -36,13 +36,16 @@ class RefExecutor(Executor):
         self.emulate_bf16 = bool(tune("ref_bf16", False))
 
     # ------------------------------------------------------------------------------ data
-    def upload(self, x, y):
+    def upload(self, x, y, w=None):
         xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
         if xt.shape[1:] != tuple(self.plan.input_shape):
             raise ValueError("input shape %s != model input %s" % (tuple(xt.shape[1:]),
                                                                    self.plan.input_shape))
         yt = torch.as_tensor(prepare_targets(y, self.plan)) if y is not None else None
-        return DeviceData(xt, yt, xt.shape[0])
+        wt = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).reshape(-1) if w is not None else None
+        if wt is not None and wt.shape[0] != xt.shape[0]:
+            raise ValueError("sample weights have %d entries for %d samples" % (wt.shape[0], xt.shape[0]))
+        return DeviceData(xt, yt, xt.shape[0], wt)
 
     # ------------------------------------------------------------------------------ core
     def _mask(self, numel, rate, stream, step):
@@ -91,14 +94,20 @@ class RefExecutor(Executor):
             z = z + st.view(hd.dense, "bias")
         return z, a, saved
 
-    def _head_loss(self, z, y):
+    def _head_loss(self, z, y, w=None):
+        """Per-row (loss, dlogits, correct); with weights w [M], loss and dlogits carry the row
+        factor w_i * M / nnz (R.weight_factor), the accuracy stays unweighted."""
         hd = self.plan.head
         if hd.activation == "softmax":
-            return R.softmax_cce(z, y)
-        if hd.activation == "sigmoid":
+            loss, dz, corr = R.softmax_cce(z, y)
+        elif hd.activation == "sigmoid":
             loss, dz, corr = R.sigmoid_bce(z.reshape(-1), y.reshape(-1))
-            return loss, dz.reshape(-1, 1), corr
-        return R.mse(z, y)
+            dz = dz.reshape(-1, 1)
+        else:
+            loss, dz, corr = R.mse(z, y)
+        if w is not None:
+            loss, dz = R.apply_weights(loss, dz, w)
+        return loss, dz, corr
 
     def _backward(self, dz, a_head, saved):
         st = self.store
@@ -179,11 +188,12 @@ class RefExecutor(Executor):
     def train_step(self, data: DeviceData, perm: torch.Tensor, pos: int, bs: int) -> None:
         idx = perm[pos:pos + bs]
         x, y = data.x[idx], data.y[idx]
+        w = data.w[idx] if data.w is not None else None
         base = getattr(self.optimizer, "_base_optimizer", self.optimizer)
         step = base.iterations + 1
         with torch.no_grad():
             z, a_head, saved = self._forward(x, True, step)
-            loss, dz, corr = self._head_loss(z, y)
+            loss, dz, corr = self._head_loss(z, y, w)
             self._backward(dz / bs, a_head, saved)
             if self.reducer is not None:
                 if not getattr(self, "_buckets_configured", False):
@@ -203,9 +213,10 @@ class RefExecutor(Executor):
 
     def eval_step(self, data: DeviceData, pos: int, bs: int) -> None:
         x, y = data.x[pos:pos + bs], data.y[pos:pos + bs]
+        w = data.w[pos:pos + bs] if data.w is not None else None
         with torch.no_grad():
             z, _, _ = self._forward(x, False, 0)
-            loss, _, corr = self._head_loss(z, y)
+            loss, _, corr = self._head_loss(z, y, w)
         self._accumulate(loss, corr, bs)
 
     def predict_step(self, data: DeviceData, pos: int, bs: int) -> torch.Tensor:

@@ -21,7 +21,7 @@ import torch
 from .. import optim as optimizers
 from ..train import callbacks as cbks
 from ..utils.env import default_device, next_seed
-from .executor_base import DeviceData
+from .executor_base import DeviceData, standardize_weights
 from .layers import Dense, InputLayer, KTensor, Layer
 from .params import ParamStore
 from .plan import build_plan, canonical_loss
@@ -185,23 +185,35 @@ class Model:
             **kwargs):
         from ..train.loop import fit_loop
         self._check_compiled()
-        if class_weight is not None or sample_weight is not None:
-            raise NotImplementedError("class_weight / sample_weight in fit")
         if steps_per_epoch is not None:
             raise NotImplementedError("steps_per_epoch")
         return fit_loop(self, x, y, batch_size or 32, epochs, verbose, callbacks, validation_split,
-                        validation_data, shuffle, initial_epoch)
+                        validation_data, shuffle, initial_epoch, sample_weight, class_weight)
 
     def evaluate(self, x=None, y=None, batch_size=None, verbose=1, sample_weight=None, steps=None):
         self._check_compiled()
         ex = self._executor
-        data = x if isinstance(x, DeviceData) else ex.upload(x, y)
+        data = self._upload_weighted(x, y, sample_weight, None)
         self._run_eval(data, batch_size or 32)
         loss, acc, _ = ex.read_metrics()
         if verbose:
             print("%d/%d [==============================] - loss: %.4f%s" % (
                 data.n, data.n, loss, (" - acc: %.4f" % acc) if self.metrics else ""))
         return [loss, acc] if self.metrics else loss
+
+    def _upload_weighted(self, x, y, sample_weight=None, class_weight=None):
+        """(x, y) on the executor's device with the per-sample loss weights Keras'
+        ``standardize_weights`` derives from ``sample_weight`` / ``class_weight``.  A DeviceData
+        is used as is, or re-wrapped (same tensors) with the weights attached."""
+        ex = self._executor
+        if isinstance(x, DeviceData):
+            w = standardize_weights(x.y.detach().cpu().numpy() if class_weight is not None else None, x.n,
+                                    sample_weight, class_weight)
+            if w is None:
+                return x
+            return DeviceData(x.x, x.y, x.n, torch.as_tensor(w).to(x.y.device))
+        w = standardize_weights(y, len(x), sample_weight, class_weight)
+        return ex.upload(x, y, w) if w is not None else ex.upload(x, y)
 
     def _run_eval(self, data, batch_size):
         ex = self._executor
@@ -243,18 +255,18 @@ class Model:
             return p.argmax(axis=-1)
         return (p > 0.5).astype("int32")
 
-    def train_on_batch(self, x, y):
+    def train_on_batch(self, x, y, sample_weight=None, class_weight=None):
         self._check_compiled()
         ex = self._executor
-        data = ex.upload(x, y)
+        data = self._upload_weighted(x, y, sample_weight, class_weight)
         ex.reset_metrics()
         perm = torch.arange(data.n, device=ex.device)
         ex.train_step(data, perm, 0, data.n)
         loss, acc, _ = ex.read_metrics()
         return [loss, acc] if self.metrics else loss
 
-    def test_on_batch(self, x, y):
-        return self.evaluate(x, y, batch_size=len(x), verbose=0)
+    def test_on_batch(self, x, y, sample_weight=None):
+        return self.evaluate(x, y, batch_size=len(x), verbose=0, sample_weight=sample_weight)
 
     # ------------------------------------------------------------------ summary
     def summary(self, line_length=None, positions=None, print_fn=None):

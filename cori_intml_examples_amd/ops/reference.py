@@ -133,6 +133,25 @@ def mse(out: torch.Tensor, y: torch.Tensor):
     return loss, dz, torch.zeros(out.shape[0], device=out.device)
 
 
+def weight_factor(w: torch.Tensor) -> torch.Tensor:
+    """Row factors of the sample-weighted loss (Keras 2.2 ``weighted_masked_objective``) for one
+    batch of weights w [M]: w_i * (M / nnz), nnz = number of non-zero weights.  Scaling the
+    per-row (loss, dlogits) by it gives rows that sum to M * L_batch with
+    L_batch = sum(w l) / nnz -- the batch's contribution to Keras' epoch mean -- and, after the
+    step's 1/M, the gradient of L_batch.  A batch of all-zero weights (0/0 in Keras) gives
+    zero factors: the divisor is clamped to 1.  All-ones weights give exactly 1.0."""
+    w = w.reshape(-1).to(torch.float32)
+    nnz = max(int((w != 0).sum()), 1)
+    scale = torch.tensor(float(w.shape[0]), dtype=torch.float32) / torch.tensor(float(nnz), dtype=torch.float32)
+    return w * scale
+
+
+def apply_weights(loss: torch.Tensor, dz: torch.Tensor, w: torch.Tensor):
+    """(loss, dz) per row scaled by weight_factor(w); dz [M] or [M, N]."""
+    f = weight_factor(w)
+    return loss * f, dz * (f if dz.dim() == 1 else f.unsqueeze(-1))
+
+
 # --------------------------------------------------------------------------- optimizers (Keras 2.2)
 def adam_update(p, g, m, v, t: int, lr: float, beta_1=0.9, beta_2=0.999, eps=EPS):
     lr_t = lr * math.sqrt(1.0 - beta_2 ** t) / (1.0 - beta_1 ** t)

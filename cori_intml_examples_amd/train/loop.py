@@ -23,25 +23,27 @@ import torch
 from . import callbacks as cbks
 
 
-def _split_validation(x, y, validation_split, validation_data):
+def _split_validation(x, y, validation_split, validation_data, w=None):
+    """(x, y, w, vx, vy, vw): ``w`` / ``vw`` are per-sample loss weights or None.  The
+    validation split slices the weights with x and y (last fraction, before shuffling)."""
     from ..models.executor_base import DeviceData
     if isinstance(x, DeviceData) and validation_data is None and validation_split and 0.0 < validation_split < 1.0:
         from ..io.synth import split
         tr, va = split(x, validation_split)
-        return tr, None, va, None
+        return tr, None, None, va, None, None
     if validation_data is not None:
+        vw = None
         if len(validation_data) == 3:
             vx, vy, vw = validation_data
-            if vw is not None:
-                raise NotImplementedError("validation sample weights")
         else:
             vx, vy = validation_data
-        return x, y, vx, vy
+        return x, y, w, vx, vy, vw
     if validation_split and 0.0 < validation_split < 1.0:
         n = len(x)
         split_at = int(n * (1.0 - validation_split))
-        return x[:split_at], y[:split_at], x[split_at:], y[split_at:]
-    return x, y, None, None
+        return (x[:split_at], y[:split_at], None if w is None else w[:split_at],
+                x[split_at:], y[split_at:], None if w is None else w[split_at:])
+    return x, y, w, None, None, None
 
 
 def shard_indices(n: int, rank: int, size: int, shuffle: bool, seed: int, epoch: int) -> torch.Tensor:
@@ -60,11 +62,18 @@ def shard_indices(n: int, rank: int, size: int, shuffle: bool, seed: int, epoch:
 
 
 def fit_loop(model, x, y, batch_size, epochs, verbose, callbacks, validation_split, validation_data,
-             shuffle, initial_epoch):
-    from ..models.executor_base import DeviceData
+             shuffle, initial_epoch, sample_weight=None, class_weight=None):
+    from ..models.executor_base import DeviceData, standardize_weights
     from ..parallel import state as dp_state
     ex = model._executor
-    x, y, vx, vy = _split_validation(x, y, validation_split, validation_data)
+    if isinstance(x, DeviceData):
+        x = model._upload_weighted(x, None, sample_weight, class_weight)   # (weights attached to the set)
+        w = None
+    else:
+        w = standardize_weights(y, len(x), sample_weight, class_weight)
+    x, y, w, vx, vy, vw = _split_validation(x, y, validation_split, validation_data, w)
+    if vw is not None and not isinstance(vx, DeviceData):
+        vw = standardize_weights(vy, len(vx), vw, None)
 
     # data-parallel sharding (default) or the reference's replicated semantics.  Sharded: every
     # rank keeps the WHOLE training set resident (HBM is not the constraint for these data
@@ -78,9 +87,14 @@ def fit_loop(model, x, y, batch_size, epochs, verbose, callbacks, validation_spl
         shard = (dp.rank, dp.size, int(_dist.broadcast_object(int(model._seed) & 0x7FFFFFFF, 0)))
 
     # (a DeviceData -- e.g. io.synth.for_model, generated on the device -- is used as is)
-    train = x if isinstance(x, DeviceData) else ex.upload(x, y)
+    train = x if isinstance(x, DeviceData) else (ex.upload(x, y, w) if w is not None else ex.upload(x, y))
     n_local = train.n // shard[1] if shard else train.n
-    val = vx if isinstance(vx, DeviceData) else (ex.upload(vx, vy) if vx is not None else None)
+    if isinstance(vx, DeviceData):
+        val = model._upload_weighted(vx, None, vw, None)
+    elif vx is not None:
+        val = ex.upload(vx, vy, vw) if vw is not None else ex.upload(vx, vy)
+    else:
+        val = None
     do_val = val is not None
 
     model.history = cbks.History()
