@@ -67,6 +67,9 @@ struct OptimArgs {
   // reduction kernels only: write the reduced gradient and stop (no update, no packs) -- the
   // data-parallel step reduces early buckets' slabs ahead of the all-reduce this way
   int grad_only = 0;
+  // third state buffer (AMSGrad's running maximum of v): read and written by the OPT_AMSGRAD
+  // instances only
+  float* s2 = nullptr;
 };
 
 // Implicit-GEMM convolution / 1x1 "dense as conv" (fwd, dgrad, dense-dX).

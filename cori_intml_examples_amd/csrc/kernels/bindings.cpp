@@ -221,7 +221,7 @@ PYBIND11_MODULE(_kernels, m) {
 
   py::class_<OptimArgs>(m, "OptimArgs")
       .def(py::init<>())
-      PTR(OptimArgs, p) PTR(OptimArgs, g) PTR(OptimArgs, s0) PTR(OptimArgs, s1) RW(OptimArgs, n) RW(OptimArgs, lo)
+      PTR(OptimArgs, p) PTR(OptimArgs, g) PTR(OptimArgs, s0) PTR(OptimArgs, s1) PTR(OptimArgs, s2) RW(OptimArgs, n) RW(OptimArgs, lo)
       PTR(OptimArgs, st) RW(OptimArgs, kind) RW(OptimArgs, beta1) RW(OptimArgs, beta2) RW(OptimArgs, eps)
       RW(OptimArgs, rho) RW(OptimArgs, momentum) RW(OptimArgs, nesterov) RW(OptimArgs, grad_scale)
       RW(OptimArgs, grad_only)
@@ -345,6 +345,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("STEP_STATE_METRIC_SLOTS") = 16;
   m.attr("STEP_STATE_MSCHED_OFFSET") = (int)offsetof(StepState, m_schedule);
   m.attr("STEP_STATE_LR_OFFSET") = (int)offsetof(StepState, lr);
+  m.attr("STEP_STATE_S_OFFSET") = (int)offsetof(StepState, s);
   m.attr("STEP_STATE_WARM_OFFSET") = (int)offsetof(StepState, warm_t0);
   m.attr("STEP_STATE_DATA_OFFSET") = (int)offsetof(StepState, data_x);
   m.attr("STEP_STATE_DATAN_OFFSET") = (int)offsetof(StepState, data_n);
@@ -415,6 +416,9 @@ PYBIND11_MODULE(_kernels, m) {
          const RedTable* rt, const OptimArgs* ro, uintptr_t rgrad, int rfirst, const XgmiPush* xp) {
         DualExtra x;
         if (rt && ro && rt->nblocks > 0) {
+          // (the extras' run-time switch, reduce_optim_block_rt; a grad_only table updates nothing)
+          if (!ro->grad_only && !opt_kind_five_way(ro->kind))
+            throw std::invalid_argument("dual_halo: no early update for optimizer kind " + std::to_string(ro->kind));
           x.rt = *rt, x.ro = *ro, x.grad = reinterpret_cast<float*>(rgrad);
           x.n_r = rt->nblocks, x.rfirst = rfirst;
           if (xp && xp->on) {

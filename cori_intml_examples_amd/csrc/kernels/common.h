@@ -192,7 +192,14 @@ struct StepState {
   unsigned long long data_w;
 };
 
-enum OptKind { OPT_SGD = 0, OPT_RMSPROP = 1, OPT_ADADELTA = 2, OPT_ADAM = 3, OPT_NADAM = 4 };
+enum OptKind {
+  OPT_SGD = 0, OPT_RMSPROP = 1, OPT_ADADELTA = 2, OPT_ADAM = 3, OPT_NADAM = 4,
+  // instances of optim_kernel / reduce_optim_kernel only (misc.hip): the run-time switches of
+  // the dual launch's extras, the dense wgrad and the xGMI kernels stay five-way
+  OPT_ADAGRAD = 5, OPT_ADAMAX = 6, OPT_AMSGRAD = 7
+};
+// host launchers of a kernel with such a five-way switch refuse every other kind
+inline bool opt_kind_five_way(int kind) { return kind >= OPT_SGD && kind <= OPT_NADAM; }
 
 // ---------------------------------------------------------------------------------------
 // Pack / unpack descriptors (fp32 master <-> bf16 fragment packs, grad slabs -> master layout)

@@ -34,6 +34,7 @@
 // fewer, longer wgrad workgroups run.
 #include <algorithm>
 #include <stdexcept>
+#include <string>
 
 #include "dense_body.h"
 #include "optim_math.h"
@@ -408,6 +409,8 @@ static void dense_wgrad_check(const WgradArgs& a, int kg, int ntt, int splits) {
   if (a.opt_w >= 0 && (splits != 1 || a.opt.p == nullptr || a.opt.st == nullptr || a.opt_w % 4 ||
                        (a.NT * 16) % 4))
     throw std::runtime_error("dense_wgrad: fused optimizer needs one split and float4-aligned rows");
+  if (a.opt_w >= 0 && !opt_kind_five_way(a.opt.kind))   // (dw_opt's run-time switch)
+    throw std::invalid_argument("dense_wgrad: no fused update for optimizer kind " + std::to_string(a.opt.kind));
   if (a.pk_fwd >= 0 && (a.opt_w < 0 || a.opt.arena == nullptr || kg != 2 || (a.pk_bwd >= 0 && (ntt & 1)) ||
                         a.Cs_in % 32 || (a.NT * 16) % 32))
     throw std::runtime_error("dense_wgrad: fused pack writes need the fused optimizer, 32-feature tiles and "

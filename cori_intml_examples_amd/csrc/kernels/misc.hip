@@ -6,11 +6,12 @@
 //                            bias-correction scalars) by the last workgroup
 //   slab_reduce  (K6/K9 2nd) deterministic fixed-order sum of split partial slabs into the
 //                            flat fp32 gradient buffer, remapped to Keras layout
-//   optim_update (K13)       ONE multi-tensor launch over the flat buffer: Adam / Nadam /
-//                            Adadelta / RMSprop / SGD with Keras 2.2 math, DP averaging
+//   optim_update (K13)       ONE multi-tensor launch over the flat buffer: Adam / AMSGrad / Adamax /
+//                            Nadam / Adadelta / Adagrad / RMSprop / SGD with Keras 2.2 math, DP averaging
 //                            folded in (grad_scale), and the bf16 fragment-major weight
 //                            packs the MFMA kernels read scattered out in the same pass
 #include <stdexcept>
+#include <string>
 
 #include "args.h"
 #include "optim_math.h"
@@ -253,14 +254,17 @@ __device__ __forceinline__ void optim_tile_block(const OptimArgs& a, int tb, bf1
   const float4 g = *reinterpret_cast<const float4*>(a.g + e);
   float4 s0 = a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : float4{0.f, 0.f, 0.f, 0.f};
   float4 s1 = a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : float4{0.f, 0.f, 0.f, 0.f};
+  float4 s2 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (KIND == OPT_AMSGRAD) s2 = *reinterpret_cast<const float4*>(a.s2 + e);
   const float gs = a.grad_scale;
-  opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x);
-  opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y);
-  opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z);
-  opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w);
+  opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
+  opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
+  opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
+  opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
   *reinterpret_cast<float4*>(a.p + e) = p;
   if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
   if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
+  if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
   bf16 (*sl)[40] = tile[wave];
   sl[r][c4] = f2bf(p.x);
   sl[r][c4 + 1] = f2bf(p.y);
@@ -309,21 +313,24 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
   const float4 g = *reinterpret_cast<const float4*>(a.g + e);
   float4 s0 = a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : float4{0.f, 0.f, 0.f, 0.f};
   float4 s1 = a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : float4{0.f, 0.f, 0.f, 0.f};
+  float4 s2 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (KIND == OPT_AMSGRAD) s2 = *reinterpret_cast<const float4*>(a.s2 + e);
   const float gs = a.grad_scale;
   if (e >= a.lo && e + 4 <= end) {
-    opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x);
-    opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y);
-    opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z);
-    opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w);
+    opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
+    opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
+    opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
+    opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
   } else {
-    if (e >= a.lo && e < end) opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x);
-    if (e + 1 >= a.lo && e + 1 < end) opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y);
-    if (e + 2 >= a.lo && e + 2 < end) opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z);
-    if (e + 3 >= a.lo && e + 3 < end) opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w);
+    if (e >= a.lo && e < end) opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
+    if (e + 1 >= a.lo && e + 1 < end) opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
+    if (e + 2 >= a.lo && e + 2 < end) opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
+    if (e + 3 >= a.lo && e + 3 < end) opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
   }
   *reinterpret_cast<float4*>(a.p + e) = p;
   if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
   if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
+  if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
   if (a.nroutes) {
     if (e >= a.lo && e + 4 <= end) {
       pack_write4(a, e, p);
@@ -337,8 +344,21 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
   if (a.defer_pack && !a.nroutes && blockIdx.x == 0 && threadIdx.x == 0) a.st->packs_stale = 1;
 }
 
+// the state buffers a kind's instances read and write unconditionally
+static void check_state_slots(const OptimArgs& a) {
+  const int need = a.kind == OPT_AMSGRAD ? 3 : (a.kind == OPT_ADAMAX ? 2 : (a.kind == OPT_ADAGRAD ? 1 : 0));
+  if ((need > 0 && !a.s0) || (need > 1 && !a.s1) || (need > 2 && !a.s2))
+    throw std::invalid_argument("optimizer kind " + std::to_string(a.kind) + ": missing state buffer");
+}
+// the table kernels that choose the optimizer at run time (xgmi_early_block) know five kinds
+static void check_five_way(const OptimArgs& a, const char* what) {
+  if (!a.grad_only && !opt_kind_five_way(a.kind))
+    throw std::invalid_argument(std::string(what) + ": no kernel instance for optimizer kind " + std::to_string(a.kind));
+}
+
 void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s) {
   if (a.n > 0 && !a.pack_only) {
+    check_state_slots(a);
     const int span = a.lo + a.n - (a.lo & ~3);
     const int flat = ((span + 3) / 4 + 255) / 256;
     if (a.ntile && a.flat_blocks != flat) throw std::invalid_argument("optim: flat_blocks mismatch");
@@ -348,7 +368,11 @@ void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s) {
       case OPT_NADAM: hipLaunchKernelGGL(optim_kernel<OPT_NADAM>, grid, dim3(256), 0, s, a); break;
       case OPT_ADADELTA: hipLaunchKernelGGL(optim_kernel<OPT_ADADELTA>, grid, dim3(256), 0, s, a); break;
       case OPT_RMSPROP: hipLaunchKernelGGL(optim_kernel<OPT_RMSPROP>, grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL(optim_kernel<OPT_SGD>, grid, dim3(256), 0, s, a); break;
+      case OPT_ADAGRAD: hipLaunchKernelGGL(optim_kernel<OPT_ADAGRAD>, grid, dim3(256), 0, s, a); break;
+      case OPT_ADAMAX: hipLaunchKernelGGL(optim_kernel<OPT_ADAMAX>, grid, dim3(256), 0, s, a); break;
+      case OPT_AMSGRAD: hipLaunchKernelGGL(optim_kernel<OPT_AMSGRAD>, grid, dim3(256), 0, s, a); break;
+      case OPT_SGD: hipLaunchKernelGGL(optim_kernel<OPT_SGD>, grid, dim3(256), 0, s, a); break;
+      default: throw std::invalid_argument("optim: no kernel instance for optimizer kind " + std::to_string(a.kind));
     }
   }
   if (!a.defer_pack || a.pack_only)
@@ -417,7 +441,8 @@ static void launch_fused(float* grad, const RedTable& tc, const OptimArgs& a, co
     case OPT_RMSPROP:
       hipLaunchKernelGGL((xchg_fused_kernel<OPT_RMSPROP, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc);
       break;
-    default: hipLaunchKernelGGL((xchg_fused_kernel<OPT_SGD, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc); break;
+    case OPT_SGD: hipLaunchKernelGGL((xchg_fused_kernel<OPT_SGD, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc); break;
+    default: throw std::invalid_argument("xGMI exchange: no kernel instance for optimizer kind " + std::to_string(a.kind));
   }
 }
 
@@ -431,6 +456,7 @@ void launch_reduce_optim_end(float* grad, const RedTable& tc, const OptimArgs& a
   const int nc = tc.nblocks <= 0 ? 0 : (xc.nx ? xc.nx : tc.nblocks);
   const int ne = te.nblocks <= 0 ? 0 : (xe.nx ? xe.nx : te.nblocks);
   if (nc + ne == 0) return;
+  check_five_way(a, "reduce_optim_end");
   if (fused_mode3(xc) && !xe.nx) {
     launch_fused<true>(grad, tc, a, xc, te, xe, nc, ne, s);
     return;
@@ -444,6 +470,7 @@ void launch_reduce_optim(float* grad, const RedTable& tab, const OptimArgs& a, h
   if (xp && xp->on) {
     const int grid = xp->mode >= 2 && xp->nx ? xp->nx : (xp->mode == 4 ? xp->b_hi - xp->b_lo : tab.nblocks);
     if (grid <= 0) return;
+    check_five_way(a, "reduce_optim (xGMI table)");
     if (fused_mode3(*xp)) {
       launch_fused<false>(grad, tab, a, *xp, tab, *xp, grid, 0, s);
       return;
@@ -452,11 +479,16 @@ void launch_reduce_optim(float* grad, const RedTable& tab, const OptimArgs& a, h
     return;
   }
   const dim3 g(tab.nblocks), b(256);
+  if (!a.grad_only) check_state_slots(a);
   switch (a.kind) {
     case OPT_ADAM: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAM>, g, b, 0, s, grad, tab, a); break;
     case OPT_NADAM: hipLaunchKernelGGL(reduce_optim_kernel<OPT_NADAM>, g, b, 0, s, grad, tab, a); break;
     case OPT_ADADELTA: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADADELTA>, g, b, 0, s, grad, tab, a); break;
     case OPT_RMSPROP: hipLaunchKernelGGL(reduce_optim_kernel<OPT_RMSPROP>, g, b, 0, s, grad, tab, a); break;
-    default: hipLaunchKernelGGL(reduce_optim_kernel<OPT_SGD>, g, b, 0, s, grad, tab, a); break;
+    case OPT_ADAGRAD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAGRAD>, g, b, 0, s, grad, tab, a); break;
+    case OPT_ADAMAX: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAMAX>, g, b, 0, s, grad, tab, a); break;
+    case OPT_AMSGRAD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_AMSGRAD>, g, b, 0, s, grad, tab, a); break;
+    case OPT_SGD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_SGD>, g, b, 0, s, grad, tab, a); break;
+    default: throw std::invalid_argument("reduce_optim: no kernel instance for optimizer kind " + std::to_string(a.kind));
   }
 }

@@ -1,5 +1,5 @@
-// Keras-2.2 optimizer update of ONE element (Adam / Nadam / Adadelta / RMSprop / SGD with
-// momentum / Nesterov), shared by the multi-tensor optimizer, the fused reduce+optimizer
+// Keras-2.2 optimizer update of ONE element (Adam / AMSGrad / Adamax / Nadam / Adadelta / Adagrad /
+// RMSprop / SGD with momentum / Nesterov), shared by the multi-tensor optimizer, the fused reduce+optimizer
 // and the fused xGMI all-reduce+optimizer kernels.  Per-step scalars (bias-corrected LR,
 // Nadam schedule) come from the device StepState written by the step bookkeeping.
 #pragma once
@@ -7,8 +7,32 @@
 
 template <int KIND>
 __device__ __forceinline__ void opt_update(const OptimArgs& a, const StepState* st, float& p, float g, float* s0,
-                                           float* s1) {
-  if (KIND == OPT_ADAM) {
+                                           float* s1, float* s2 = nullptr) {
+  // The three kinds below run in optim_kernel (data-parallel step, fuse_optim=0) and in
+  // reduce_optim_kernel (single-GPU step): no fp contraction, so both give the same bits
+  // whatever the surrounding code lets the compiler fuse
+  if (KIND == OPT_AMSGRAD) {          // s2: the running maximum of v (only this kind touches it)
+#pragma clang fp contract(off)
+    const float m = a.beta1 * *s0 + (1.f - a.beta1) * g;
+    const float v = a.beta2 * *s1 + (1.f - a.beta2) * g * g;
+    const float vhat = fmaxf(*s2, v);
+    *s0 = m;
+    *s1 = v;
+    *s2 = vhat;
+    p -= st->s[0] * m / (sqrtf(vhat) + a.eps);
+  } else if (KIND == OPT_ADAMAX) {    // st->s[0] = lr / (1 - beta1^t)
+#pragma clang fp contract(off)
+    const float m = a.beta1 * *s0 + (1.f - a.beta1) * g;
+    const float u = fmaxf(a.beta2 * *s1, fabsf(g));
+    *s0 = m;
+    *s1 = u;
+    p -= st->s[0] * m / (u + a.eps);
+  } else if (KIND == OPT_ADAGRAD) {
+#pragma clang fp contract(off)
+    const float acc = *s0 + g * g;
+    *s0 = acc;
+    p -= st->s[0] * g / (sqrtf(acc) + a.eps);
+  } else if (KIND == OPT_ADAM) {
     const float m = a.beta1 * *s0 + (1.f - a.beta1) * g;
     const float v = a.beta2 * *s1 + (1.f - a.beta2) * g * g;
     *s0 = m;

@@ -157,19 +157,28 @@ __device__ __forceinline__ void xpush4(const XgmiPush& xp, long long e, const fl
 // The optimizer state of the elements a thread will update, loaded BEFORE the reduction whose
 // result it updates them with: its memory round trip overlaps the slab loads instead of
 // following them (~1 us of the reduction launch's latency chain)
+// (s2: the third buffer, OPT_AMSGRAD instances only -- load_state2; dead in every other one)
 struct OptState4 {
-  float4 p, s0, s1;
+  float4 p, s0, s1, s2;
 };
 struct OptState1 {
-  float p, s0, s1;
+  float p, s0, s1, s2;
 };
 __device__ __forceinline__ OptState4 load_state4(const OptimArgs& a, int e) {
   const float4 z = {0.f, 0.f, 0.f, 0.f};
   return OptState4{*reinterpret_cast<const float4*>(a.p + e), a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : z,
-                   a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : z};
+                   a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : z, z};
 }
 __device__ __forceinline__ OptState1 load_state1(const OptimArgs& a, int e) {
-  return OptState1{a.p[e], a.s0 ? a.s0[e] : 0.f, a.s1 ? a.s1[e] : 0.f};
+  return OptState1{a.p[e], a.s0 ? a.s0[e] : 0.f, a.s1 ? a.s1[e] : 0.f, 0.f};
+}
+template <int KIND>
+__device__ __forceinline__ void load_state2(const OptimArgs& a, int e, OptState4& st) {
+  if constexpr (KIND == OPT_AMSGRAD) st.s2 = *reinterpret_cast<const float4*>(a.s2 + e);
+}
+template <int KIND>
+__device__ __forceinline__ void load_state2(const OptimArgs& a, int e, OptState1& st) {
+  if constexpr (KIND == OPT_AMSGRAD) st.s2 = a.s2[e];
 }
 
 // Keras update of the elements a table block's thread holds (vec4 descriptor: the float4 at
@@ -189,15 +198,16 @@ __device__ __forceinline__ void update_vec4(const RedDesc& dsc, const OptimArgs&
   }
   bf16* tl = reinterpret_cast<bf16*>(red);
   if (mine) {
-    float4 p = st.p, s0 = st.s0, s1 = st.s1;
+    float4 p = st.p, s0 = st.s0, s1 = st.s1, s2 = st.s2;
     const float gs = a.grad_scale;
-    opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x);
-    opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y);
-    opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z);
-    opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w);
+    opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
+    opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
+    opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
+    opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
     *reinterpret_cast<float4*>(a.p + e) = p;
     if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
     if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
+    if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
     if (tr) {
       bf16x4 v;
       v[0] = f2bf(p.x); v[1] = f2bf(p.y); v[2] = f2bf(p.z); v[3] = f2bf(p.w);
@@ -229,11 +239,12 @@ __device__ __forceinline__ void update_vec4(const RedDesc& dsc, const OptimArgs&
 
 template <int KIND>
 __device__ __forceinline__ void update_elem(const OptimArgs& a, int e, float g, const OptState1& st) {
-  float p = st.p, s0 = st.s0, s1 = st.s1;
-  opt_update<KIND>(a, a.st, p, g * a.grad_scale, &s0, &s1);
+  float p = st.p, s0 = st.s0, s1 = st.s1, s2 = st.s2;
+  opt_update<KIND>(a, a.st, p, g * a.grad_scale, &s0, &s1, &s2);
   a.p[e] = p;
   if (a.s0) a.s0[e] = s0;
   if (a.s1) a.s1[e] = s1;
+  if constexpr (KIND == OPT_AMSGRAD) a.s2[e] = s2;
   if (a.nroutes) pack_write(a, e, p);
 }
 
@@ -253,27 +264,27 @@ __device__ __forceinline__ void reduce_optim_block(float* __restrict__ grad, con
     OptState4 st{};
     if (PRE && upd) {   // (slab_reduce_vec4's map: split-lane 0 of element group t % G holds the sum)
       const int G = 256 / dsc.tpe, le = ((blk - dsc.blk0) * G + t % G) * 4;
-      if (t < G && le < dsc.numel) st = load_state4(a, dsc.dst_off + le);
+      if (t < G && le < dsc.numel) st = load_state4(a, dsc.dst_off + le), load_state2<KIND>(a, dsc.dst_off + le, st);
     }
     int e;
     float4 g;
     const bool mine = slab_reduce_vec4(dsc, blk, red, e, g);
     if (mine) *reinterpret_cast<float4*>(grad + e) = g;
     if (mine && xp) xpush4(*xp, e, g);
-    if (!PRE && mine && upd) st = load_state4(a, e);
+    if (!PRE && mine && upd) st = load_state4(a, e), load_state2<KIND>(a, e, st);
     if (upd) update_vec4<KIND>(dsc, a, blk, red, mine, e, g, st);   // (grad_only: the reduced gradient is all)
   } else {
     OptState1 st{};
     if (PRE && upd) {   // (slab_reduce_elem's map: thread t < E holds element t of the block)
       const int E = 256 / dsc.tpe, le = (blk - dsc.blk0) * E + t;
-      if (t < E && le < dsc.numel) st = load_state1(a, dsc.dst_off + le);
+      if (t < E && le < dsc.numel) st = load_state1(a, dsc.dst_off + le), load_state2<KIND>(a, dsc.dst_off + le, st);
     }
     int e;
     float g;
     const bool mine = slab_reduce_elem(tab, blk, red, e, g);
     if (mine) grad[e] = g;
     if (mine && xp) xpush1(*xp, e, g);
-    if (!PRE && mine && upd) st = load_state1(a, e);
+    if (!PRE && mine && upd) st = load_state1(a, e), load_state2<KIND>(a, e, st);
     if (mine && upd) update_elem<KIND>(a, e, g, st);
   }
   if (a.defer_pack && !a.nroutes && upd && blk == 0 && threadIdx.x == 0) a.st->packs_stale = 1;

@@ -23,11 +23,15 @@ __device__ __forceinline__ void step_bookkeeping(const StepBeginArgs& a, bool wr
   const double lr = base / (1.0 + (double)a.decay * (t - 1.0));
   st->lr_eff = (float)lr;
   switch (a.opt_kind) {
-    case OPT_ADAM: {
+    case OPT_ADAM:
+    case OPT_AMSGRAD: {
       const double b1t = pow((double)a.beta1, t), b2t = pow((double)a.beta2, t);
       st->s[0] = (float)(lr * sqrt(1.0 - b2t) / (1.0 - b1t));
       break;
     }
+    case OPT_ADAMAX:
+      st->s[0] = (float)(lr / (1.0 - pow((double)a.beta1, t)));
+      break;
     case OPT_NADAM: {
       const double b1 = a.beta1;
       const double mc_t = b1 * (1.0 - 0.5 * pow(0.96, t * a.schedule_decay));

@@ -274,7 +274,9 @@ void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s) {
     case OPT_NADAM: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_NADAM>, grid, block, 0, s, a); break;
     case OPT_ADADELTA: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_ADADELTA>, grid, block, 0, s, a); break;
     case OPT_RMSPROP: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_RMSPROP>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_SGD>, grid, block, 0, s, a); break;
+    case OPT_SGD:
+    case -1: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_SGD>, grid, block, 0, s, a); break;   // (-1: sum only)
+    default: throw std::invalid_argument("xgmi all-reduce: no kernel instance for optimizer kind " + std::to_string(a.opt.kind));
   }
 }
 

@@ -15,8 +15,9 @@ File layout, written through the native ``_h5lite`` mod
     /optimizer_weights      attr  weight_names; one dataset per optimizer variable
 
 Optimizer variables follow Keras 2.2.4's ``Optimizer.weights`` order:
-Adam ``[iterations] + m + v + vhat``, Nadam ``[iterations] + m + v``, Adadelta
-``accumulators + delta_accumulators``, RMSprop ``accumulators``, SGD ``[iterations] + moments``.
+Adam ``[iterations] + m + v + vhat`` (vhat parameter-shaped with ``amsgrad``, else shape-(1,) zeros),
+Adamax ``[iterations] + m + u``, Nadam ``[iterations] + m + v``, Adadelta
+``accumulators + delta_accumulators``, RMSprop / Adagrad ``accumulators``, SGD ``[iterations] + moments``.
 The DistributedOptimizer wrapper serialises under its base class name so the file
 reloads without the parallel package (Appendix B.2 last bullet).  Writes go to a
 temporary file that is renamed into place, so a crash mid-save never leaves a torn
@@ -59,8 +60,13 @@ def _opt_layout(opt, n_params):
         for k in (0, 1):
             for i in range(n_params):
                 out.append((None, ("slot", k, i)))
-        for i in range(n_params):
-            out.append((None, ("zero1", i)))
+        for i in range(n_params):   # vhats: parameter-shaped with amsgrad, else Keras' shape-(1,) zeros
+            out.append((None, ("slot", 2, i) if getattr(opt, "amsgrad", False) else ("zero1", i)))
+    elif cls == "Adamax":
+        out.append(("Adamax/iterations:0", ("iter",)))
+        for k in (0, 1):
+            for i in range(n_params):
+                out.append((None, ("slot", k, i)))
     elif cls == "Nadam":
         out.append(("Nadam/iterations:0", ("iter",)))
         for k in (0, 1):
@@ -70,7 +76,7 @@ def _opt_layout(opt, n_params):
         for k in (0, 1):
             for i in range(n_params):
                 out.append((None, ("slot", k, i)))
-    elif cls == "RMSprop":
+    elif cls in ("RMSprop", "Adagrad"):
         for i in range(n_params):
             out.append((None, ("slot", 0, i)))
     else:   # SGD
@@ -276,6 +282,6 @@ def _restore_optimizer(model, opt, vals, iterations_hint=None) -> None:
             slots[src[1]][s.offset:s.offset + s.numel] = np.asarray(v, np.float32).reshape(-1)
     if iterations_hint is not None:
         iterations = iterations_hint
-    elif type(opt).__name__ in ("Adadelta", "RMSprop"):
+    elif type(opt).__name__ in ("Adadelta", "RMSprop", "Adagrad"):
         iterations = 0      # Keras does not store the counter for these
     model._executor.set_optimizer_state(iterations, slots)

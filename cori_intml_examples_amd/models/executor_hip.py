@@ -30,7 +30,12 @@ from .hip_geometry import GeometryMixin, cdiv, r8  # noqa: F401  (cdiv: re-expor
 from .plan import Plan
 
 BF16 = torch.bfloat16
-OPT_KIND = {"sgd": 0, "rmsprop": 1, "adadelta": 2, "adam": 3, "nadam": 4}
+OPT_KIND = {"sgd": 0, "rmsprop": 1, "adadelta": 2, "adam": 3, "nadam": 4, "adagrad": 5, "adamax": 6, "amsgrad": 7}
+# kinds with instances of optim_kernel / reduce_optim_kernel only: the kernels that choose the
+# optimizer at run time (the dual launch's early reduction, the dense wgrad's fused update, the
+# xGMI exchange and all-reduce kernels) stay five-way, so a step of these kinds carries no early
+# reduction and no fused dense update, and its data plane updates after the all-reduce
+STANDALONE_KINDS = frozenset(("adagrad", "adamax", "amsgrad"))
 PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_DENSE_FWD, PACK_DENSE_BWD = 0, 1, 2, 3
 RED_CONVW, RED_BIAS, RED_FLATW = 0, 1, 2
 
@@ -333,6 +338,8 @@ class HipExecutor(Executor):
             a.s0 = self.slots[0].data_ptr()
         if len(self.slots) > 1:
             a.s1 = self.slots[1].data_ptr()
+        if len(self.slots) > 2:
+            a.s2 = self.slots[2].data_ptr()
         a.n = self.store.numel
         a.st = self.state.data_ptr()
         o = self.opt
@@ -848,7 +855,8 @@ class BatchPlan(GeometryMixin):
         # profiles/r4c_ab_legacy.txt); "1" = every one-split layer; "0" = off
         dense_opt = str(tune("dense_opt", "auto")).lower()
         self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim", True)
-                             and dense_opt not in ("0", "false", "off", "no"))
+                             and dense_opt not in ("0", "false", "off", "no")
+                             and ex.opt.kind not in STANDALONE_KINDS)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
 
         for g, ds in reversed(list(zip(ex.denses, ex.plan.denses))):
@@ -1216,7 +1224,9 @@ class BatchPlan(GeometryMixin):
         assigned.  grad_only (data-parallel step): reduction only -- no update, no pack
         writes, so later pack readers do not matter."""
         self.early_red = {}
-        if not tune("early_reduce", True):
+        # (the extras choose the optimizer at run time among five kinds: the others' head and
+        # dense groups stay in the end-of-step / per-bucket reduce_optim_kernel<KIND> launch)
+        if not tune("early_reduce", True) or self.ex.opt.kind in STANDALONE_KINDS:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous

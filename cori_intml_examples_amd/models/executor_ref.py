@@ -169,6 +169,14 @@ class RefExecutor(Executor):
         if k == "adam":
             R.adam_update(p, g, self.slots[0][:n], self.slots[1][:n], t, lr, base.beta_1, base.beta_2,
                           base.epsilon)
+        elif k == "amsgrad":
+            R.amsgrad_update(p, g, self.slots[0][:n], self.slots[1][:n], self.slots[2][:n], t, lr, base.beta_1,
+                             base.beta_2, base.epsilon)
+        elif k == "adamax":
+            R.adamax_update(p, g, self.slots[0][:n], self.slots[1][:n], t, lr, base.beta_1, base.beta_2,
+                            base.epsilon)
+        elif k == "adagrad":
+            R.adagrad_update(p, g, self.slots[0][:n], lr, base.epsilon)
         elif k == "adadelta":
             R.adadelta_update(p, g, self.slots[0][:n], self.slots[1][:n], lr, base.rho, base.epsilon)
         elif k == "nadam":

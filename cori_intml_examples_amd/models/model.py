@@ -160,6 +160,9 @@ class Model:
 
     def _make_executor(self):
         base = getattr(self.optimizer, "_base_optimizer", self.optimizer)
+        if getattr(self.optimizer, "distributed", False):
+            from ..parallel import dist
+            dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda")
         if self._device.type == "cuda":
             from .executor_hip import HipExecutor
             self._executor = HipExecutor(self._plan, self.store, base, self._seed)

@@ -160,6 +160,26 @@ def adam_update(p, g, m, v, t: int, lr: float, beta_1=0.9, beta_2=0.999, eps=EPS
     p.sub_(lr_t * m / (v.sqrt() + eps))
 
 
+def amsgrad_update(p, g, m, v, vhat, t: int, lr: float, beta_1=0.9, beta_2=0.999, eps=EPS):
+    lr_t = lr * math.sqrt(1.0 - beta_2 ** t) / (1.0 - beta_1 ** t)
+    m.mul_(beta_1).add_(g, alpha=1.0 - beta_1)
+    v.mul_(beta_2).addcmul_(g, g, value=1.0 - beta_2)
+    torch.maximum(vhat, v, out=vhat)
+    p.sub_(lr_t * m / (vhat.sqrt() + eps))
+
+
+def adamax_update(p, g, m, u, t: int, lr: float, beta_1=0.9, beta_2=0.999, eps=EPS):
+    lr_t = lr / (1.0 - beta_1 ** t)
+    m.mul_(beta_1).add_(g, alpha=1.0 - beta_1)
+    torch.maximum(u.mul_(beta_2), g.abs(), out=u)
+    p.sub_(lr_t * m / (u + eps))
+
+
+def adagrad_update(p, g, a, lr: float, eps=EPS):
+    a.addcmul_(g, g)
+    p.sub_(lr * g / (a.sqrt() + eps))
+
+
 def adadelta_update(p, g, a, d, lr: float, rho=0.95, eps=EPS):
     a.mul_(rho).addcmul_(g, g, value=1.0 - rho)
     upd = g * torch.sqrt(d + eps) / torch.sqrt(a + eps)

@@ -125,6 +125,19 @@ class RMSprop(Optimizer):
         return {"rho": self.rho, "epsilon": self.epsilon}
 
 
+class Adagrad(Optimizer):
+    kind = "adagrad"
+    n_slots = 1
+    default_lr = 0.01
+
+    def __init__(self, lr=None, epsilon=None, decay=0.0, **kw):
+        super().__init__(lr=lr, decay=decay, **kw)
+        self.epsilon = EPS if epsilon is None else float(epsilon)
+
+    def hparams(self):
+        return {"epsilon": self.epsilon}
+
+
 class Adadelta(Optimizer):
     kind = "adadelta"
     n_slots = 2
@@ -146,15 +159,29 @@ class Adam(Optimizer):
 
     def __init__(self, lr=None, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, amsgrad=False, **kw):
         super().__init__(lr=lr, decay=decay, **kw)
-        if amsgrad:
-            raise NotImplementedError("amsgrad")
         self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
         self.epsilon = EPS if epsilon is None else float(epsilon)
-        self.amsgrad = False
+        self.amsgrad = bool(amsgrad)
+        if self.amsgrad:             # third slot: the running maximum of v
+            self.kind, self.n_slots = "amsgrad", 3
 
     def hparams(self):
         return {"beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon,
-                "amsgrad": False}
+                "amsgrad": self.amsgrad}
+
+
+class Adamax(Optimizer):
+    kind = "adamax"
+    n_slots = 2
+    default_lr = 0.002
+
+    def __init__(self, lr=None, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, **kw):
+        super().__init__(lr=lr, decay=decay, **kw)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = EPS if epsilon is None else float(epsilon)
+
+    def hparams(self):
+        return {"beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
 
 
 class Nadam(Optimizer):
@@ -181,7 +208,8 @@ class Nadam(Optimizer):
 
 
 # lowercase aliases as accepted by keras.optimizers.get
-_BY_NAME = {"sgd": SGD, "rmsprop": RMSprop, "adadelta": Adadelta, "adam": Adam, "nadam": Nadam}
+_BY_NAME = {"sgd": SGD, "rmsprop": RMSprop, "adagrad": Adagrad, "adadelta": Adadelta, "adam": Adam,
+            "adamax": Adamax, "nadam": Nadam}
 
 
 def get(identifier) -> Optimizer:

@@ -513,6 +513,31 @@ def auto_plane(grad_bytes: Optional[int] = None) -> str:
     return "rccl"
 
 
+# Optimizer kinds without instances of the xGMI exchange / all-reduce kernels (they update
+# through the optimizer launch behind an RCCL all-reduce): never on the "xgmi" / "hybrid" planes.
+RCCL_ONLY_KINDS = frozenset(("adagrad", "adamax", "amsgrad"))
+
+
+def plane_for_optimizer(plane: str, optimizer, forced: bool) -> str:
+    """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
+    for RCCL_ONLY_KINDS when it was merely chosen (auto / a recorded verdict), and is a
+    ValueError when it was forced (INTML_XGMI, or a job without an RCCL communicator)."""
+    base = getattr(optimizer, "_base_optimizer", optimizer)
+    if plane not in ("xgmi", "hybrid") or getattr(base, "kind", None) not in RCCL_ONLY_KINDS:
+        return plane
+    if forced:
+        name = type(base).__name__ + ("(amsgrad=True)" if getattr(base, "amsgrad", False) else "")
+        raise ValueError("optimizer %s has no kernels for the %r data plane (its update runs behind an RCCL "
+                         "all-reduce): unset INTML_XGMI / INTML_COMM or pick one of SGD, RMSprop, Adadelta, "
+                         "Adam, Nadam" % (name, plane))
+    return "rccl"
+
+
+def forced_plane() -> Optional[str]:
+    """The plane INTML_XGMI pins ("xgmi" / "hybrid" / "rccl"), None for auto."""
+    return None if os.environ.get("INTML_XGMI", "auto").lower() in ("auto", "") else data_plane()
+
+
 class NativeGradReducer:
     """Bucketed gradient all-reduce on the native RCCL engine, CAPTURABLE: the executor
     inserts ``launch(k, ..)`` into the step's launch sequence on a comm stream forked after
@@ -523,8 +548,9 @@ class NativeGradReducer:
     capturable = True
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
-                 rank: Optional[int] = None, size: Optional[int] = None, device=None):
+                 rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None):
         self.store, self.comm = store, comm
+        self.optimizer = optimizer      # (plane_for_optimizer: kinds that stay off the xGMI planes)
         self.compression = compression
         self.bucket_bytes = bucket_bytes
         # comm None: the RCCL-free data plane (state.xgmi_only) -- the whole gradient is ONE
@@ -549,6 +575,8 @@ class NativeGradReducer:
     def configure(self, groups: Sequence[Tuple[int, int]]) -> List[List[int]]:
         self.plane = (data_plane(4 * sum(hi - lo for lo, hi in groups)) if self.comm is not None
                       else "xgmi")
+        self.plane = plane_for_optimizer(self.plane, getattr(self, "optimizer", None),
+                                         forced=self.comm is None or forced_plane() is not None)
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
@@ -705,6 +733,19 @@ class NativeGradReducer:
             grad[: self.store.numel].div_(self.size)
 
 
+def check_optimizer_plane(optimizer, on_gpu: bool) -> None:
+    """ValueError when the job pins a data plane ``optimizer`` has no kernels for (INTML_XGMI =
+    xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds the executor,
+    so nothing has been launched when it raises."""
+    if not is_initialized():
+        init()
+    st = _st()
+    if on_gpu and st.comm is not None:
+        plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True)
+    elif on_gpu and st.xgmi_only and st.size > 1:
+        plane_for_optimizer("xgmi", optimizer, forced=True)
+
+
 def make_reducer(executor, optimizer):
     if not is_initialized():
         init()
@@ -712,9 +753,10 @@ def make_reducer(executor, optimizer):
     bb = getattr(optimizer, "bucket_bytes", None) or st.bucket_bytes
     comp = getattr(optimizer, "compression", None)
     on_gpu = getattr(executor.store, "device", torch.device("cpu")).type == "cuda"
+    check_optimizer_plane(optimizer, on_gpu)
     if on_gpu and st.comm is not None:
-        return NativeGradReducer(executor.store, st.comm, comp, bb)
+        return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
-                                 device=executor.store.device)
+                                 device=executor.store.device, optimizer=optimizer)
     return GradReducer(executor.store, comp, bb)
