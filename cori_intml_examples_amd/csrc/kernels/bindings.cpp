@@ -417,8 +417,7 @@ PYBIND11_MODULE(_kernels, m) {
         DualExtra x;
         if (rt && ro && rt->nblocks > 0) {
           // (the extras' run-time switch, reduce_optim_block_rt; a grad_only table updates nothing)
-          if (!ro->grad_only && !opt_kind_five_way(ro->kind))
-            throw std::invalid_argument("dual_halo: no early update for optimizer kind " + std::to_string(ro->kind));
+          if (!ro->grad_only) opt_require_five_way("dual_halo: no early update", ro->kind);
           x.rt = *rt, x.ro = *ro, x.grad = reinterpret_cast<float*>(rgrad);
           x.n_r = rt->nblocks, x.rfirst = rfirst;
           if (xp && xp->on) {
@@ -438,6 +437,9 @@ PYBIND11_MODULE(_kernels, m) {
       py::arg("rt") = nullptr, py::arg("ro") = nullptr, py::arg("rgrad") = 0, py::arg("rfirst") = 0,
       py::arg("xp") = nullptr,
       "dual wgrad + dgrad launch; with (rt, ro, rgrad) it also runs that table's reduction + optimizer");
+  py::dict kinds;   // common.h's optimizer-kind table: name -> (id, slots, run-time-switch instance)
+  for (const OptKindRow& r : OPT_KINDS) kinds[r.name] = py::make_tuple(r.id, r.slots, r.rt != 0);
+  m.attr("OPT_KINDS") = kinds;
   m.attr("MAX_STACK") = MAX_STACK;
   m.attr("MAX_STACK_SPLIT") = MAX_STACK_SPLIT;
   m.attr("STACK_THREADS") = conv_stack_threads();

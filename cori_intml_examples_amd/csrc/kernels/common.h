@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdexcept>
+#include <string>
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -192,14 +194,69 @@ struct StepState {
   unsigned long long data_w;
 };
 
-enum OptKind {
-  OPT_SGD = 0, OPT_RMSPROP = 1, OPT_ADADELTA = 2, OPT_ADAM = 3, OPT_NADAM = 4,
-  // instances of optim_kernel / reduce_optim_kernel only (misc.hip): the run-time switches of
-  // the dual launch's extras, the dense wgrad and the xGMI kernels stay five-way
-  OPT_ADAGRAD = 5, OPT_ADAMAX = 6, OPT_AMSGRAD = 7
-};
-// host launchers of a kernel with such a five-way switch refuse every other kind
-inline bool opt_kind_five_way(int kind) { return kind >= OPT_SGD && kind <= OPT_NADAM; }
+// The optimizer kinds, one row each: X(enum name, value, lower-case name, state buffers its
+// instances touch unconditionally (s0 / s1 are optional to the others: null reads as zeros),
+// 1 if the kernels that choose the optimizer at RUN time have an instance).  Those kernels --
+// the dual launch's extras, the dense wgrad's fused update, the xGMI table / exchange /
+// all-reduce kernels -- stay five-way (docs/ARCHITECTURE.md); the other kinds are instances
+// of optim_kernel / reduce_optim_kernel only (misc.hip).
+#define OPT_KIND_TABLE(X)                                                                            \
+  X(OPT_SGD, 0, "sgd", 0, 1) X(OPT_RMSPROP, 1, "rmsprop", 0, 1) X(OPT_ADADELTA, 2, "adadelta", 0, 1) \
+  X(OPT_ADAM, 3, "adam", 0, 1) X(OPT_NADAM, 4, "nadam", 0, 1) X(OPT_ADAGRAD, 5, "adagrad", 1, 0)     \
+  X(OPT_ADAMAX, 6, "adamax", 2, 0) X(OPT_AMSGRAD, 7, "amsgrad", 3, 0)
+struct OptKindRow { int id; const char* name; int slots, rt; };
+#define X(id, value, name, slots, rt) id = value,
+enum OptKind { OPT_KIND_TABLE(X) };
+#undef X
+#define X(id, value, name, slots, rt) {id, name, slots, rt},
+constexpr OptKindRow OPT_KINDS[] = {OPT_KIND_TABLE(X)};
+#undef X
+constexpr const OptKindRow* opt_kind_row(int kind) {   // (nullptr: no such kind)
+  for (const OptKindRow& r : OPT_KINDS)
+    if (r.id == kind) return &r;
+  return nullptr;
+}
+constexpr bool opt_kind_five_way(int kind) { return opt_kind_row(kind) && opt_kind_row(kind)->rt; }
+// host launchers refuse a kind without an instance before anything is launched
+inline void opt_refuse(const std::string& what, int kind) {
+  throw std::invalid_argument(what + " for optimizer kind " + std::to_string(kind));
+}
+inline void opt_require_five_way(const std::string& what, int kind) {
+  if (!opt_kind_five_way(kind)) opt_refuse(what, kind);
+}
+
+// Run-time kind -> compile-time KIND: f(OptTag<KIND>{}), f a generic lambda.
+template <int KIND> struct OptTag { static constexpr int kind = KIND; };
+// The five run-time kinds (a wave-uniform switch on the device, where any other kind runs the
+// SGD instance: host launchers check first).  Written out, not generated from the table: the
+// order of the cases is part of the code the compiler emits for the dual launch.
+template <class F>
+__host__ __device__ __forceinline__ void opt_dispatch5(int kind, F&& f) {
+  switch (kind) {
+    case OPT_ADAM: f(OptTag<OPT_ADAM>{}); break;
+    case OPT_NADAM: f(OptTag<OPT_NADAM>{}); break;
+    case OPT_ADADELTA: f(OptTag<OPT_ADADELTA>{}); break;
+    case OPT_RMSPROP: f(OptTag<OPT_RMSPROP>{}); break;
+    default: f(OptTag<OPT_SGD>{}); break;
+  }
+}
+#define X(id, value, name, slots, rt) static_assert(rt == (id <= OPT_NADAM), "opt_dispatch5 vs the table's flags");
+OPT_KIND_TABLE(X)
+#undef X
+template <class F>
+void opt_dispatch5_host(const char* what, int kind, F&& f) {   // "<what>: no kernel instance for ..."
+  opt_require_five_way(std::string(what) + ": no kernel instance", kind);
+  opt_dispatch5(kind, f);
+}
+template <class F>
+void opt_dispatch_all(const char* what, int kind, F&& f) {   // every kind (host only)
+  switch (kind) {
+#define X(id, value, name, slots, rt) case id: return f(OptTag<id>{});
+    OPT_KIND_TABLE(X)
+#undef X
+  }
+  opt_refuse(std::string(what) + ": no kernel instance", kind);
+}
 
 // ---------------------------------------------------------------------------------------
 // Pack / unpack descriptors (fp32 master <-> bf16 fragment packs, grad slabs -> master layout)

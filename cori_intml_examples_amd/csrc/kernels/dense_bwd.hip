@@ -62,13 +62,7 @@ __device__ __forceinline__ int dw_row(int r, int ld) { return r * ld + (r >> 3) 
 
 // the Keras update of one element, optimizer kind chosen at run time (wave-uniform)
 __device__ __forceinline__ void dw_opt(const OptimArgs& o, float& p, float g, float* s0, float* s1) {
-  switch (o.kind) {
-    case OPT_ADAM: opt_update<OPT_ADAM>(o, o.st, p, g, s0, s1); break;
-    case OPT_NADAM: opt_update<OPT_NADAM>(o, o.st, p, g, s0, s1); break;
-    case OPT_ADADELTA: opt_update<OPT_ADADELTA>(o, o.st, p, g, s0, s1); break;
-    case OPT_RMSPROP: opt_update<OPT_RMSPROP>(o, o.st, p, g, s0, s1); break;
-    default: opt_update<OPT_SGD>(o, o.st, p, g, s0, s1); break;
-  }
+  opt_dispatch5(o.kind, [&](auto k) { opt_update<decltype(k)::kind>(o, o.st, p, g, s0, s1); });
 }
 
 // fused update of 4 consecutive elements [e, e+4) whose gradient is g; p / s0 / s1 are
@@ -409,8 +403,7 @@ static void dense_wgrad_check(const WgradArgs& a, int kg, int ntt, int splits) {
   if (a.opt_w >= 0 && (splits != 1 || a.opt.p == nullptr || a.opt.st == nullptr || a.opt_w % 4 ||
                        (a.NT * 16) % 4))
     throw std::runtime_error("dense_wgrad: fused optimizer needs one split and float4-aligned rows");
-  if (a.opt_w >= 0 && !opt_kind_five_way(a.opt.kind))   // (dw_opt's run-time switch)
-    throw std::invalid_argument("dense_wgrad: no fused update for optimizer kind " + std::to_string(a.opt.kind));
+  if (a.opt_w >= 0) opt_require_five_way("dense_wgrad: no fused update", a.opt.kind);   // (dw_opt's run-time switch)
   if (a.pk_fwd >= 0 && (a.opt_w < 0 || a.opt.arena == nullptr || kg != 2 || (a.pk_bwd >= 0 && (ntt & 1)) ||
                         a.Cs_in % 32 || (a.NT * 16) % 32))
     throw std::runtime_error("dense_wgrad: fused pack writes need the fused optimizer, 32-feature tiles and "

@@ -250,21 +250,10 @@ __device__ __forceinline__ void optim_tile_block(const OptimArgs& a, int tb, bf1
   const int r = lane >> 3, c4 = (lane & 7) * 4;
   const int row0 = rb * 8;
   const int e = R.lo + (row0 + r) * N + col0 + c4;
-  float4 p = *reinterpret_cast<const float4*>(a.p + e);
-  const float4 g = *reinterpret_cast<const float4*>(a.g + e);
-  float4 s0 = a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : float4{0.f, 0.f, 0.f, 0.f};
-  float4 s1 = a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : float4{0.f, 0.f, 0.f, 0.f};
-  float4 s2 = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (KIND == OPT_AMSGRAD) s2 = *reinterpret_cast<const float4*>(a.s2 + e);
-  const float gs = a.grad_scale;
-  opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
-  opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
-  opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
-  opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
-  *reinterpret_cast<float4*>(a.p + e) = p;
-  if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
-  if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
-  if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
+  float4 p, g, s0, s1, s2;
+  opt_load4<KIND>(a, e, p, s0, s1, s2, &g);
+  opt_update4<KIND>(a, a.st, p, g, s0, s1, s2);
+  opt_store4<KIND>(a, e, p, s0, s1, s2);
   bf16 (*sl)[40] = tile[wave];
   sl[r][c4] = f2bf(p.x);
   sl[r][c4 + 1] = f2bf(p.y);
@@ -309,28 +298,18 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
   // (a tiled route starts and ends on multiples of 4: its float4 groups are all-or-nothing)
   if (a.ntile && in_tiled_route(a, e)) return;
   const StepState* st = a.st;
-  float4 p = *reinterpret_cast<const float4*>(a.p + e);
-  const float4 g = *reinterpret_cast<const float4*>(a.g + e);
-  float4 s0 = a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : float4{0.f, 0.f, 0.f, 0.f};
-  float4 s1 = a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : float4{0.f, 0.f, 0.f, 0.f};
-  float4 s2 = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (KIND == OPT_AMSGRAD) s2 = *reinterpret_cast<const float4*>(a.s2 + e);
-  const float gs = a.grad_scale;
+  float4 p, g, s0, s1, s2;
+  opt_load4<KIND>(a, e, p, s0, s1, s2, &g);
   if (e >= a.lo && e + 4 <= end) {
-    opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
-    opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
-    opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
-    opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
-  } else {
+    opt_update4<KIND>(a, st, p, g, s0, s1, s2);
+  } else {   // a boundary group: the elements outside the range are written back unchanged
+    const float gs = a.grad_scale;
     if (e >= a.lo && e < end) opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
     if (e + 1 >= a.lo && e + 1 < end) opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
     if (e + 2 >= a.lo && e + 2 < end) opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
     if (e + 3 >= a.lo && e + 3 < end) opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
   }
-  *reinterpret_cast<float4*>(a.p + e) = p;
-  if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
-  if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
-  if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
+  opt_store4<KIND>(a, e, p, s0, s1, s2);
   if (a.nroutes) {
     if (e >= a.lo && e + 4 <= end) {
       pack_write4(a, e, p);
@@ -346,14 +325,14 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
 
 // the state buffers a kind's instances read and write unconditionally
 static void check_state_slots(const OptimArgs& a) {
-  const int need = a.kind == OPT_AMSGRAD ? 3 : (a.kind == OPT_ADAMAX ? 2 : (a.kind == OPT_ADAGRAD ? 1 : 0));
+  const OptKindRow* row = opt_kind_row(a.kind);
+  const int need = row ? row->slots : 0;
   if ((need > 0 && !a.s0) || (need > 1 && !a.s1) || (need > 2 && !a.s2))
     throw std::invalid_argument("optimizer kind " + std::to_string(a.kind) + ": missing state buffer");
 }
 // the table kernels that choose the optimizer at run time (xgmi_early_block) know five kinds
 static void check_five_way(const OptimArgs& a, const char* what) {
-  if (!a.grad_only && !opt_kind_five_way(a.kind))
-    throw std::invalid_argument(std::string(what) + ": no kernel instance for optimizer kind " + std::to_string(a.kind));
+  if (!a.grad_only) opt_require_five_way(std::string(what) + ": no kernel instance", a.kind);
 }
 
 void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s) {
@@ -363,17 +342,9 @@ void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s) {
     const int flat = ((span + 3) / 4 + 255) / 256;
     if (a.ntile && a.flat_blocks != flat) throw std::invalid_argument("optim: flat_blocks mismatch");
     const dim3 grid(flat + (a.ntile ? a.tile_b0[a.ntile] : 0));
-    switch (a.kind) {
-      case OPT_ADAM: hipLaunchKernelGGL(optim_kernel<OPT_ADAM>, grid, dim3(256), 0, s, a); break;
-      case OPT_NADAM: hipLaunchKernelGGL(optim_kernel<OPT_NADAM>, grid, dim3(256), 0, s, a); break;
-      case OPT_ADADELTA: hipLaunchKernelGGL(optim_kernel<OPT_ADADELTA>, grid, dim3(256), 0, s, a); break;
-      case OPT_RMSPROP: hipLaunchKernelGGL(optim_kernel<OPT_RMSPROP>, grid, dim3(256), 0, s, a); break;
-      case OPT_ADAGRAD: hipLaunchKernelGGL(optim_kernel<OPT_ADAGRAD>, grid, dim3(256), 0, s, a); break;
-      case OPT_ADAMAX: hipLaunchKernelGGL(optim_kernel<OPT_ADAMAX>, grid, dim3(256), 0, s, a); break;
-      case OPT_AMSGRAD: hipLaunchKernelGGL(optim_kernel<OPT_AMSGRAD>, grid, dim3(256), 0, s, a); break;
-      case OPT_SGD: hipLaunchKernelGGL(optim_kernel<OPT_SGD>, grid, dim3(256), 0, s, a); break;
-      default: throw std::invalid_argument("optim: no kernel instance for optimizer kind " + std::to_string(a.kind));
-    }
+    opt_dispatch_all("optim", a.kind, [&](auto k) {
+      hipLaunchKernelGGL(optim_kernel<decltype(k)::kind>, grid, dim3(256), 0, s, a);
+    });
   }
   if (!a.defer_pack || a.pack_only)
     launch_pack(a.p, a.arena, tab, s);    // the MFMA kernels read the bf16 packs
@@ -432,18 +403,9 @@ template <bool END>
 static void launch_fused(float* grad, const RedTable& tc, const OptimArgs& a, const XgmiPush& xc, const RedTable& te,
                          const XgmiPush& xe, int nc, int ne, hipStream_t s) {
   const dim3 g(nc + ne), b(256);
-  switch (a.kind) {
-    case OPT_ADAM: hipLaunchKernelGGL((xchg_fused_kernel<OPT_ADAM, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc); break;
-    case OPT_NADAM: hipLaunchKernelGGL((xchg_fused_kernel<OPT_NADAM, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc); break;
-    case OPT_ADADELTA:
-      hipLaunchKernelGGL((xchg_fused_kernel<OPT_ADADELTA, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc);
-      break;
-    case OPT_RMSPROP:
-      hipLaunchKernelGGL((xchg_fused_kernel<OPT_RMSPROP, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc);
-      break;
-    case OPT_SGD: hipLaunchKernelGGL((xchg_fused_kernel<OPT_SGD, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc); break;
-    default: throw std::invalid_argument("xGMI exchange: no kernel instance for optimizer kind " + std::to_string(a.kind));
-  }
+  opt_dispatch5_host("xGMI exchange", a.kind, [&](auto k) {
+    hipLaunchKernelGGL((xchg_fused_kernel<decltype(k)::kind, END>), g, b, 0, s, grad, tc, a, xc, te, xe, nc);
+  });
 }
 
 // mode 3 goes through the fused kernel when it runs one workgroup per block and has the
@@ -480,15 +442,7 @@ void launch_reduce_optim(float* grad, const RedTable& tab, const OptimArgs& a, h
   }
   const dim3 g(tab.nblocks), b(256);
   if (!a.grad_only) check_state_slots(a);
-  switch (a.kind) {
-    case OPT_ADAM: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAM>, g, b, 0, s, grad, tab, a); break;
-    case OPT_NADAM: hipLaunchKernelGGL(reduce_optim_kernel<OPT_NADAM>, g, b, 0, s, grad, tab, a); break;
-    case OPT_ADADELTA: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADADELTA>, g, b, 0, s, grad, tab, a); break;
-    case OPT_RMSPROP: hipLaunchKernelGGL(reduce_optim_kernel<OPT_RMSPROP>, g, b, 0, s, grad, tab, a); break;
-    case OPT_ADAGRAD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAGRAD>, g, b, 0, s, grad, tab, a); break;
-    case OPT_ADAMAX: hipLaunchKernelGGL(reduce_optim_kernel<OPT_ADAMAX>, g, b, 0, s, grad, tab, a); break;
-    case OPT_AMSGRAD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_AMSGRAD>, g, b, 0, s, grad, tab, a); break;
-    case OPT_SGD: hipLaunchKernelGGL(reduce_optim_kernel<OPT_SGD>, g, b, 0, s, grad, tab, a); break;
-    default: throw std::invalid_argument("reduce_optim: no kernel instance for optimizer kind " + std::to_string(a.kind));
-  }
+  opt_dispatch_all("reduce_optim", a.kind, [&](auto k) {
+    hipLaunchKernelGGL(reduce_optim_kernel<decltype(k)::kind>, g, b, 0, s, grad, tab, a);
+  });
 }

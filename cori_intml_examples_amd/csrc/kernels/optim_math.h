@@ -71,6 +71,36 @@ __device__ __forceinline__ void opt_update(const OptimArgs& a, const StepState* 
   }
 }
 
+// The same for four consecutive elements at e (16-byte aligned): load p and the state (s0 / s1
+// optional; s2 is touched by the OPT_AMSGRAD instances only and dead in every other one; with
+// g also the gradient at a.g + e), update with the gradient scaled by grad_scale, store back.
+template <int KIND>
+__device__ __forceinline__ void opt_load4(const OptimArgs& a, long long e, float4& p, float4& s0, float4& s1,
+                                          float4& s2, float4* g = nullptr) {
+  p = *reinterpret_cast<const float4*>(a.p + e);
+  if (g) *g = *reinterpret_cast<const float4*>(a.g + e);
+  s0 = a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : float4{0.f, 0.f, 0.f, 0.f};
+  s1 = a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : float4{0.f, 0.f, 0.f, 0.f};
+  s2 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (KIND == OPT_AMSGRAD) s2 = *reinterpret_cast<const float4*>(a.s2 + e);
+}
+template <int KIND>
+__device__ __forceinline__ void opt_update4(const OptimArgs& a, const StepState* st, float4& p, const float4& g,
+                                            float4& s0, float4& s1, float4& s2) {
+  const float gs = a.grad_scale;
+  opt_update<KIND>(a, st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
+  opt_update<KIND>(a, st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
+  opt_update<KIND>(a, st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
+  opt_update<KIND>(a, st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
+}
+template <int KIND>
+__device__ __forceinline__ void opt_store4(const OptimArgs& a, long long e, const float4& p, const float4& s0,
+                                             const float4& s1, const float4& s2) {
+  *reinterpret_cast<float4*>(a.p + e) = p;
+  if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
+  if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
+  if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
+}
 
 // ---------------------------------------------------------------------------------------
 // bf16 copies of updated master elements into the fragment packs (routes: PackRoute, args.h).

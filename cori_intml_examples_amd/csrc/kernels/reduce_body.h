@@ -157,28 +157,26 @@ __device__ __forceinline__ void xpush4(const XgmiPush& xp, long long e, const fl
 // The optimizer state of the elements a thread will update, loaded BEFORE the reduction whose
 // result it updates them with: its memory round trip overlaps the slab loads instead of
 // following them (~1 us of the reduction launch's latency chain)
-// (s2: the third buffer, OPT_AMSGRAD instances only -- load_state2; dead in every other one)
+// (s2: the third buffer, OPT_AMSGRAD instances only; dead in every other one)
 struct OptState4 {
   float4 p, s0, s1, s2;
 };
 struct OptState1 {
   float p, s0, s1, s2;
 };
+template <int KIND>
 __device__ __forceinline__ OptState4 load_state4(const OptimArgs& a, int e) {
   const float4 z = {0.f, 0.f, 0.f, 0.f};
-  return OptState4{*reinterpret_cast<const float4*>(a.p + e), a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : z,
-                   a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : z, z};
-}
-__device__ __forceinline__ OptState1 load_state1(const OptimArgs& a, int e) {
-  return OptState1{a.p[e], a.s0 ? a.s0[e] : 0.f, a.s1 ? a.s1[e] : 0.f, 0.f};
-}
-template <int KIND>
-__device__ __forceinline__ void load_state2(const OptimArgs& a, int e, OptState4& st) {
+  OptState4 st{*reinterpret_cast<const float4*>(a.p + e), a.s0 ? *reinterpret_cast<const float4*>(a.s0 + e) : z,
+               a.s1 ? *reinterpret_cast<const float4*>(a.s1 + e) : z, z};
   if constexpr (KIND == OPT_AMSGRAD) st.s2 = *reinterpret_cast<const float4*>(a.s2 + e);
+  return st;
 }
 template <int KIND>
-__device__ __forceinline__ void load_state2(const OptimArgs& a, int e, OptState1& st) {
+__device__ __forceinline__ OptState1 load_state1(const OptimArgs& a, int e) {
+  OptState1 st{a.p[e], a.s0 ? a.s0[e] : 0.f, a.s1 ? a.s1[e] : 0.f, 0.f};
   if constexpr (KIND == OPT_AMSGRAD) st.s2 = a.s2[e];
+  return st;
 }
 
 // Keras update of the elements a table block's thread holds (vec4 descriptor: the float4 at
@@ -199,15 +197,8 @@ __device__ __forceinline__ void update_vec4(const RedDesc& dsc, const OptimArgs&
   bf16* tl = reinterpret_cast<bf16*>(red);
   if (mine) {
     float4 p = st.p, s0 = st.s0, s1 = st.s1, s2 = st.s2;
-    const float gs = a.grad_scale;
-    opt_update<KIND>(a, a.st, p.x, g.x * gs, &s0.x, &s1.x, &s2.x);
-    opt_update<KIND>(a, a.st, p.y, g.y * gs, &s0.y, &s1.y, &s2.y);
-    opt_update<KIND>(a, a.st, p.z, g.z * gs, &s0.z, &s1.z, &s2.z);
-    opt_update<KIND>(a, a.st, p.w, g.w * gs, &s0.w, &s1.w, &s2.w);
-    *reinterpret_cast<float4*>(a.p + e) = p;
-    if (a.s0) *reinterpret_cast<float4*>(a.s0 + e) = s0;
-    if (a.s1) *reinterpret_cast<float4*>(a.s1 + e) = s1;
-    if constexpr (KIND == OPT_AMSGRAD) *reinterpret_cast<float4*>(a.s2 + e) = s2;
+    opt_update4<KIND>(a, a.st, p, g, s0, s1, s2);
+    opt_store4<KIND>(a, e, p, s0, s1, s2);
     if (tr) {
       bf16x4 v;
       v[0] = f2bf(p.x); v[1] = f2bf(p.y); v[2] = f2bf(p.z); v[3] = f2bf(p.w);
@@ -264,30 +255,36 @@ __device__ __forceinline__ void reduce_optim_block(float* __restrict__ grad, con
     OptState4 st{};
     if (PRE && upd) {   // (slab_reduce_vec4's map: split-lane 0 of element group t % G holds the sum)
       const int G = 256 / dsc.tpe, le = ((blk - dsc.blk0) * G + t % G) * 4;
-      if (t < G && le < dsc.numel) st = load_state4(a, dsc.dst_off + le), load_state2<KIND>(a, dsc.dst_off + le, st);
+      if (t < G && le < dsc.numel) st = load_state4<KIND>(a, dsc.dst_off + le);
     }
     int e;
     float4 g;
     const bool mine = slab_reduce_vec4(dsc, blk, red, e, g);
     if (mine) *reinterpret_cast<float4*>(grad + e) = g;
     if (mine && xp) xpush4(*xp, e, g);
-    if (!PRE && mine && upd) st = load_state4(a, e), load_state2<KIND>(a, e, st);
+    if (!PRE && mine && upd) st = load_state4<KIND>(a, e);
     if (upd) update_vec4<KIND>(dsc, a, blk, red, mine, e, g, st);   // (grad_only: the reduced gradient is all)
   } else {
     OptState1 st{};
     if (PRE && upd) {   // (slab_reduce_elem's map: thread t < E holds element t of the block)
       const int E = 256 / dsc.tpe, le = (blk - dsc.blk0) * E + t;
-      if (t < E && le < dsc.numel) st = load_state1(a, dsc.dst_off + le), load_state2<KIND>(a, dsc.dst_off + le, st);
+      if (t < E && le < dsc.numel) st = load_state1<KIND>(a, dsc.dst_off + le);
     }
     int e;
     float g;
     const bool mine = slab_reduce_elem(tab, blk, red, e, g);
     if (mine) grad[e] = g;
     if (mine && xp) xpush1(*xp, e, g);
-    if (!PRE && mine && upd) st = load_state1(a, e), load_state2<KIND>(a, e, st);
+    if (!PRE && mine && upd) st = load_state1<KIND>(a, e);
     if (mine && upd) update_elem<KIND>(a, e, g, st);
   }
   if (a.defer_pack && !a.nroutes && upd && blk == 0 && threadIdx.x == 0) a.st->packs_stale = 1;
+}
+
+// the same with the optimizer kind chosen at run time (a workgroup-uniform switch)
+__device__ __forceinline__ void reduce_optim_block_rt(float* __restrict__ grad, const RedTable& tab,
+                                                      const OptimArgs& a, int blk, float* red) {
+  opt_dispatch5(a.kind, [&](auto k) { reduce_optim_block<decltype(k)::kind>(grad, tab, a, blk, red); });
 }
 
 // ---------------------------------------------------------------- xGMI early-bucket exchange
@@ -426,8 +423,8 @@ __device__ __forceinline__ void xchg_update_block(float* __restrict__ grad, cons
   if (parts & 2) {
     if (pre4) st4 = *pre4;
     else if (pre1) st1 = *pre1;
-    else if (n == 4) st4 = load_state4(a, e);
-    else if (n == 1) st1 = load_state1(a, e);
+    else if (n == 4) st4 = load_state4<KIND>(a, e);
+    else if (n == 1) st1 = load_state1<KIND>(a, e);
   }
   const long long ie = (long long)e - x.lo;     // bucket index
   const int own = n ? (int)(ie / C) : -1;
@@ -493,7 +490,7 @@ __device__ __forceinline__ void xchg_fused_block(float* __restrict__ grad, const
   if (dsc.vec4) {
     OptState4 st{};
     const int G = 256 / dsc.tpe, le = ((blk - dsc.blk0) * G + t % G) * 4;
-    if (t < G && le < dsc.numel) st = load_state4(a, dsc.dst_off + le);
+    if (t < G && le < dsc.numel) st = load_state4<KIND>(a, dsc.dst_off + le);
     int e;
     const bool mine = slab_reduce_vec4(dsc, blk, red, e, g4);
     if (mine) *reinterpret_cast<float4*>(grad + e) = g4;
@@ -510,7 +507,7 @@ __device__ __forceinline__ void xchg_fused_block(float* __restrict__ grad, const
   } else {
     OptState1 st{};
     const int E = 256 / dsc.tpe, le = (blk - dsc.blk0) * E + t;
-    if (t < E && le < dsc.numel) st = load_state1(a, dsc.dst_off + le);
+    if (t < E && le < dsc.numel) st = load_state1<KIND>(a, dsc.dst_off + le);
     int e;
     float g;
     const bool mine = slab_reduce_elem(tab, blk, red, e, g);
@@ -573,13 +570,7 @@ __device__ __forceinline__ void xgmi_early_block(float* __restrict__ grad, const
   if constexpr (M3) {
   if (x.mode == 3 && x.size == 1 && !x.p1) {   // no peers: the single-GPU reduction + update
     for (int b = r; b < x.nblk; b += step) {
-      switch (a.kind) {
-        case OPT_ADAM: reduce_optim_block<OPT_ADAM>(grad, tab, a, b, red); break;
-        case OPT_NADAM: reduce_optim_block<OPT_NADAM>(grad, tab, a, b, red); break;
-        case OPT_ADADELTA: reduce_optim_block<OPT_ADADELTA>(grad, tab, a, b, red); break;
-        case OPT_RMSPROP: reduce_optim_block<OPT_RMSPROP>(grad, tab, a, b, red); break;
-        default: reduce_optim_block<OPT_SGD>(grad, tab, a, b, red); break;
-      }
+      reduce_optim_block_rt(grad, tab, a, b, red);
       __syncthreads();
     }
     return;
@@ -593,25 +584,7 @@ __device__ __forceinline__ void xgmi_early_block(float* __restrict__ grad, const
   }
   }
   for (int b = b0 + r; b < b1; b += step) {
-    switch (a.kind) {
-      case OPT_ADAM: xchg_update_block<OPT_ADAM>(grad, tab, a, b, red, x, parts); break;
-      case OPT_NADAM: xchg_update_block<OPT_NADAM>(grad, tab, a, b, red, x, parts); break;
-      case OPT_ADADELTA: xchg_update_block<OPT_ADADELTA>(grad, tab, a, b, red, x, parts); break;
-      case OPT_RMSPROP: xchg_update_block<OPT_RMSPROP>(grad, tab, a, b, red, x, parts); break;
-      default: xchg_update_block<OPT_SGD>(grad, tab, a, b, red, x, parts); break;
-    }
+    opt_dispatch5(a.kind, [&](auto k) { xchg_update_block<decltype(k)::kind>(grad, tab, a, b, red, x, parts); });
     __syncthreads();   // (the next block reuses red)
-  }
-}
-
-// the same with the optimizer kind chosen at run time (a workgroup-uniform switch)
-__device__ __forceinline__ void reduce_optim_block_rt(float* __restrict__ grad, const RedTable& tab,
-                                                      const OptimArgs& a, int blk, float* red) {
-  switch (a.kind) {
-    case OPT_ADAM: reduce_optim_block<OPT_ADAM>(grad, tab, a, blk, red); break;
-    case OPT_NADAM: reduce_optim_block<OPT_NADAM>(grad, tab, a, blk, red); break;
-    case OPT_ADADELTA: reduce_optim_block<OPT_ADADELTA>(grad, tab, a, blk, red); break;
-    case OPT_RMSPROP: reduce_optim_block<OPT_RMSPROP>(grad, tab, a, blk, red); break;
-    default: reduce_optim_block<OPT_SGD>(grad, tab, a, blk, red); break;
   }
 }

@@ -145,17 +145,10 @@ __device__ __forceinline__ void finish4(const XgmiArgs& a, float* __restrict__ g
   if (idx + 4 <= n && !part) {       // float4 path (idx, C, k multiples of 4: 16-byte aligned)
     *reinterpret_cast<float4*>(grad + idx) = g4;
     if (a.mode == 1) {
-      float4 p4 = *reinterpret_cast<const float4*>(o.p + idx);
-      float4 m4 = o.s0 ? *reinterpret_cast<const float4*>(o.s0 + idx) : float4{0.f, 0.f, 0.f, 0.f};
-      float4 v4 = o.s1 ? *reinterpret_cast<const float4*>(o.s1 + idx) : float4{0.f, 0.f, 0.f, 0.f};
-      const float gs = o.grad_scale;
-      opt_update<KIND>(o, o.st, p4.x, g4.x * gs, &m4.x, &v4.x);
-      opt_update<KIND>(o, o.st, p4.y, g4.y * gs, &m4.y, &v4.y);
-      opt_update<KIND>(o, o.st, p4.z, g4.z * gs, &m4.z, &v4.z);
-      opt_update<KIND>(o, o.st, p4.w, g4.w * gs, &m4.w, &v4.w);
-      *reinterpret_cast<float4*>(o.p + idx) = p4;
-      if (o.s0) *reinterpret_cast<float4*>(o.s0 + idx) = m4;
-      if (o.s1) *reinterpret_cast<float4*>(o.s1 + idx) = v4;
+      float4 p4, m4, v4, s2;   // (s2: no instance of this kernel touches it)
+      opt_load4<KIND>(o, idx, p4, m4, v4, s2);
+      opt_update4<KIND>(o, o.st, p4, g4, m4, v4, s2);
+      opt_store4<KIND>(o, idx, p4, m4, v4, s2);
       if (o.nroutes) pack_write4(o, o.lo + (int)idx, p4);   // o.lo: the bucket's flat start
     }
     return;
@@ -269,15 +262,10 @@ int xgmi_grid(const XgmiArgs& a) { return (a.chunk + a.sub - 1) / a.sub; }
 
 void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s) {
   const dim3 grid(xgmi_grid(a)), block(256);
-  switch (a.mode == 1 ? a.opt.kind : -1) {
-    case OPT_ADAM: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_ADAM>, grid, block, 0, s, a); break;
-    case OPT_NADAM: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_NADAM>, grid, block, 0, s, a); break;
-    case OPT_ADADELTA: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_ADADELTA>, grid, block, 0, s, a); break;
-    case OPT_RMSPROP: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_RMSPROP>, grid, block, 0, s, a); break;
-    case OPT_SGD:
-    case -1: hipLaunchKernelGGL(xgmi_allreduce_kernel<OPT_SGD>, grid, block, 0, s, a); break;   // (-1: sum only)
-    default: throw std::invalid_argument("xgmi all-reduce: no kernel instance for optimizer kind " + std::to_string(a.opt.kind));
-  }
+  // (modes other than 1 only sum: the SGD instance, whose update never runs)
+  opt_dispatch5_host("xgmi all-reduce", a.mode == 1 ? a.opt.kind : OPT_SGD, [&](auto k) {
+    hipLaunchKernelGGL(xgmi_allreduce_kernel<decltype(k)::kind>, grid, block, 0, s, a);
+  });
 }
 
 // ---------------------------------------------------------------- host: memory + IPC

@@ -24,18 +24,19 @@ import torch
 
 from ..ops.hip import kernels
 from ..ops.rng import keep_threshold
+from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, fill_kernel_args
 from ..utils.env import env_flag, tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin, cdiv, r8  # noqa: F401  (cdiv: re-exported for tests)
 from .plan import Plan
 
 BF16 = torch.bfloat16
-OPT_KIND = {"sgd": 0, "rmsprop": 1, "adadelta": 2, "adam": 3, "nadam": 4, "adagrad": 5, "adamax": 6, "amsgrad": 7}
-# kinds with instances of optim_kernel / reduce_optim_kernel only: the kernels that choose the
-# optimizer at run time (the dual launch's early reduction, the dense wgrad's fused update, the
-# xGMI exchange and all-reduce kernels) stay five-way, so a step of these kinds carries no early
+# views of the optimizer-kind table (optim/optimizers.py KINDS).  STANDALONE_KINDS: kinds with
+# instances of optim_kernel / reduce_optim_kernel only -- the kernels that choose the optimizer
+# at run time (the dual launch's early reduction, the dense wgrad's fused update, the xGMI
+# exchange and all-reduce kernels) stay five-way, so a step of these kinds carries no early
 # reduction and no fused dense update, and its data plane updates after the all-reduce
-STANDALONE_KINDS = frozenset(("adagrad", "adamax", "amsgrad"))
+OPT_KIND = KIND_IDS
 PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_DENSE_FWD, PACK_DENSE_BWD = 0, 1, 2, 3
 RED_CONVW, RED_BIAS, RED_FLATW = 0, 1, 2
 
@@ -342,14 +343,7 @@ class HipExecutor(Executor):
             a.s2 = self.slots[2].data_ptr()
         a.n = self.store.numel
         a.st = self.state.data_ptr()
-        o = self.opt
-        a.kind = OPT_KIND[o.kind]
-        a.beta1 = getattr(o, "beta_1", 0.9)
-        a.beta2 = getattr(o, "beta_2", 0.999)
-        a.eps = getattr(o, "epsilon", 1e-7)
-        a.rho = getattr(o, "rho", 0.95)
-        a.momentum = getattr(o, "momentum", 0.0)
-        a.nesterov = int(getattr(o, "nesterov", False))
+        fill_kernel_args(self.opt, a)
         a.grad_scale = self.grad_scale
         a.pack_only = int(pack_only)
         a.defer_pack = int(defer_pack)
@@ -679,12 +673,7 @@ class BatchPlan(GeometryMixin):
         sb.st = st_ptr
         sb.training = int(training)
         sb.bs = bs
-        o = ex.opt
-        sb.opt_kind = OPT_KIND[o.kind]
-        sb.beta1 = getattr(o, "beta_1", 0.9)
-        sb.beta2 = getattr(o, "beta_2", 0.999)
-        sb.decay = getattr(o, "initial_decay", 0.0)
-        sb.schedule_decay = getattr(o, "schedule_decay", 0.004)
+        fill_kernel_args(ex.opt, sb, "opt_kind")
         ga = K.GatherArgs()
         ga.st = st_ptr
         ga.bs = bs

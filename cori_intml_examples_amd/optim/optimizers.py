@@ -48,6 +48,34 @@ class KVariable:
     __hash__ = object.__hash__
 
 
+# The optimizer kinds of the fused update kernels, kind -> (id, state buffers the kernels touch
+# unconditionally, True if the kernels that choose the optimizer at run time have an instance):
+# the Python copy of csrc/kernels/common.h's OPT_KIND_TABLE, which the extension exports as
+# OPT_KINDS (tests/test_optimizer_kinds.py compares the two).  A kind without the run-time
+# instance runs no early reduction, no fused dense update and no xGMI data plane.
+KINDS = {"sgd": (0, 0, True), "rmsprop": (1, 0, True), "adadelta": (2, 0, True), "adam": (3, 0, True),
+         "nadam": (4, 0, True), "adagrad": (5, 1, False), "adamax": (6, 2, False), "amsgrad": (7, 3, False)}
+KIND_IDS = {k: v[0] for k, v in KINDS.items()}
+STANDALONE_KINDS = frozenset(k for k, v in KINDS.items() if not v[2])
+
+# hyper-parameters of the kernel argument structs: (optimizer attribute, struct field, default
+# when the optimizer has none, conversion)
+_HYPER = (("beta_1", "beta1", 0.9, float), ("beta_2", "beta2", 0.999, float), ("epsilon", "eps", 1e-7, float),
+          ("rho", "rho", 0.95, float), ("momentum", "momentum", 0.0, float), ("nesterov", "nesterov", False, int),
+          ("initial_decay", "decay", 0.0, float), ("schedule_decay", "schedule_decay", 0.004, float))
+
+
+def fill_kernel_args(opt, args, kind_field: str = "kind"):
+    """Write ``opt``'s kind id and hyper-parameters into the fields ``args`` has (OptimArgs:
+    kind, beta1, beta2, eps, rho, momentum, nesterov; StepBeginArgs: opt_kind, beta1, beta2,
+    decay, schedule_decay)."""
+    setattr(args, kind_field, KIND_IDS[opt.kind])
+    for attr, field, default, conv in _HYPER:
+        if hasattr(args, field):
+            setattr(args, field, conv(getattr(opt, attr, default)))
+    return args
+
+
 def get_value(x) -> float:
     return x.get() if isinstance(x, KVariable) else float(x)
 

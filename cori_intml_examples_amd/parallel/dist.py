@@ -26,6 +26,7 @@ import torch
 import torch.distributed as tdist
 
 from . import state as S
+from ..optim.optimizers import STANDALONE_KINDS
 from ..utils.env import tune
 
 
@@ -515,7 +516,7 @@ def auto_plane(grad_bytes: Optional[int] = None) -> str:
 
 # Optimizer kinds without instances of the xGMI exchange / all-reduce kernels (they update
 # through the optimizer launch behind an RCCL all-reduce): never on the "xgmi" / "hybrid" planes.
-RCCL_ONLY_KINDS = frozenset(("adagrad", "adamax", "amsgrad"))
+RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-switch instance)
 
 
 def plane_for_optimizer(plane: str, optimizer, forced: bool) -> str:
