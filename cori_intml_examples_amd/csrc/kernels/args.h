@@ -209,6 +209,11 @@ struct WgradArgs {
   // (with opt_w: opt_nograd = 1 skips storing the in-place gradient the update consumed --
   // single-GPU step, nothing reads it; the data-parallel step never fuses the update here)
   int opt_nograd = 0;
+  // halo kernels: run a layer-signature instance (geometry fixed at compile time, wgrad_sig.h)
+  // when one matches (wgrad_halo_variant / dual_halo_variant); 0 = always the generic kernels
+  // (A/B and the bit-identity tests).  Host-only; it sits in the 4 bytes of padding before
+  // pk_fwd, so the kernel-argument layout of every WgradArgs kernel is what it was without it.
+  int spec = 1;
   // ... and (pk_fwd >= 0) the updated weights' bf16 copies written into the layer's forward /
   // backward fragment packs (element offsets in opt.arena, their n-tile counts) as whole
   // 16-byte vectors from an LDS tile -- the workgroup's 32 features x NTT*16 outputs are
@@ -224,6 +229,13 @@ struct WgradArgs {
   const int* xidx = nullptr;
   const StepState* xst = nullptr;
 };
+
+// The WgradArgs fields that are geometry of the halo kernels: the ONE list behind the body's
+// geometry traits (wgrad_halo_body.h), the layer signatures and the host's field-by-field
+// signature match (wgrad_sig.h / wgrad_sig.hip)
+#define WG_GEO_INTS(F)                                                                                       \
+  F(H) F(W) F(Cs_in) F(Ho) F(Wo) F(KH) F(KW) F(stride) F(pad_t) F(pad_l) F(Ktiles) F(NT) F(Cs_dy) F(dHp) F(dWp) \
+  F(R) F(xpix) F(xrow) F(dyld) F(kperm) F(wt)
 
 // Dense forward, split-K partial products: part[s][m][n]
 struct StepBeginArgs {

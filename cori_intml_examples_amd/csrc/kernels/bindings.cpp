@@ -22,6 +22,8 @@ size_t wgrad_tile_lds_bytes(int ntc);
 void launch_wgrad_halo(const WgradArgs& a, int MT, int NTT, int splits, hipStream_t s);
 size_t wgrad_halo_lds_bytes(const WgradArgs& a, int MT, int NTT);
 int wgrad_halo_resident(const WgradArgs& a, int MT, int NTT, bool bias);
+int wgrad_halo_variant(const WgradArgs& a, int MT, int NTT);
+int dual_halo_variant(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp, bool extras);
 int head_rows_per_block(bool fused);
 int head_epi_max();
 void launch_wgrad(const WgradArgs& a, int ktw, int ntt, int splits, hipStream_t s);
@@ -141,7 +143,7 @@ PYBIND11_MODULE(_kernels, m) {
       RW(WgradArgs, dbg) PTR(WgradArgs, ts) PTR(WgradArgs, ts2) RW(WgradArgs, opt) RW(WgradArgs, opt_w)
       RW(WgradArgs, opt_b) RW(WgradArgs, xpix) RW(WgradArgs, xrow) RW(WgradArgs, dyld) RW(WgradArgs, kperm)
       PTR(WgradArgs, xidx) PTR(WgradArgs, xst) RW(WgradArgs, pk_fwd) RW(WgradArgs, pk_bwd) RW(WgradArgs, pk_NT)
-      RW(WgradArgs, pk_NTb) RW(WgradArgs, wt) RW(WgradArgs, opt_nograd);
+      RW(WgradArgs, pk_NTb) RW(WgradArgs, wt) RW(WgradArgs, opt_nograd) RW(WgradArgs, spec);
 
   py::class_<DenseFwdArgs>(m, "DenseFwdArgs")
       .def(py::init<>())
@@ -355,6 +357,9 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("conv_halo_lds_bytes", &conv_halo_lds_bytes);
   m.def("wgrad_halo_lds_bytes", &wgrad_halo_lds_bytes);
   m.def("wgrad_halo_resident", &wgrad_halo_resident);
+  m.def("wgrad_halo_variant", &wgrad_halo_variant);
+  m.def("dual_halo_variant", &dual_halo_variant, py::arg("ca"), py::arg("ntc"), py::arg("wa"), py::arg("MT"),
+        py::arg("NTT"), py::arg("xp") = false, py::arg("extras") = false);
   m.def("head_rows_per_block", &head_rows_per_block, py::arg("fused") = false);
   m.def("conv_tile_lds_bytes", &conv_tile_lds_bytes);
   m.def("conv_tile", [](const ConvMMArgs& a, int ntc, uintptr_t s, bool big, int nbuf) {

@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "wgrad_halo_body.h"
+#include "wgrad_sig.h"
 
 // INSTR: ablation (a.dbg) and diagnostics-stamp (a.ts / a.ts2) code compiled in; the
 // production instance (INSTR = false) is launched whenever none of them is asked for -- that
@@ -57,12 +58,24 @@ static void wh_t(const WgradArgs& a, int MT, dim3 grid, size_t lds, hipStream_t 
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a, MT);
 }
 
+// 1 + index of the layer signature (wgrad_sig.hip) whose standalone instance serves these args,
+// or 0: the generic kernel.  Ablation / stamp requests always take the generic kernel.
+int wgrad_halo_variant(const WgradArgs& a, int MT, int NTT) {
+  if (!a.spec || wh_instr(a)) return 0;
+  const int v = wgrad_sig_find(a, MT, NTT);
+  return v && wgrad_sig_at(v).alone ? v : 0;
+}
+
 // MT m-tiles x NTT n-tiles per workgroup; each wave owns ceil((MT+bias)/4) m-tiles
 // (MTW <= 4, MTW*NTT <= 16); grid = (splits, n-groups, m-groups)
 void launch_wgrad_halo(const WgradArgs& a, int MT, int NTT, int splits, hipStream_t s) {
   const bool cs4 = a.Cs_in == 4;
   dim3 grid(splits, (a.NT + NTT - 1) / NTT, (a.Ktiles + MT - 1) / MT);
   const size_t lds = wgrad_halo_lds_bytes(a, MT, NTT);
+  if (const int v = wgrad_halo_variant(a, MT, NTT)) {   // (pipe: wh_t's rule)
+    wgrad_sig_at(v).alone(a, grid, lds, grid.x * grid.y * grid.z < 512 && a.blocks_per_split > 1, s);
+    return;
+  }
   const int mtw = (MT + (a.bslab ? 1 : 0) + 3) / 4;
 #define C(M_, N_)                                            \
   if (mtw <= M_ && NTT == N_) {                              \

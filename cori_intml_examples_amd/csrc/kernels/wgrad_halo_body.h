@@ -18,11 +18,41 @@ __device__ __forceinline__ bf16x4 tr_read_h(const bf16* p) {
 #define WH_STAMP(i)                                                                     \
   if (INSTR && a.ts2 && threadIdx.x == 0 && (i) < 16) a.ts2[(size_t)blockIdx.x * 16 + (i)] = wall_clock64();
 
+// Where the body reads its geometry (template parameter G).  The pointers, the batch size B,
+// blocks_per_split and the grid always come from WgradArgs.
+//   WgGeoRt: every value is the WgradArgs field (MT the launch's) -- the generic kernels.
+//   WgGeoFix<S, XIDX>: constants of a layer signature S (wgrad_sig.h); the staging index math,
+//     the FastDiv divisors and the path choices (rowal, pexp, the bias tile, write-through)
+//     fold at compile time.  XIDX: the input is read through a.xidx.
+// (WG_GEO_INTS, args.h: the one list of the geometry fields)
+struct WgGeoRt {
+#define F(n) \
+  __device__ __forceinline__ static int n(const WgradArgs& a) { return a.n; }
+  WG_GEO_INTS(F)
+#undef F
+  __device__ __forceinline__ static int MT(int mt_launch) { return mt_launch; }
+  __device__ __forceinline__ static bool pooled(const WgradArgs& a) { return a.dy_code != nullptr; }
+  __device__ __forceinline__ static bool bias(const WgradArgs& a) { return a.bslab != nullptr; }
+  __device__ __forceinline__ static bool xidx(const WgradArgs& a) { return a.xidx != nullptr; }
+};
+template <class S, bool XIDX>
+struct WgGeoFix {
+#define F(n) \
+  __device__ __forceinline__ static constexpr int n(const WgradArgs&) { return S::n; }
+  WG_GEO_INTS(F)
+#undef F
+  __device__ __forceinline__ static constexpr int MT(int) { return S::MT; }
+  __device__ __forceinline__ static constexpr bool pooled(const WgradArgs&) { return S::pooled; }
+  __device__ __forceinline__ static constexpr bool bias(const WgradArgs&) { return S::bias; }
+  __device__ __forceinline__ static constexpr bool xidx(const WgradArgs&) { return XIDX; }
+};
+
 // image b of the wgrad input: the activation buffer, or (prologue-free step, first layer)
 // dataset row xidx[b] of the bound dataset
+template <class G>
 __device__ __forceinline__ const bf16* wg_xbase(const WgradArgs& a, int b) {
-  if (a.xidx) return reinterpret_cast<const bf16*>(a.xst->data_x) + (size_t)a.xidx[b] * a.xst->data_R;
-  return a.x + (size_t)b * a.H * a.W * a.Cs_in;
+  if (G::xidx(a)) return reinterpret_cast<const bf16*>(a.xst->data_x) + (size_t)a.xidx[b] * a.xst->data_R;
+  return a.x + (size_t)b * G::H(a) * G::W(a) * G::Cs_in(a);
 }
 
 // row stride (floats) of a wave's 16x16 write-through staging square: rows 4 apart land
@@ -31,19 +61,21 @@ __device__ __forceinline__ const bf16* wg_xbase(const WgradArgs& a, int b) {
 
 // INSTR: the ablation switches (dbg) and diagnostics stamps (a.ts2) are compiled in (the
 // co-scheduled dual launch instantiates false)
-template <int MTW, int NTT, bool CS4, bool PIPE, bool INSTR = true>
-__device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT, const int bx, const int by,
+// G: the geometry source (WgGeoRt / WgGeoFix above); MT_launch is read by WgGeoRt only
+template <int MTW, int NTT, bool CS4, bool PIPE, bool INSTR = true, class G = WgGeoRt>
+__device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT_launch, const int bx, const int by,
                                                 const int bz, char* smem) {
+  const int MT = G::MT(MT_launch);
   const int dbg = INSTR ? a.dbg : 0;
-  const int R = a.R, s = a.stride, Cs = a.Cs_in;
-  const int W_in = (a.Wo - 1) * s + a.KW;
-  const int R_in = (R - 1) * s + a.KH;
-  const int npb = R * a.Wo;                         // pixels per full block
+  const int R = G::R(a), s = G::stride(a), Cs = G::Cs_in(a);
+  const int W_in = (G::Wo(a) - 1) * s + G::KW(a);
+  const int R_in = (R - 1) * s + G::KH(a);
+  const int npb = R * G::Wo(a);                         // pixels per full block
   const int npb32 = (npb + 31) & ~31;
   // LDS layout (bank-conflict model, models/lds_layout.py): X-halo pixel stride XP and row
   // stride XR (pixels), dY row stride ldb; 0 = dense
-  const int XP = a.xpix ? a.xpix : Cs, XR = a.xrow ? a.xrow : W_in;
-  const int ldb = a.dyld ? a.dyld : NTT * 16 + 8;   // dY LDS row stride (elements)
+  const int XP = G::xpix(a) ? G::xpix(a) : Cs, XR = G::xrow(a) ? G::xrow(a) : W_in;
+  const int ldb = G::dyld(a) ? G::dyld(a) : NTT * 16 + 8;   // dY LDS row stride (elements)
   bf16* xl = reinterpret_cast<bf16*>(smem);
   const int x_elems = ((R_in * XR * XP) + 7) & ~7;
   bf16* dyl = xl + x_elems;
@@ -57,8 +89,8 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
             g = lane >> 4;
   const int mt0 = bz * MT;
   const int nt0 = by * NTT;
-  const int KHW = a.KH * a.KW;
-  const bool do_bias = a.bslab != nullptr && bz == 0;
+  const int KHW = G::KH(a) * G::KW(a);
+  const bool do_bias = G::bias(a) && bz == 0;
   const int MTb = MT + (do_bias ? 1 : 0);          // pseudo m-tile MT = bias (ones operand)
 
   WH_STAMP(0);
@@ -67,9 +99,9 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
     const int k = (mt0 + c / 4) * 16 + 4 * (c & 3);
     const int tap = k / Cs;
     int e = -1;
-    if (tap < KHW && mt0 + c / 4 < a.Ktiles) {
-      const int ky = tap / a.KW;
-      e = (ky * XR + (tap - ky * a.KW)) * XP + (k - tap * Cs);
+    if (tap < KHW && mt0 + c / 4 < G::Ktiles(a)) {
+      const int ky = tap / G::KW(a);
+      e = (ky * XR + (tap - ky * G::KW(a))) * XP + (k - tap * Cs);
     }
     ktab[c] = e;
   }
@@ -94,7 +126,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
 #pragma unroll
     for (int v = 0; v < NTT; ++v) acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nrb = (a.Ho + R - 1) / R;
+  const int nrb = (G::Ho(a) + R - 1) / R;
   const int nblocks = a.B * nrb;
   const int blk0 = bx * a.blocks_per_split;
   const int blk1 = min(nblocks, blk0 + a.blocks_per_split);
@@ -103,17 +135,17 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
   const int cpr = NTT * 2;
   const int nch_x = R_in * W_in * cpp;              // X-halo chunks per block
   const int nch_y = npb32 * cpr;                    // dY chunks per block
-  const FastDiv fcpp(cpp), fwin(W_in), fcpr(cpr), fwo(a.Wo);
+  const FastDiv fcpp(cpp), fwin(W_in), fcpr(cpr), fwo(G::Wo(a));
 
   const bool dbg_stage = !(dbg & 1);
   // Pooled dY (dP + argmax codes) over whole even blocks: stage each pooled chunk ONCE and
   // expand it into its 2x2 window's pixel rows in LDS (a quarter of the global loads of a
   // per-pixel unpool; every LDS dY element of the block is written, zeros included).
-  const int hw = a.Wo >> 1;
+  const int hw = G::Wo(a) >> 1;
   // (pipelined path only: in the plain path its extra registers cost occupancy -- measured)
-  const bool pexp = PIPE && a.dy_code && !(dbg & 16) && (R & 1) == 0 && a.Ho % R == 0 && (a.Wo & 1) == 0 &&
-                    npb32 == npb && a.NT % NTT == 0 && a.NT * 16 <= a.Cs_dy && 2 * a.dHp >= a.Ho &&
-                    2 * a.dWp >= a.Wo;
+  const bool pexp = PIPE && G::pooled(a) && !(dbg & 16) && (R & 1) == 0 && G::Ho(a) % R == 0 && (G::Wo(a) & 1) == 0 &&
+                    npb32 == npb && G::NT(a) % NTT == 0 && G::NT(a) * 16 <= G::Cs_dy(a) && 2 * G::dHp(a) >= G::Ho(a) &&
+                    2 * G::dWp(a) >= G::Wo(a);
   const int nq = (R >> 1) * hw * cpr;               // pooled dY chunks per block
   const FastDiv fhw(hw > 0 ? hw : 1);
   // pooled chunk q of the block starting at conv row oy0 -> global dP offset (in elements)
@@ -121,7 +153,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
     const int p2 = fcpr.div(q), ch = q - p2 * cpr;
     const int ry = fhw.div(p2);
     const int wy = (oy0 >> 1) + ry, wx = p2 - ry * hw;
-    return (((size_t)b * a.dHp + wy) * a.dWp + wx) * a.Cs_dy + nt0 * 16 + ch * 8;
+    return (((size_t)b * G::dHp(a) + wy) * G::dWp(a) + wx) * G::Cs_dy(a) + nt0 * 16 + ch * 8;
   };
   // write pooled chunk q (dP values v, codes cw) to the 4 pixels of its window
   // ... the same from the chunk's precomputed LDS offset (window's top-left pixel row)
@@ -137,14 +169,14 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         m[2 * h + 1] = ((((w >> 16) & 0xFF) == (uint32_t)pos) ? 0x0000FFFFu : 0u) |
                        ((((w >> 24) & 0xFF) == (uint32_t)pos) ? 0xFFFF0000u : 0u);
       }
-      *reinterpret_cast<uint4*>(dyl + dst + ((pos >> 1) * a.Wo + (pos & 1)) * ldb) =
+      *reinterpret_cast<uint4*>(dyl + dst + ((pos >> 1) * G::Wo(a) + (pos & 1)) * ldb) =
           uint4{v.x & m[0], v.y & m[1], v.z & m[2], v.w & m[3]};
     }
   };
   auto pq_store = [&](int q, const uint4& v, const uint2& cw) {
     const int p2 = fcpr.div(q), ch = q - p2 * cpr;
     const int ry = fhw.div(p2);
-    const int p00 = (2 * ry) * a.Wo + 2 * (p2 - ry * hw);
+    const int p00 = (2 * ry) * G::Wo(a) + 2 * (p2 - ry * hw);
 #pragma unroll
     for (int pos = 0; pos < 4; ++pos) {
       uint32_t m[4];
@@ -156,7 +188,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         m[2 * h + 1] = ((((w >> 16) & 0xFF) == (uint32_t)pos) ? 0x0000FFFFu : 0u) |
                        ((((w >> 24) & 0xFF) == (uint32_t)pos) ? 0xFFFF0000u : 0u);
       }
-      const int p = p00 + (pos >> 1) * a.Wo + (pos & 1);
+      const int p = p00 + (pos >> 1) * G::Wo(a) + (pos & 1);
       *reinterpret_cast<uint4*>(dyl + (size_t)p * ldb + ch * 8) =
           uint4{v.x & m[0], v.y & m[1], v.z & m[2], v.w & m[3]};
     }
@@ -164,7 +196,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
 
   // MFMA reduction over the staged block's npix pixels
   // per-lane pixel offsets within a 32-pixel k-step (the kperm bijection, see below)
-  const int dP0 = ((a.kperm & 1) ? 4 * g : 8 * g) + (i >> 2), dP1 = dP0 + ((a.kperm & 1) ? 16 : 4);
+  const int dP0 = ((G::kperm(a) & 1) ? 4 * g : 8 * g) + (i >> 2), dP1 = dP0 + ((G::kperm(a) & 1) ? 16 : 4);
   auto mma_block = [&](const int npix) {
       const int nks = (dbg & 2) ? 0 : (npix + 31) >> 5;
       // Row-aligned fast path (output width % 32 == 0, whole k-steps): a k-step's 32 pixels
@@ -172,7 +204,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
       // constant -- no per-step division or clamping (same pixels, same k order).  One MFMA
       // body for both paths (a second copy doubled the accumulators' AGPRs and halved the
       // occupancy of the dual kernels).
-      const bool rowal = (a.Wo & 31) == 0 && (npix & 31) == 0 && !(a.kperm & 2);
+      const bool rowal = (G::Wo(a) & 31) == 0 && (npix & 31) == 0 && !(G::kperm(a) & 2);
       const int la0 = dP0 * s * XP, la1 = dP1 * s * XP;
       int y = 0, x0 = 0;
       // (a row-divisor form of the scalar k-step base -- widths dividing 32, RPV conv2's 16-wide
@@ -189,13 +221,13 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         int off0, off1;
         if (rowal) {
           const int base = __builtin_amdgcn_readfirstlane(((y * s) * XR + x0 * s) * XP);
-          if ((x0 += 32) == a.Wo) { x0 = 0; ++y; }
+          if ((x0 += 32) == G::Wo(a)) { x0 = 0; ++y; }
           off0 = base + la0, off1 = base + la1;
         } else {
           const int q0 = min(P0, npix - 1), q1 = min(P1, npix - 1);
           const int y0 = fwo.div(q0), y1 = fwo.div(q1);
-          off0 = ((y0 * s) * XR + (q0 - y0 * a.Wo) * s) * XP;
-          off1 = ((y1 * s) * XR + (q1 - y1 * a.Wo) * s) * XP;
+          off0 = ((y0 * s) * XR + (q0 - y0 * G::Wo(a)) * s) * XP;
+          off1 = ((y1 * s) * XR + (q1 - y1 * G::Wo(a)) * s) * XP;
         }
         const bf16* pbrow = dyl + (size_t)P0 * ldb + 4 * (i & 3);
   #pragma unroll
@@ -249,11 +281,11 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
       const int idx = min(tid + u * 256, nch_x - 1);
       const int pix = fcpp.div(idx), c = (idx - pix * cpp) * cw;
       const int r = fwin.div(pix), px = pix - r * W_in;
-      const int ix = px - a.pad_l;
+      const int ix = px - G::pad_l(a);
       xa[u] = (r * XR + px) * XP + c;
       xrow[u] = r;
-      xoff[u] = (r * a.W + ix) * Cs + c;
-      if (ix >= 0 && ix < a.W) xcol |= 1u << u;
+      xoff[u] = (r * G::W(a) + ix) * Cs + c;
+      if (ix >= 0 && ix < G::W(a)) xcol |= 1u << u;
     }
     if (pexp) {
 #pragma unroll
@@ -261,20 +293,20 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         const int q = min(tid + u * 256, nq - 1);
         const int p2 = fcpr.div(q), ch = q - p2 * cpr;
         const int ry = fhw.div(p2), wx = p2 - ry * hw;
-        qoff[u] = (ry * a.dWp + wx) * a.Cs_dy + nt0 * 16 + ch * 8;
-        qdst[u] = ((2 * ry) * a.Wo + 2 * wx) * ldb + ch * 8;
+        qoff[u] = (ry * G::dWp(a) + wx) * G::Cs_dy(a) + nt0 * 16 + ch * 8;
+        qdst[u] = ((2 * ry) * G::Wo(a) + 2 * wx) * ldb + ch * 8;
       }
     }
     auto fetch = [&](const int blk) {
       const int b = blk / nrb, oy0 = (blk - b * nrb) * R;
-      const int npix = min(R, a.Ho - oy0) * a.Wo;
-      const int yb = oy0 * s - a.pad_t;
-      const bf16* xbase = wg_xbase(a, b);
-      const bf16* xrow0 = xbase + (ptrdiff_t)yb * a.W * Cs;         // may point before xbase
+      const int npix = min(R, G::Ho(a) - oy0) * G::Wo(a);
+      const int yb = oy0 * s - G::pad_t(a);
+      const bf16* xbase = wg_xbase<G>(a, b);
+      const bf16* xrow0 = xbase + (ptrdiff_t)yb * G::W(a) * Cs;         // may point before xbase
 #pragma unroll
       for (int u = 0; u < WH_PX; ++u) {
         const int iy = yb + xrow[u];
-        const bool ok = ((xcol >> u) & 1u) && iy >= 0 && iy < a.H;
+        const bool ok = ((xcol >> u) & 1u) && iy >= 0 && iy < G::H(a);
         const bf16* src = ok ? xrow0 + xoff[u] : xbase;
         if (CS4) {
           const uint2 v = *reinterpret_cast<const uint2*>(src);
@@ -285,7 +317,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         }
       }
       if (pexp) {
-        const size_t qb = (((size_t)b * a.dHp + (oy0 >> 1)) * a.dWp) * a.Cs_dy;
+        const size_t qb = (((size_t)b * G::dHp(a) + (oy0 >> 1)) * G::dWp(a)) * G::Cs_dy(a);
 #pragma unroll
         for (int u = 0; u < WH_PY; ++u) {
           const size_t o = qb + qoff[u];
@@ -294,25 +326,25 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         }
         return;
       }
-      const size_t boff = (size_t)b * a.dHp * a.dWp * a.Cs_dy;
+      const size_t boff = (size_t)b * G::dHp(a) * G::dWp(a) * G::Cs_dy(a);
 #pragma unroll
       for (int u = 0; u < WH_PY; ++u) {
         const int idx = min(tid + u * 256, nch_y - 1);
         const int p = fcpr.div(idx);
         const int n0 = nt0 * 16 + (idx - p * cpr) * 8;
-        bool ok = p < npix && n0 < a.Cs_dy;
+        bool ok = p < npix && n0 < G::Cs_dy(a);
         const int pp = ok ? p : 0;
         const int pyl = fwo.div(pp);
-        const int oy = oy0 + pyl, ox = pp - pyl * a.Wo;
+        const int oy = oy0 + pyl, ox = pp - pyl * G::Wo(a);
         size_t o;
-        if (a.dy_code) {   // pooled: dP + argmax code of the window (unpool on commit)
+        if (G::pooled(a)) {   // pooled: dP + argmax code of the window (unpool on commit)
           const int wy = oy >> 1, wx = ox >> 1;
-          ok = ok && wy < a.dHp && wx < a.dWp;
-          o = ok ? boff + ((size_t)wy * a.dWp + wx) * a.Cs_dy + n0 : 0;
+          ok = ok && wy < G::dHp(a) && wx < G::dWp(a);
+          o = ok ? boff + ((size_t)wy * G::dWp(a) + wx) * G::Cs_dy(a) + n0 : 0;
           yc[u] = *reinterpret_cast<const uint2*>(a.dy_code + o);
           yp[u] = ok ? (uint32_t)(((oy & 1) << 1) | (ox & 1)) : 0xFFu;
         } else {
-          o = ok ? (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cs_dy + n0 : 0;
+          o = ok ? (((size_t)b * G::Ho(a) + oy) * G::Wo(a) + ox) * G::Cs_dy(a) + n0 : 0;
           yc[u] = uint2{0u, 0u};
           yp[u] = ok ? 0u : 0xFFu;
         }
@@ -339,7 +371,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
         if (idx >= nch_y) continue;
         uint4 v = yr[u];
         const uint32_t pos = yp[u];
-        if (a.dy_code) {   // keep element j iff its argmax code is this pixel's window position
+        if (G::pooled(a)) {   // keep element j iff its argmax code is this pixel's window position
           uint32_t m[4];
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
@@ -361,7 +393,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
     WH_STAMP(1);
     for (int blk = blk0; blk < blk1; ++blk) {
       const int b = blk / nrb, oy0 = (blk - b * nrb) * R;
-      const int npix = min(R, a.Ho - oy0) * a.Wo;
+      const int npix = min(R, G::Ho(a) - oy0) * G::Wo(a);
       if (blk != blk0) __syncthreads();   // previous block's readers are done
       commit();
       __syncthreads();
@@ -375,19 +407,19 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
     for (int blk = blk0; blk < blk1; ++blk) {
       const int b = blk / nrb;
       const int oy0 = (blk - b * nrb) * R;
-      const int rows = min(R, a.Ho - oy0);
-      const int npix = rows * a.Wo;
+      const int rows = min(R, G::Ho(a) - oy0);
+      const int npix = rows * G::Wo(a);
       if (blk != blk0) __syncthreads();   // previous block's readers are done
       if (dbg_stage) {   // X halo
-        const int yb = oy0 * s - a.pad_t, xb0 = -a.pad_l;
-        const bf16* xbase = wg_xbase(a, b);
+        const int yb = oy0 * s - G::pad_t(a), xb0 = -G::pad_l(a);
+        const bf16* xbase = wg_xbase<G>(a, b);
         auto coords = [&](int idx, int& c, int& iy, int& ix) -> bool {
           const int pix = fcpp.div(idx);
           c = (idx - pix * cpp) * cw;
           const int r = fwin.div(pix);
           iy = yb + r;
           ix = xb0 + (pix - r * W_in);
-          return iy >= 0 && ix >= 0 && iy < a.H && ix < a.W;
+          return iy >= 0 && ix >= 0 && iy < G::H(a) && ix < G::W(a);
         };
         // (the LDS offset rides along with the loaded value: the coordinates are computed
         // once, in the load, instead of again in the store)
@@ -397,7 +429,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
               [&](int idx) {
                 int c, iy, ix;
                 const bool ok = coords(idx, c, iy, ix);
-                return XChunk4{load_bf16x4_if(ok, xbase + ((size_t)iy * a.W + ix) * 4, xbase),
+                return XChunk4{load_bf16x4_if(ok, xbase + ((size_t)iy * G::W(a) + ix) * 4, xbase),
                                ((iy - yb) * XR + (ix - xb0)) * XP + c};
               },
               [&](int, const XChunk4& v) { *reinterpret_cast<bf16x4*>(xl + v.o) = v.v; });
@@ -407,7 +439,7 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
               [&](int idx) {
                 int c, iy, ix;
                 const bool ok = coords(idx, c, iy, ix);
-                return XChunk8{load_bf16x8_if(ok, xbase + ((size_t)iy * a.W + ix) * Cs + c, xbase),
+                return XChunk8{load_bf16x8_if(ok, xbase + ((size_t)iy * G::W(a) + ix) * Cs + c, xbase),
                                ((iy - yb) * XR + (ix - xb0)) * XP + c};
               },
               [&](int, const XChunk8& v) { *reinterpret_cast<bf16x8*>(xl + v.o) = v.v; });
@@ -429,18 +461,18 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
             if (q0 + u * 256 < nq) pq_store(q0 + u * 256, v[u], cw[u]);
         }
       } else if (dbg_stage) {   // dY rows (rebuilt from pooled dP + codes when the conv is pooled)
-        const size_t boff = (size_t)b * a.dHp * a.dWp * a.Cs_dy;
+        const size_t boff = (size_t)b * G::dHp(a) * G::dWp(a) * G::Cs_dy(a);
         staged_copy<8, bf16x8>(
             nch_y, tid, 256,
             [&](int idx) {
               const int p = fcpr.div(idx);
               const int n0 = nt0 * 16 + (idx - p * cpr) * 8;
-              const bool ok = p < npix && n0 < a.Cs_dy;
+              const bool ok = p < npix && n0 < G::Cs_dy(a);
               const int pp = ok ? p : 0;
               const int pyl = fwo.div(pp);
-              const int oy = oy0 + pyl, ox = pp - pyl * a.Wo;
-              if (a.dy_code) return unpool_load8(a.dy + boff, a.dy_code + boff, a.dHp, a.dWp, a.Cs_dy, oy, ox, n0, ok);
-              return load_bf16x8_if(ok, a.dy + (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cs_dy + n0, a.dy);
+              const int oy = oy0 + pyl, ox = pp - pyl * G::Wo(a);
+              if (G::pooled(a)) return unpool_load8(a.dy + boff, a.dy_code + boff, G::dHp(a), G::dWp(a), G::Cs_dy(a), oy, ox, n0, ok);
+              return load_bf16x8_if(ok, a.dy + (((size_t)b * G::Ho(a) + oy) * G::Wo(a) + ox) * G::Cs_dy(a) + n0, a.dy);
             },
             [&](int idx, const bf16x8& v) {
               const int p = fcpr.div(idx);
@@ -455,8 +487,8 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
     }
   }
 
-  const int ld = a.NT * 16;
-  float* slab = a.slab + (size_t)bx * a.Ktiles * 16 * ld;
+  const int ld = G::NT(a) * 16;
+  float* slab = a.slab + (size_t)bx * G::Ktiles(a) * 16 * ld;
   if (dbg & 4) {
 #pragma unroll
     for (int u = 0; u < MTW; ++u)
@@ -469,26 +501,26 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
   // leaves as one 16-byte sc1 store per lane (4 rows x 64 B), so the launch ends with none
   // of its partial bytes dirty in L2; plain form: 4 scalar stores per lane
   float* sq = reinterpret_cast<float*>(smem) + wave * (16 * WH_SQ);
-  if (a.wt) __syncthreads();   // the staging images' last readers are done: LDS is scratch
+  if (G::wt(a)) __syncthreads();   // the staging images' last readers are done: LDS is scratch
 #pragma unroll
   for (int u = 0; u < MTW; ++u) {
     const int mt = wave + 4 * u;
     if (u >= nval) continue;
 #pragma unroll
     for (int v = 0; v < NTT; ++v) {
-      if (nt0 + v >= a.NT) continue;
+      if (nt0 + v >= G::NT(a)) continue;
       if (u == ubias) {   // bias tile: every row holds the column sums; row 0 lives in lanes 0..15
         if (g == 0) a.bslab[(size_t)bx * ld + (nt0 + v) * 16 + i] = acc[u][v][0];
         continue;
       }
-      if (mt0 + mt >= a.Ktiles) continue;
-      if (a.wt) {
+      if (mt0 + mt >= G::Ktiles(a)) continue;
+      if (G::wt(a)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) sq[(g * 4 + j) * WH_SQ + i] = acc[u][v][j];
         __builtin_amdgcn_wave_barrier();
         const int row = lane >> 2, c4 = (lane & 3) * 4;
         const u32x4 val = *reinterpret_cast<const u32x4*>(sq + row * WH_SQ + c4);
-        const size_t off = (size_t)bx * a.Ktiles * 16 * ld + (size_t)((mt0 + mt) * 16 + row) * ld + (nt0 + v) * 16 + c4;
+        const size_t off = (size_t)bx * G::Ktiles(a) * 16 * ld + (size_t)((mt0 + mt) * 16 + row) * ld + (nt0 + v) * 16 + c4;
         st_wt16(a.slab, (unsigned)(off * 4), val);
         __builtin_amdgcn_wave_barrier();
         continue;

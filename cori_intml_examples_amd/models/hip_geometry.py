@@ -440,6 +440,11 @@ class GeometryMixin:
         a.bslab = bslab.data_ptr() if bslab is not None else 0
         # write-through slabs (16-byte sc1 stores, byte offsets < 2 GB)
         a.wt = int(bool(int(tune("wt", 7)) & 4) and slab.numel() * 4 < (1 << 31))
+        # layer-signature instances (geometry fixed at compile time, csrc/kernels/wgrad_sig.h)
+        # where one matches; wgrad_spec=0: always the generic kernels (A/B, bit-identity tests).
+        # The split count above is sized by the GENERIC instance's residency either way, so the
+        # slab layout and the reduction order do not depend on this switch.
+        a.spec = int(tune("wgrad_spec", 1))
         self.wgrad_slabs.append((slab, bslab))
         return a, (MT, NTT, S), slab, bslab
 
