@@ -17,18 +17,20 @@ from __future__ import annotations
 import gc
 import os
 from dataclasses import dataclass, field
+from operator import attrgetter
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from ..ops.hip import kernels
-from ..ops.rng import keep_threshold
 from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, fill_kernel_args
 from ..utils.env import env_flag, tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin, cdiv, r8  # noqa: F401  (cdiv: re-exported for tests)
 from .plan import Plan
+from .step_program import (Exchange, Launch, RedDesc, RedGroup, check_bucket_cover,  # noqa: F401  (re-exported)
+                           defer_after_readers, dropout_pair, splice_bucket_launches, stream_program)
 
 BF16 = torch.bfloat16
 # views of the optimizer-kind table (optim/optimizers.py KINDS).  STANDALONE_KINDS: kinds with
@@ -104,83 +106,6 @@ class DenseGeo:
     pack_bwd: int = -1
 
 
-def splice_bucket_launches(launches, inserts, per_bucket):
-    """Insert each bucket's launches into the step's launch list.
-
-    ``inserts``: (launch index after which bucket k's partial slabs are final, k);
-    ``per_bucket``: [(name pattern, factory k -> fn(stream), stream tag)] appended, in
-    order, at that point (slab reduction, then all-reduce / optimizer on the comm stream).
-    Returns (new launch list, bucket_ready[k] = index just past bucket k's launches)."""
-    out, ready, pos = [], [0] * len(inserts), 0
-    for at, k in sorted(inserts):
-        out.extend(launches[pos:at])
-        pos = at
-        for pat, make, tag in per_bucket:
-            fn = make(k)
-            if fn is not None:          # a factory returns None for buckets it does not apply to
-                out.append((pat % k, fn, tag))
-        ready[k] = len(out)
-    out.extend(launches[pos:])
-    return out, ready
-
-
-def defer_after_readers(launches, pattern, spans, readers):
-    """Move each bucket's comm-stream optimizer (launch name ``pattern % k``) behind the
-    last launch that reads a bf16 pack of a parameter in bucket k's span ``spans[k]``.
-
-    The optimizer writes the packs of the weights it updates (pack routes), and a
-    comm-stream launch forks after everything issued on main before it: a bucket whose
-    slabs are final before a later dgrad / dense-dX launch reads the same layer's pack
-    (wide convs have no dual launch, so their dgrad runs after the wgrad) must not update
-    that pack while the reader runs.  ``readers``: [(launch name, param lo, param hi)].
-    Returns the new launch list (the all-reduce stays where it was, so it still overlaps)."""
-    out = list(launches)
-    for k, (lo, hi) in enumerate(spans):
-        names = [it[0] for it in out]
-        name = pattern % k
-        if name not in names:
-            continue
-        at = names.index(name)
-        rd = {rn for rn, rlo, rhi in readers if rlo < hi and rhi > lo}
-        last = max((i for i, n in enumerate(names) if n in rd), default=-1)
-        if last > at:
-            item = out.pop(at)
-            out.insert(last, item)          # (the pop shifted the reader to last - 1)
-    return out
-
-
-def stream_program(tags, comm=True):
-    """The stream schedule of a launch sequence, as a list of ops:
-    ("run", stream, i)  launch i on "main" / "comm";
-    ("wait", dst, src)  make stream dst wait for everything issued so far on src.
-
-    'main' launches (any tag other than 'comm': 'side' marks the launches that only feed a
-    slab reduction) run in order on the current stream.  'comm' launches fork the comm
-    stream after everything issued so far (the bucket's slab reduction) -- RCCL and the
-    bucket's optimizer run there while main continues the backward -- and the comm stream
-    is joined back into main at the end.  ``comm=False``: comm launches run in order on main
-    (a linear graph)."""
-    ops, used = [], False
-    for i, tag in enumerate(tags):
-        if tag == "comm" and comm:
-            ops.append(("wait", "comm", "main"))
-            ops.append(("run", "comm", i))
-            used = True
-        else:
-            ops.append(("run", "main", i))
-    if used:
-        ops.append(("wait", "main", "comm"))
-    return ops
-
-
-def check_bucket_cover(spans, numel):
-    """Bucket (lo, hi) spans must tile [0, numel) exactly: disjoint, no gap, nothing left
-    out (every gradient is reduced, all-reduced and updated exactly once)."""
-    sp = sorted(spans)
-    if not sp or sp[0][0] != 0 or sp[-1][1] != numel or any(a[1] != b[0] for a, b in zip(sp, sp[1:])):
-        raise AssertionError("gradient buckets %s do not tile [0, %d)" % (spans, numel))
-
-
 class HipExecutor(Executor):
     def __init__(self, plan: Plan, store, optimizer, seed: int):
         super().__init__(plan, store, optimizer, seed)
@@ -206,6 +131,7 @@ class HipExecutor(Executor):
         self._plans: Dict[Tuple[int, str], "BatchPlan"] = {}
         self._lr_host = None
         self._expected_pos = None
+        self._expected_eval_pos = None
         self._bound_data = None
         self._bound_ref = None
         self._bound_w = 0
@@ -315,7 +241,7 @@ class HipExecutor(Executor):
             routes.append((sp.offset, sp.offset + sp.numel, 2, g.src.H * g.src.W, g.src.C, g.N, g.src.Cs, 0,
                            g.NT, g.NTb if g.KSb else 0, g.pack_fwd, g.pack_bwd if g.KSb else -1))
         # (a dense layer whose optimizer runs inside its wgrad kernel writes its packs there
-        # too -- WgradArgs.pk_fwd -- or is not fused: see BatchPlan._build_args)
+        # too -- WgradArgs.pk_fwd -- or is not fused: see BatchPlan._dense_wgrad)
         self.routes_ok = bool(routes) and len(routes) <= K.MAX_ROUTES and tune("opt_packs", True)
         self.routes = None
         self.route_list = routes
@@ -494,7 +420,7 @@ class HipExecutor(Executor):
         self.opt.iterations += k
 
     def _set_eval_pos(self, pos, bs):
-        if getattr(self, "_expected_eval_pos", None) != pos:
+        if self._expected_eval_pos != pos:
             self._st_i32[3] = pos
         self._expected_eval_pos = pos + bs
 
@@ -547,6 +473,11 @@ class BatchPlan(GeometryMixin):
     """Buffers + prepared kernel argument structs for one (batch size, mode); records the
     launch sequence and replays it from a HIP graph."""
 
+    # the exchange plan's fields, readable on the plan under their names as well
+    early_push, early_xchg, xchg_end, xchg_fin, bucket_xchg, pushed, exchanged = (
+        property(attrgetter("xchg." + n)) for n in ("early_push", "early_xchg", "xchg_end", "xchg_fin",
+                                                    "bucket_xchg", "pushed", "exchanged"))
+
     def __init__(self, ex: HipExecutor, bs: int, mode: str, weighted: bool = False):
         self.ex, self.bs, self.mode = ex, bs, mode
         self.weighted = bool(weighted) and mode != "predict"
@@ -558,8 +489,19 @@ class BatchPlan(GeometryMixin):
         self.dp_graphs = None
         # (a second compute stream for the weight gradients and a per-bucket early optimizer
         # stream were measured slower on one MI355X and removed: docs/ARCHITECTURE.md §6)
-        self.optim_fused = False           # set by _build_reduce
-        self.early_red = {}                # dual launch name -> (RedTable, span): set by _build_reduce
+        self.optim_fused = False           # set by _assign_buckets
+        self.early_red = {}                # dual launch name -> (RedTable, span, grad_only): _early_groups
+        self.xchg = Exchange()             # the xGMI exchange plan of a data-parallel step
+        self.launches: List[Launch] = []
+        self.srcidx = None                 # prologue-free step: the dataset row of each image
+        self.stack_args = None
+        self.red_groups: List[RedGroup] = []   # per layer, in backward order
+        self.pack_readers = []     # (launch name, param lo, hi): backward launches reading a layer's pack
+        self.wgrad_slabs = []
+        self.dense_fused_opt = []          # (WgradArgs, params) updated inside dense_wgrad
+        self.bucket_tables, self.bucket_ready = [], []
+        self._no_packs = K.PackTable()     # a comm-stream optimizer re-packs nothing
+        self._ncu = self._zero16 = None    # hip_geometry: CU count, the DMA kernels' zero bytes
         # Native RCCL data plane: the bucket all-reduces are part of the launch sequence (on
         # their own comm stream) and captured with the rest of the step into ONE HIP graph.
         red = ex.reducer
@@ -567,7 +509,7 @@ class BatchPlan(GeometryMixin):
                               and red.active and tune("comm_capture", True))
         # tune comm_fork=0: the captured all-reduces stay on the main stream (a linear graph:
         # no cross-queue edges, whose graph-launch cost is several us each, but no overlap)
-        # (default: fork only when there is more than one bucket to overlap; set in _build_reduce)
+        # (default: fork only when there is more than one bucket to overlap; set in _comm_launches)
         self.comm_fork = None
         self.comm_stream = None
         # ... and each bucket's optimizer update follows its all-reduce on the comm stream (the
@@ -653,21 +595,38 @@ class BatchPlan(GeometryMixin):
             rate, stream = g.rate, g.stream
             bt.dy = self.dense_dh[g.j].data_ptr()
         if rate > 0:
-            bt.drop_thr = keep_threshold(rate)
-            bt.drop_scale = 1.0 / (1.0 - rate)
+            bt.drop_thr, bt.drop_scale = dropout_pair(rate)
         bt.seed, bt.stream_id = ex.seed, stream
         # write-through gradient stores (16-byte sc1; byte offsets < 2 GB)
         dyb = self.conv_dy[g.i] if src.kind == "conv" else self.dense_dh[g.j]
         bt.wt = int(bool(int(tune("wt", 7)) & 2) and dyb.numel() * 2 < (1 << 31))
         return bt
 
-    def _build_args(self):
-        ex, K, bs = self.ex, self.ex.K, self.bs
-        st_ptr = ex.state.data_ptr()
-        store = ex.store
-        training = self.training
-        self.launches = []          # list of (name, callable(stream))
+    # ---------------------------------------------------------------- step program: forward
+    def _add(self, name, fn, tag="main", **args):
+        self.launches.append(Launch(name, fn, tag, args))
 
+    def _build_args(self):
+        """The step program, stage by stage; each stage appends its launches."""
+        ex = self.ex
+        stack, sb = self._build_prologue()
+        self._build_conv_fwd(stack)
+        head_epi = self._build_dense_fwd(sb)
+        self._build_head(head_epi)
+        if not self.training:
+            return
+        self._begin_backward()
+        for g, ds in reversed(list(zip(ex.denses, ex.plan.denses))):
+            self._build_dense_bwd(g, ds)
+        for g, cs in reversed(list(zip(ex.convs, ex.plan.convs))):
+            self._build_conv_bwd(g, cs)
+        self._build_reduce()
+
+    def _build_prologue(self):
+        """The prologue launch (gather + re-pack + bookkeeping), unless the step is prologue-free.
+        Returns (the conv stack's args or None, the StepBeginArgs)."""
+        ex, K, bs, training = self.ex, self.ex.K, self.bs, self.training
+        st_ptr = ex.state.data_ptr()
         # step begin
         sb = K.StepBeginArgs()
         sb.st = st_ptr
@@ -692,7 +651,6 @@ class BatchPlan(GeometryMixin):
         # targets), the optimizer keeps the bf16 packs current, and the first dense launch runs
         # the step bookkeeping -- the step has no prologue launch
         self.pro_free = bool(stack is not None and ex.denses and ex.routes_ok and tune("pro_free", True))
-        self.srcidx = None
         if self.pro_free:
             self.srcidx = torch.zeros(max(bs, 1), dtype=torch.int32, device=ex.device)
             stack.from_data, stack.training, stack.step_inc = 1, int(training), int(training)
@@ -707,30 +665,32 @@ class BatchPlan(GeometryMixin):
             pa.pack_mode = 0
         elif pro_dbg == 2:
             pa.gather_blocks = 0
-        pa.master = store.master.data_ptr()
+        pa.master = ex.store.master.data_ptr()
         pa.arena = ex.arena.data_ptr()
         if training and ex.routes_ok:
             pa.pack_mode = 0          # the optimizer writes the packs itself (pack routes)
         if not self.pro_free:
-            self.launches.append(("prologue", lambda s, a=pa: K.prologue(a, ex.pack_table, s)))
+            self._add("prologue", lambda s, a=pa: K.prologue(a, ex.pack_table, s), pro=pa)
+        return stack, sb
 
-        # ---------------- forward convs
+    def _build_conv_fwd(self, stack):
+        """The forward convs: the layer-fused stack launch, or one launch per layer."""
+        ex, K = self.ex, self.ex.K
         if stack is not None:
             self.stack_args = stack
-            self.launches.append(("conv_stack_fwd", lambda s, a=stack: K.conv_stack_fwd(a, s)))
-        x_buf, H, W, Cs = self.xb, ex.in_H, ex.in_W, ex.in_Cs
+            self._add("conv_stack_fwd", lambda s, a=stack: K.conv_stack_fwd(a, s), stack=stack)
+            return
+        x_buf = self.xb
         for g, cs in zip(ex.convs, ex.plan.convs):
-            if stack is not None:
-                break
             a = K.ConvMMArgs()
             a.x = x_buf.data_ptr()
-            a.B, a.H, a.W, a.Cs_in = bs, g.H, g.W, g.Cs_in
+            a.B, a.H, a.W, a.Cs_in = self.bs, g.H, g.W, g.Cs_in
             a.Ho, a.Wo = g.Ho, g.Wo
             a.KH, a.KW, a.stride, a.pad_t, a.pad_l, a.in_dil = g.KH, g.KW, g.stride, g.pad_t, g.pad_l, 1
             a.KS = g.KS
             a.wpk = ex.arena.data_ptr() + 2 * g.pack_fwd
             a.NT = g.NT
-            a.bias = store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
+            a.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
             a.N = g.Cout
             a.mode = 0
             a.relu, a.pool = int(g.relu), int(g.pool)
@@ -738,14 +698,16 @@ class BatchPlan(GeometryMixin):
             a.Cs_out, a.Hp, a.Wp = g.Cs_out, g.Hp, g.Wp
             if g.pool:
                 a.code = self.conv_code[g.i].data_ptr()
-            if training and g.rate > 0:
-                a.drop_thr = keep_threshold(g.rate)
-                a.drop_scale = 1.0 / (1.0 - g.rate)
-            a.seed, a.stream_id, a.st = ex.seed, g.stream, st_ptr
-            self.launches.append(("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool)))
+            if self.training and g.rate > 0:
+                a.drop_thr, a.drop_scale = dropout_pair(g.rate)
+            a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
+            self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool), ca=a)
             x_buf = self.conv_out[g.i]
 
-        # ---------------- forward denses
+    def _build_dense_fwd(self, sb):
+        """The hidden dense layers: split-K GEMM + epilogue each.  Returns the last layer's
+        epilogue args when the head launch runs that epilogue itself, else None."""
+        ex, K, bs = self.ex, self.ex.K, self.bs
         head_epi = None
         for g, ds in zip(ex.denses, ex.plan.denses):
             splits, kps = self.dense_splits[g.j]
@@ -756,20 +718,18 @@ class BatchPlan(GeometryMixin):
             a.NT, a.KS = g.NT, g.KS
             a.splits, a.ks_per_split = splits, kps
             a.part = self.dense_part[g.j].data_ptr()
-            if self.pro_free and g.j == 0 and training:
+            if self.pro_free and g.j == 0 and self.training:
                 a.book, a.sb = 1, sb      # this step's bookkeeping (the stack read t + 1)
-            self.launches.append(("dense_fwd%d" % g.j, lambda s, a=a: K.dense_fwd(a, s)))
-            last_fwd = (len(self.launches) - 1, a, g)
+            self._add("dense_fwd%d" % g.j, lambda s, a=a: K.dense_fwd(a, s), da=a)
             e = K.DenseEpiArgs()
             e.part = a.part
             e.splits, e.M, e.N, e.Ns, e.ldp = splits, bs, g.N, g.Ns, g.NT * 16
-            e.bias = store.view(ds.dense, "bias").data_ptr() if ds.dense.use_bias else 0
+            e.bias = ex.store.view(ds.dense, "bias").data_ptr() if ds.dense.use_bias else 0
             e.relu = int(g.relu)
             e.out = self.dense_out[g.j].data_ptr()
-            if training and g.rate > 0:
-                e.drop_thr = keep_threshold(g.rate)
-                e.drop_scale = 1.0 / (1.0 - g.rate)
-            e.seed, e.stream_id, e.st = ex.seed, g.stream, st_ptr
+            if self.training and g.rate > 0:
+                e.drop_thr, e.drop_scale = dropout_pair(g.rate)
+            e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
                     and tune("fuse_head", True)):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
@@ -777,14 +737,16 @@ class BatchPlan(GeometryMixin):
                 head_epi = e
                 self.head_blocks = cdiv(bs, K.head_rows_per_block(True))
             else:
-                self.launches.append(("dense_epi%d" % g.j, lambda s, e=e: K.dense_epi(e, s)))
+                self._add("dense_epi%d" % g.j, lambda s, e=e: K.dense_epi(e, s), epi=e)
+        return head_epi
 
-        # ---------------- head
+    def _build_head(self, head_epi):
+        ex, K, store, training = self.ex, self.ex.K, self.ex.store, self.training
         hd = ex.plan.head
         h = K.HeadArgs()
         src = ex.head_src
         h.h = self._src_buf(src).data_ptr()
-        h.M, h.K, h.Ks, h.N = bs, hd.K, src.width, hd.N
+        h.M, h.K, h.Ks, h.N = self.bs, hd.K, src.width, hd.N
         h.flat_C, h.flat_Cs = src.C, src.Cs
         h.w = store.view(hd.dense, "kernel").data_ptr()
         h.bias = store.view(hd.dense, "bias").data_ptr() if hd.dense.use_bias else 0
@@ -800,8 +762,8 @@ class BatchPlan(GeometryMixin):
             h.epi = head_epi
         h.training = int(training)
         h.generic = int(tune("head_generic", False))
-        h.inv_bs = 1.0 / bs
-        h.st = st_ptr
+        h.inv_bs = 1.0 / self.bs
+        h.st = ex.state.data_ptr()
         if self.probs is not None:
             h.probs = self.probs.data_ptr()
         if training:
@@ -813,27 +775,30 @@ class BatchPlan(GeometryMixin):
         # (a fused dense layer + head launch -- 16-wave K-slice tiles, the last arriving workgroup
         # of each row group running the head -- measured 15.6 us against 13.3 us for the split-K
         # dense launch + this head launch at RPV B=128, and was removed in round 5)
-        self.launches.append(("head", lambda s, a=h: K.head(a, s)))
-        if not training:
-            return
+        self._add("head", lambda s, a=h: K.head(a, s), head=h)
 
-        # ---------------- backward
-        self.red_groups = []       # (lo, hi, [desc tuples]) in backward order
-        self.pack_readers = []     # (launch name, param lo, hi): backward launches reading a layer's pack
-        self.red_ready = []        # launch count after which each group's partial slabs are final
+    # ---------------------------------------------------------------- step program: backward
+    def _add_group(self, spec, descs, bias_spec=None):
+        """A layer's reduction group over its kernel (and bias) span, its partial slabs final
+        after the launches appended so far."""
+        lo, hi = spec.offset, spec.offset + spec.numel
+        if bias_spec is not None:
+            hi = max(hi, bias_spec.offset + bias_spec.numel)
+        self.red_groups.append(RedGroup(lo, hi, descs, len(self.launches)))
+        return lo, hi
+
+    def _begin_backward(self):
+        """The head's reduction group (its slabs are final after the head launch) and the
+        fused-dense-optimizer switches."""
+        ex, store, hd = self.ex, self.ex.store, self.ex.plan.head
         hw = store.spec(hd.dense, "kernel")
-        descs = [(self.head_wslab.data_ptr(), hd.K * hd.N, self.head_blocks, hd.N, hw.offset, hw.numel,
-                  RED_BIAS, 0, 0, 0, 0, 0)]
-        lo, hi = hw.offset, hw.offset + hw.numel
-        if hd.dense.use_bias:
-            hb = store.spec(hd.dense, "bias")
-            descs.append((self.head_bslab.data_ptr(), hd.N, self.head_blocks, hd.N, hb.offset, hb.numel,
-                          RED_BIAS, 0, 0, 0, 0, 0))
-            hi = max(hi, hb.offset + hb.numel)
-        self.red_groups.append((lo, hi, descs))
-        self._add_group_reduce()
-        self.wgrad_slabs = []
-        self.dense_fused_opt = []          # (WgradArgs, params) updated inside dense_wgrad
+        hb = store.spec(hd.dense, "bias") if hd.dense.use_bias else None
+        descs = [RedDesc(self.head_wslab.data_ptr(), hd.K * hd.N, self.head_blocks, hd.N, hw.offset, hw.numel,
+                         RED_BIAS)]
+        if hb is not None:
+            descs.append(RedDesc(self.head_bslab.data_ptr(), hd.N, self.head_blocks, hd.N, hb.offset, hb.numel,
+                                 RED_BIAS))
+        self._add_group(hw, descs, hb)
         # opt-in: the dense layer's optimizer update inside its (one-split) wgrad kernel.  Measured
         # slower on RPV at batch 128: the 128 wgrad workgroups move the layer's 14 MB of optimizer
         # state at per-CU bandwidth (wgrad 6.1 -> 9.7 us) while the end-of-step reduction, which
@@ -848,359 +813,391 @@ class BatchPlan(GeometryMixin):
                              and ex.opt.kind not in STANDALONE_KINDS)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
 
-        for g, ds in reversed(list(zip(ex.denses, ex.plan.denses))):
-            xin = self._src_buf(g.src)
-            sp = store.spec(ds.dense, "kernel")
-            # Unpadded flatten source and N % 16 == 0: the single-split slab IS the Keras
-            # (in, out) layout, so the wgrad kernel writes the gradient buffer directly and
-            # the slab round trip disappears (the dense kernel is most of the model's bytes).
-            direct = (g.src.C == g.src.Cs and g.N % 16 == 0 and g.src.width % 16 == 0
-                      and g.src.width * g.N * 4 > (16 << 20))     # small layers keep split-K slabs
-            direct_ptr = (store.grad.data_ptr() + 4 * sp.offset) if direct else None
-            # dense_bwd.hip kernels (per-wave pipelined wgrad, vectorised dX epilogue) where the
-            # 8-element alignment they assume holds; the generic wgrad / split-K path otherwise
-            bwd2 = tune("dense_bwd2", True) and g.src.width % 8 == 0 and g.Ns % 8 == 0
+    def _dense_wgrad(self, g, ds, direct):
+        """A dense layer's weight gradient: (Wgrad, launch callable, whether the optimizer
+        update is fused into it, whether the dense_bwd.hip kernels run it)."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        xin = self._src_buf(g.src)
+        sp = store.spec(ds.dense, "kernel")
+        direct_ptr = (store.grad.data_ptr() + 4 * sp.offset) if direct else None
+        # dense_bwd.hip kernels (per-wave pipelined wgrad, vectorised dX epilogue) where the
+        # 8-element alignment they assume holds; the generic wgrad / split-K path otherwise
+        bwd2 = tune("dense_bwd2", True) and g.src.width % 8 == 0 and g.Ns % 8 == 0
+        if not bwd2:
+            w = self._wgrad_args(xin, g.src.width, self.dense_dh[g.j], g.Ns, g.N, ds.dense.use_bias, direct_ptr)
+            return w, (lambda s, a=w.a, c=w.cfg: K.wgrad(a, *c, s)), False, False
+        w = self._dense_wgrad_args(xin, g.src.width, self.dense_dh[g.j], g.Ns, g.N, ds.dense.use_bias, direct_ptr)
+        wa, (kg, ntt) = w.a, w.tiles
+        # one split + identity layout: the kernel's fixed-order sum IS the Keras
+        # gradient -- write it in place and apply the optimizer there (single GPU,
+        # fused-optimizer step), so the layer skips the end-of-step reduction
+        fused_opt = (self.dense_opt_ok and (self.dense_opt_all or direct)
+                     and w.splits == 1 and g.src.C == g.src.Cs and g.N % 16 == 0 and sp.offset % 4 == 0)
+        # with optimizer-written packs the kernel must write this layer's packs itself
+        pk_ok = (kg == 2 and g.src.width % 32 == 0 and g.N % 32 == 0
+                 and (not g.KSb or ntt % 2 == 0))
+        if fused_opt and ex.routes_ok and not pk_ok:
             fused_opt = False
-            if bwd2:
-                wa, cfg, slab, bslab = self._dense_wgrad_args(xin, g.src.width, self.dense_dh[g.j], g.Ns, g.N, bs,
-                                                              ds.dense.use_bias, direct_ptr)
-                # one split + identity layout: the kernel's fixed-order sum IS the Keras
-                # gradient -- write it in place and apply the optimizer there (single GPU,
-                # fused-optimizer step), so the layer skips the end-of-step reduction
-                fused_opt = (self.dense_opt_ok and (self.dense_opt_all or direct)
-                             and cfg[2] == 1 and g.src.C == g.src.Cs and g.N % 16 == 0 and sp.offset % 4 == 0)
-                # with optimizer-written packs the kernel must write this layer's packs itself
-                pk_ok = (cfg[0] == 2 and g.src.width % 32 == 0 and g.N % 32 == 0
-                         and (not g.KSb or cfg[1] % 2 == 0))
-                if fused_opt and ex.routes_ok and not pk_ok:
-                    fused_opt = False
-                if fused_opt:
-                    grad = store.grad.data_ptr()
-                    wa.slab = grad + 4 * sp.offset
-                    wa.opt = ex._optim_args(False, defer_pack=True)
-                    wa.opt_w = sp.offset
-                    # the gradient the update consumed is not stored (134 MB of writes for the
-                    # legacy Dense(512): 1.107 -> 1.097 ms/step, with dw_order 1.101 -> 1.086,
-                    # profiles/r6_dense_wgrad_ab.txt) -- this layer's gradient is then not
-                    # readable through the store (store.view(..., grad=True)); opt_nograd=0 keeps it
-                    wa.opt_nograd = int(tune("opt_nograd", True))
-                    if ex.routes_ok:
-                        wa.pk_fwd, wa.pk_NT = g.pack_fwd, g.NT
-                        wa.pk_bwd, wa.pk_NTb = (g.pack_bwd, g.NTb) if g.KSb else (-1, 0)
-                    if ds.dense.use_bias:
-                        wa.bslab = grad + 4 * store.spec(ds.dense, "bias").offset
-                        wa.opt_b = store.spec(ds.dense, "bias").offset
-                # grid order 1: the n groups of one feature group consecutive (whole rows of the
-                # weight / optimizer-state arrays per resident wave of workgroups; legacy -5 us)
-                dw_order = int(tune("dw_order", 1))
-                dw_late = bool(tune("dw_late", True))     # 4 waves / SIMD: legacy 1.070 -> 1.059 ms
-                wl = lambda s, a=wa, c=cfg, o=dw_order, l=dw_late: K.dense_wgrad(a, c[0], c[1], c[2], s, o, l)
-            else:
-                wa, cfg, slab, bslab = self._wgrad_args(
-                    xin, 1, 1, g.src.width, 1, 1, 1, 1, 1, 0, 0, self.dense_dh[g.j], g.Ns, g.N, bs,
-                    ds.dense.use_bias, direct=direct_ptr)
-                wl = lambda s, a=wa, c=cfg: K.wgrad(a, c[0], c[1], c[2], s)
-            self.launches.append(("wgrad_dense%d" % g.j, wl, "side"))
-            w_at = len(self.launches) - 1
-            S, ld = cfg[2], g.NT * 16
-            descs = [] if (direct or fused_opt) else [(slab.data_ptr(), wa.Ktiles * 16 * ld, S, ld, sp.offset,
-                                                        sp.numel, RED_FLATW, 0, 0, g.src.C, g.N, g.src.Cs)]
-            lo, hi = sp.offset, sp.offset + sp.numel
+        if fused_opt:
+            grad = store.grad.data_ptr()
+            wa.slab = grad + 4 * sp.offset
+            wa.opt = ex._optim_args(False, defer_pack=True)
+            wa.opt_w = sp.offset
+            # the gradient the update consumed is not stored (134 MB of writes for the
+            # legacy Dense(512): 1.107 -> 1.097 ms/step, with dw_order 1.101 -> 1.086,
+            # profiles/r6_dense_wgrad_ab.txt) -- this layer's gradient is then not
+            # readable through the store (store.view(..., grad=True)); opt_nograd=0 keeps it
+            wa.opt_nograd = int(tune("opt_nograd", True))
+            if ex.routes_ok:
+                wa.pk_fwd, wa.pk_NT = g.pack_fwd, g.NT
+                wa.pk_bwd, wa.pk_NTb = (g.pack_bwd, g.NTb) if g.KSb else (-1, 0)
             if ds.dense.use_bias:
-                bp_ = store.spec(ds.dense, "bias")
-                if not fused_opt:
-                    descs.append((bslab.data_ptr(), ld, S, ld, bp_.offset, bp_.numel, RED_BIAS, 0, 0, 0, 0, 0))
-                hi = max(hi, bp_.offset + bp_.numel)
-            if fused_opt:
-                self.dense_fused_opt.append((wa, hi - lo))
-            self.red_groups.append((lo, hi, descs))
-            self._add_group_reduce()
-            if g.KSb:
-                a = K.DenseFwdArgs()
-                a.x = self.dense_dh[g.j].data_ptr()
-                a.M, a.Ks = bs, g.Ns
-                a.wpk = ex.arena.data_ptr() + 2 * g.pack_bwd
-                a.NT, a.KS = g.NTb, g.KSb
-                a.splits, a.ks_per_split = 1, g.KSb
-                a.mode = 1
-                a.st = st_ptr
-                a.bt = self._bt_for(g.src)
-                dname = "dense_dx%d" % g.j
-                ntc = self._dense_dx_ntc(a) if (bwd2 and a.bt.pCs % 8 == 0 and a.Ks % 8 == 0
-                                               and not K.dense_big(a.NT, a.KS)) else 0
-                if fused_opt:
-                    # the wgrad's fused optimizer rewrites this layer's backward pack: its dX (that
-                    # pack's reader) runs first, as a launch of its own on the same stream -- never
-                    # in one launch with it (dense_bwd_pair: dX workgroups would read a pack the
-                    # wgrad workgroups are rewriting)
-                    fn = ((lambda s, a=a, n=ntc: K.dense_dx(a, n, s)) if ntc else (lambda s, a=a: K.dense_fwd(a, s)))
-                    self.launches[w_at] = (self.launches[w_at][0], self.launches[w_at][1], "main")
-                    self.launches.insert(w_at, (dname, fn, "main"))
-                    self.red_ready[-1] += 1
-                elif tune("dual_dense", True):
-                    # one launch for the dense wgrad and dX (independent GEMMs over dH), in the
-                    # wgrad's slot (its slabs are final after it)
-                    dname = "dense_bwd%d" % g.j
-                    if ntc:
-                        fn = lambda s, a=a, w=wa, c=cfg, n=ntc: K.dense_bwd_pair(w, c[0], c[1], c[2], a, n, s)
-                    elif bwd2:
-                        fn = lambda s, a=a, w=wa, c=cfg: (K.dense_wgrad(w, c[0], c[1], c[2], s), K.dense_fwd(a, s))
-                    else:
-                        fn = lambda s, a=a, w=wa, c=cfg: self._dense_dual(w, c, a, s)
-                    self.launches[w_at] = (dname, fn, "main")
-                elif ntc:
-                    self.launches.append((dname, lambda s, a=a, n=ntc: K.dense_dx(a, n, s)))
-                else:
-                    self.launches.append((dname, lambda s, a=a: K.dense_fwd(a, s)))
-                self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
+                wa.bslab = grad + 4 * store.spec(ds.dense, "bias").offset
+                wa.opt_b = store.spec(ds.dense, "bias").offset
+        # grid order 1: the n groups of one feature group consecutive (whole rows of the
+        # weight / optimizer-state arrays per resident wave of workgroups; legacy -5 us)
+        dw_order = int(tune("dw_order", 1))
+        dw_late = bool(tune("dw_late", True))     # 4 waves / SIMD: legacy 1.070 -> 1.059 ms
+        wl = lambda s, a=wa, c=w.cfg, o=dw_order, l=dw_late: K.dense_wgrad(a, *c, s, o, l)
+        return w, wl, fused_opt, True
 
-        for g, cs in reversed(list(zip(ex.convs, ex.plan.convs))):
-            xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
-            if self._wide(g.Cs_in, g.KS, g.NT):
-                wa, cfg, slab, bslab = self._wgrad_tile_args(xin, g, bs, cs.conv.use_bias)
-                self.launches.append(("wgrad_conv%d" % g.i, lambda s, a=wa, c=cfg: K.wgrad_tile(a, c[0], s),
-                                      "side"))
+    def _dense_dx(self, g, bwd2):
+        """A dense layer's dX GEMM through its backward pack: (DenseFwdArgs, n-tiles per wave
+        of dense_dx_kernel or 0 for the split-K dense kernel, launch callable)."""
+        ex, K = self.ex, self.ex.K
+        a = K.DenseFwdArgs()
+        a.x = self.dense_dh[g.j].data_ptr()
+        a.M, a.Ks = self.bs, g.Ns
+        a.wpk = ex.arena.data_ptr() + 2 * g.pack_bwd
+        a.NT, a.KS = g.NTb, g.KSb
+        a.splits, a.ks_per_split = 1, g.KSb
+        a.mode = 1
+        a.st = ex.state.data_ptr()
+        a.bt = self._bt_for(g.src)
+        ntc = self._dense_dx_ntc(a) if (bwd2 and a.bt.pCs % 8 == 0 and a.Ks % 8 == 0
+                                       and not K.dense_big(a.NT, a.KS)) else 0
+        return a, ntc, ((lambda s, a=a, n=ntc: K.dense_dx(a, n, s)) if ntc else (lambda s, a=a: K.dense_fwd(a, s)))
+
+    def _build_dense_bwd(self, g, ds):
+        """One dense layer's backward: its wgrad and (unless it is the first layer) its dX, as
+        one launch or two, and the layer's reduction group."""
+        K, store = self.ex.K, self.ex.store
+        sp = store.spec(ds.dense, "kernel")
+        bsp = store.spec(ds.dense, "bias") if ds.dense.use_bias else None
+        # Unpadded flatten source and N % 16 == 0: the single-split slab IS the Keras
+        # (in, out) layout, so the wgrad kernel writes the gradient buffer directly and
+        # the slab round trip disappears (the dense kernel is most of the model's bytes).
+        direct = (g.src.C == g.src.Cs and g.N % 16 == 0 and g.src.width % 16 == 0
+                  and g.src.width * g.N * 4 > (16 << 20))     # small layers keep split-K slabs
+        w, wl, fused_opt, bwd2 = self._dense_wgrad(g, ds, direct)
+        wa, cfg = w.a, w.cfg
+        wname, dname = "wgrad_dense%d" % g.j, "dense_dx%d" % g.j
+        da, ntc, dl = self._dense_dx(g, bwd2) if g.KSb else (None, 0, None)
+        dx_first = da is not None and fused_opt
+        dual = da is not None and not fused_opt and tune("dual_dense", True)
+        if dx_first:
+            # the wgrad's fused optimizer rewrites this layer's backward pack: its dX (that
+            # pack's reader) runs first, as a launch of its own on the same stream -- never
+            # in one launch with it (dense_bwd_pair: dX workgroups would read a pack the
+            # wgrad workgroups are rewriting)
+            self._add(dname, dl, da=da)
+        if dual:
+            # one launch for the dense wgrad and dX (independent GEMMs over dH); the layer's
+            # slabs are final after it
+            dname = "dense_bwd%d" % g.j
+            if ntc:
+                fn = lambda s, a=da, w=wa, c=cfg, n=ntc: K.dense_bwd_pair(w, *c, a, n, s)
+            elif bwd2:
+                fn = lambda s, a=da, w=wa, c=cfg: (K.dense_wgrad(w, *c, s), K.dense_fwd(a, s))
             else:
-                wa, cfg, slab, bslab = self._wgrad_halo_args(xin, g, bs, cs.conv.use_bias)
-                if g.i == 0 and self.pro_free:      # the images the stack read from the dataset
-                    wa.xidx, wa.xst = self.srcidx.data_ptr(), st_ptr
-                self.launches.append(("wgrad_conv%d" % g.i,
-                                      lambda s, a=wa, c=cfg: K.wgrad_halo(a, c[0], c[1], c[2], s), "side"))
-            w_at = len(self.launches) - 1
-            sp = store.spec(cs.conv, "kernel")
-            S, ld = cfg[2], g.NT * 16
-            descs = [(slab.data_ptr(), wa.Ktiles * 16 * ld, S, ld, sp.offset, sp.numel, RED_CONVW,
-                      g.KH, g.KW, g.Cin, g.Cout, g.Cs_in)]
-            lo, hi = sp.offset, sp.offset + sp.numel
-            if cs.conv.use_bias:
-                bp_ = store.spec(cs.conv, "bias")
-                descs.append((bslab.data_ptr(), ld, S, ld, bp_.offset, bp_.numel, RED_BIAS, 0, 0, 0, 0, 0))
-                hi = max(hi, bp_.offset + bp_.numel)
-            self.red_groups.append((lo, hi, descs))
-            self._add_group_reduce()
-            if g.i > 0:
-                prev = ex.convs[g.i - 1]
-                a = K.ConvMMArgs()
-                a.x = self.conv_dy[g.i].data_ptr()
-                a.B, a.H, a.W, a.Cs_in = bs, g.Ho, g.Wo, g.Cs_out
-                if g.pool:      # dY rebuilt on load from pooled dP + argmax codes
-                    a.in_code = self.conv_code[g.i].data_ptr()
-                    a.in_pH, a.in_pW = g.Hp, g.Wp
-                a.Ho, a.Wo = g.H, g.W            # == prev stage output grid
-                a.KH, a.KW, a.stride = g.KH, g.KW, 1
-                a.pad_t, a.pad_l, a.in_dil = g.KH - 1 - g.pad_t, g.KW - 1 - g.pad_l, g.stride
-                a.KS = g.KSd
-                a.wpk = ex.arena.data_ptr() + 2 * g.pack_dgrad
-                a.NT = g.NTd
-                a.mode, a.flat_out = 1, 0
-                a.st = st_ptr
-                a.bt = self._bt_for(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
-                a.tm = tune("dgrad_tm%d" % g.i, 0)      # co-scheduled dgrad m-tiles per wave per pass
-                a.dbg = tune("dgrad_dbg", 0)            # A/B switches (ConvMMArgs::dbg; exact ones only)
-                dname = "dgrad_conv%d" % g.i
-                dual = (tune("dual_halo", True)
-                        and not self._wide(g.Cs_in, g.KS, g.NT) and not self._wide(a.Cs_in, a.KS, g.NTd))
-                if dual:
-                    # one launch for the layer's wgrad and dgrad (independent GEMMs sharing dY):
-                    # replaces the wgrad launch in place (its slabs are final after it)
-                    ntc = self._halo_cfg(a, g.NTd, False, dual=True)
-                    dname = "wgrad_dgrad_conv%d" % g.i
-                    self.launches[w_at] = (dname, lambda s, a=a, n=ntc, w=wa, c=cfg, nm=dname: self._dual(a, n, w, c, s, nm),
-                                           "main")
-                else:
-                    self.launches.append((dname, self._conv_launch(a, g.NTd, False)))
-                self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
-        self._build_reduce()
+                fn = lambda s, a=da, w=wa, c=cfg: self._dense_dual(w, c, a, s)
+            self._add(dname, fn, wa=wa, cfg=cfg, da=da)
+        else:
+            self._add(wname, wl, "main" if dx_first else "side", wa=wa, cfg=cfg)
+        ld = g.NT * 16
+        descs = [] if (direct or fused_opt) else [RedDesc(w.slab.data_ptr(), wa.Ktiles * 16 * ld, w.splits, ld,
+                                                          sp.offset, sp.numel, RED_FLATW, 0, 0, g.src.C, g.N,
+                                                          g.src.Cs)]
+        if bsp is not None and not fused_opt:
+            descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
+        lo, hi = self._add_group(sp, descs, bsp)
+        if fused_opt:
+            self.dense_fused_opt.append((wa, hi - lo))
+        if da is not None and not (dx_first or dual):
+            self._add(dname, dl, da=da)
+        if da is not None:
+            self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
 
-    def _add_group_reduce(self):
-        """Record where the group just appended has its partial slabs final."""
-        self.red_ready.append(len(self.launches))
+    def _dgrad_args(self, g):
+        """ConvMMArgs of conv layer g's dgrad (a stride-1 conv over the input-dilated dY with
+        the flipped taps of its backward pack), written through the previous stage's backward."""
+        ex = self.ex
+        prev = ex.convs[g.i - 1]
+        a = ex.K.ConvMMArgs()
+        a.x = self.conv_dy[g.i].data_ptr()
+        a.B, a.H, a.W, a.Cs_in = self.bs, g.Ho, g.Wo, g.Cs_out
+        if g.pool:      # dY rebuilt on load from pooled dP + argmax codes
+            a.in_code = self.conv_code[g.i].data_ptr()
+            a.in_pH, a.in_pW = g.Hp, g.Wp
+        a.Ho, a.Wo = g.H, g.W            # == prev stage output grid
+        a.KH, a.KW, a.stride = g.KH, g.KW, 1
+        a.pad_t, a.pad_l, a.in_dil = g.KH - 1 - g.pad_t, g.KW - 1 - g.pad_l, g.stride
+        a.KS = g.KSd
+        a.wpk = ex.arena.data_ptr() + 2 * g.pack_dgrad
+        a.NT = g.NTd
+        a.mode, a.flat_out = 1, 0
+        a.st = ex.state.data_ptr()
+        a.bt = self._bt_for(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
+        a.tm = tune("dgrad_tm%d" % g.i, 0)      # co-scheduled dgrad m-tiles per wave per pass
+        a.dbg = tune("dgrad_dbg", 0)            # A/B switches (ConvMMArgs::dbg; exact ones only)
+        return a
 
+    def _build_conv_bwd(self, g, cs):
+        """One conv layer's backward: its wgrad and (unless it is the first layer) its dgrad --
+        one dual launch where both take the halo kernels -- and the layer's reduction group."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
+        wide = self._wide(g.Cs_in, g.KS, g.NT)
+        if wide:
+            w = self._wgrad_tile_args(xin, g, cs.conv.use_bias)
+            wl = lambda s, a=w.a, c=w.cfg: K.wgrad_tile(a, c[0], s)
+        else:
+            w = self._wgrad_halo_args(xin, g, cs.conv.use_bias)
+            if g.i == 0 and self.pro_free:      # the images the stack read from the dataset
+                w.a.xidx, w.a.xst = self.srcidx.data_ptr(), ex.state.data_ptr()
+            wl = lambda s, a=w.a, c=w.cfg: K.wgrad_halo(a, *c, s)
+        ca = self._dgrad_args(g) if g.i > 0 else None
+        dual = (ca is not None and tune("dual_halo", True)
+                and not wide and not self._wide(ca.Cs_in, ca.KS, g.NTd))
+        dname = "dgrad_conv%d" % g.i
+        if dual:
+            # one launch for the layer's wgrad and dgrad (independent GEMMs sharing dY); the
+            # layer's slabs are final after it
+            ntc = self._halo_cfg(ca, g.NTd, False, dual=True)
+            dname = "wgrad_dgrad_conv%d" % g.i
+            fn = lambda s, a=ca, n=ntc, w=w.a, c=w.cfg, nm=dname: self._dual(a, n, w, c, s, nm)
+            self._add(dname, fn, "main", ca=ca, ntc=ntc, wa=w.a, cfg=w.cfg)
+        else:
+            self._add("wgrad_conv%d" % g.i, wl, "side", wa=w.a, cfg=w.cfg)
+        sp = store.spec(cs.conv, "kernel")
+        bsp = store.spec(cs.conv, "bias") if cs.conv.use_bias else None
+        ld = g.NT * 16
+        descs = [RedDesc(w.slab.data_ptr(), w.a.Ktiles * 16 * ld, w.splits, ld, sp.offset, sp.numel, RED_CONVW,
+                         g.KH, g.KW, g.Cin, g.Cout, g.Cs_in)]
+        if bsp is not None:
+            descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
+        self._add_group(sp, descs, bsp)
+        if ca is not None:
+            if not dual:
+                self._add(dname, self._conv_launch(ca, g.NTd, False), ca=ca)
+            self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
+
+    # ---------------------------------------------------------------- step program: reductions
     def _build_reduce(self):
         """Merge per-layer slab groups (backward order) into buckets -- the DP reducer's
         buckets, or the same 1 MiB bucketing without DP (dense layer first, then convs) --
         and insert one reduction launch per bucket right after its last group's wgrad, on
         the side stream, so the dense bucket's reduction overlaps the conv backward."""
-        ex, K = self.ex, self.ex.K
-        groups = [(lo, hi) for lo, hi, _ in self.red_groups]
-        reducer = ex.reducer
-        dp_early = []
-        self.early_push, self.pushed, self.early_xchg, self.exchanged = {}, None, {}, False
-        self.bucket_xchg, self.xchg_end, self.xchg_fin = {}, None, None
-        if reducer is not None:
-            bucket_groups = reducer.configure(groups)
-            # one bucket at the end of the backward (the adaptive plan for gradients <= 16 MB):
-            # the groups final before the first dual launch (head, dense -- the single-GPU
-            # step's early bucket) are REDUCED early there (grad_only: no update), so the
-            # end-of-backward reduction ahead of the all-reduce only has the conv layers' slabs
-            # left (the update stays behind the all-reduce)
-            # one rank (the N = 1 data-parallel step): nothing to exchange -- the early groups
-            # are reduced AND updated in that launch, as on a single GPU (xchg_p1: keep the
-            # exchange structure, to measure its fixed cost)
-            solo = reducer.size == 1 and getattr(reducer, "xgmi", None) is not None and not tune("xchg_p1", False)
-            if len(bucket_groups) == 1 and self.comm_in_graph and tune("dp_early", True):
-                dp_early = self._early_groups(grad_only=not solo)
-                if solo and self.early_red:
-                    self.pushed = next(iter(self.early_red.values()))[1]
-                    self.exchanged = True
-                # producer push (xGMI plane): the early groups' reduced gradient goes straight to
-                # its owners' inboxes from the launch that reduces it, inside the backward, and
-                # the fused all-reduce kernel skips those elements in its phase 1
-                # ... and (exchange) the NEXT dual launch finishes that range's all-reduce and
-                # applies its update in extra workgroups of its own, so the fused kernel after
-                # the backward is left with the conv layers only
-                if tune("xgmi_push", True) and not solo:
-                    # every early table would start at block-flag slot 0 (fbase) and the pushed /
-                    # exchanged range is ONE span: _early_groups caps them at one dual launch
-                    assert len(self.early_red) <= 1, "exchange: one early table per step (flag slots, pushed range)"
-                    for nm, (tab_, (elo, ehi), go) in self.early_red.items():
-                        if not go:
-                            continue
-                        # (xchg_at=end: the exchange as a launch of its own after the end-of-
-                        # backward reduction instead of extra workgroups of the next dual launch)
-                        at_end = tune("xchg_at", "dual") == "end"
-                        nxt = (("end" if at_end else self._xchg_launch(nm, elo, ehi))
-                               if tune("xgmi_xchg", True) else None)
-                        # split exchange (default): the owner half (wait for the senders, sum,
-                        # push the sums back: mode 4) in extra workgroups of the next dual launch,
-                        # covering only the table blocks this rank owns part of (none at one
-                        # rank), and the finish half (wait for the other owners, update: mode 5)
-                        # beside the end-of-backward table in ONE launch -- every wait is on a
-                        # flag raised in an EARLIER launch, and no conv-sized workgroup holds a
-                        # CU slot for the update (xchg_split=0: both halves in the dual launch)
-                        if nxt and not at_end and tune("xchg_split", True):
-                            trip = reducer.exchange_args(elo, ehi, tab_.nblocks, table=tab_)
-                            if trip is not None:
-                                self.early_push[nm] = trip[0]
-                                if trip[1].b_hi > trip[1].b_lo:
-                                    self.early_xchg[nxt] = (tab_, trip[1])
-                                self.xchg_fin = (tab_, trip[2])
-                                self.pushed, self.exchanged = (elo, ehi), True
-                                continue
-                        pair = reducer.exchange_args(elo, ehi, tab_.nblocks) if nxt else None
-                        if pair is not None:
-                            self.early_push[nm] = pair[0]
-                            if at_end:
-                                self.xchg_end = (tab_, pair[1])
-                            else:
-                                self.early_xchg[nxt] = (tab_, pair[1])
-                            self.pushed, self.exchanged = (elo, ehi), True
-                            continue
-                        xp = reducer.push_args(elo, ehi)
-                        if xp is not None:
-                            self.early_push[nm], self.pushed = xp, (elo, ehi)
+        ex, reducer = self.ex, self.ex.reducer
+        if reducer is None:
+            bucket_groups, dp_early = self._assign_buckets(), []
         else:
-            # single stream, no all-reduce to overlap: ONE reduction launch at the end of the
-            # backward (each launch boundary costs ~5 us here), if the descriptors fit a table
-            ndesc = sum(len(d) for _, _, d in self.red_groups)
-            one = ndesc <= tune("red_desc_max", 16)       # (RedTable capacity, MAX_RED)
-            limit = 1 << 62 if one else int(os.environ.get("INTML_BUCKET_BYTES", 1 << 20))
-            # ... with the optimizer fused into it when its table covers every parameter
-            covered = sum(d[5] for _, _, ds in self.red_groups for d in ds)
-            covered += sum(n for _, n in self.dense_fused_opt)
-            self.optim_fused = one and covered == ex.store.numel and tune("fuse_optim", True)
-            if not self.optim_fused:
-                # the step ends with a full optimizer launch after all: the dense layers keep
-                # writing their gradient in place, but leave the update -- and the bf16 pack
-                # writes that go with it -- to it, so they also store the gradient it reads
-                for wa, _ in self.dense_fused_opt:
-                    wa.opt_w, wa.opt_b = -1, -1
-                    wa.pk_fwd, wa.pk_bwd = -1, -1
-                    wa.opt_nograd = 0
-                self.dense_fused_opt = []
-            early = self._early_groups() if self.optim_fused else []
-            bucket_groups, cur, nb = [], [], 0
-            for gi, (lo, hi) in enumerate(groups):
-                if gi in early:
-                    continue
-                cur.append(gi)
-                nb += (hi - lo) * 4
-                if nb >= limit:
-                    bucket_groups.append(cur)
-                    cur, nb = [], 0
-            if cur:
-                bucket_groups.append(cur)
-        self.bucket_tables = []
+            bucket_groups, dp_early = self._assign_buckets_dp(reducer)
         inserts = []                       # (launch index to insert after, bucket)
         for k, bg in enumerate(bucket_groups):
-            tab = K.RedTable()
+            tab = ex.K.RedTable()
             # longest reductions (most slabs) first: their workgroups dispatch first and their
             # memory round trips overlap the many short ones instead of trailing the launch
-            for d in sorted((d for i in bg if i not in dp_early for d in self.red_groups[i][2]),
-                            key=lambda d: -d[2]):
+            for d in sorted((d for i in bg if i not in dp_early for d in self.red_groups[i].descs),
+                            key=lambda d: -d.S):
                 tab.add(*d)
-            lo = min(self.red_groups[i][0] for i in bg)
-            hi = max(self.red_groups[i][1] for i in bg)
+            lo = min(self.red_groups[i].lo for i in bg)
+            hi = max(self.red_groups[i].hi for i in bg)
             self.bucket_tables.append((lo, hi, tab))
-            inserts.append((max(self.red_ready[i] for i in bg), k))
+            inserts.append((max(self.red_groups[i].ready for i in bg), k))
         extra = []
-        xk = getattr(reducer, "xgmi_bucket", None) if self.comm_in_graph else None
-        # xGMI exchange of the end-of-backward table too (XgmiPush mode 3): its launch reduces the
-        # conv layers' slabs, pushes them to their owners, finishes their all-reduce and applies
-        # the update -- with the early range exchanged inside the backward, the whole step's
-        # all-reduce + optimizer then runs in table launches and the fused kernel is not launched
-        self.bucket_xchg = {}
-        if xk is not None and tune("xgmi_xchg", True) and (self.exchanged or not dp_early):
-            blo, bhi, btab = self.bucket_tables[xk]
-            rlo, rhi = reducer.buckets[xk]
-            early_n = (self.pushed[1] - self.pushed[0]) if self.exchanged else 0
-            tab_n = sum(self.red_groups[i][1] - self.red_groups[i][0]
-                        for i in bucket_groups[xk] if i not in dp_early)
-            if btab.nblocks > 0 and early_n + tab_n == rhi - rlo:
-                # (the early table's flag slots [0, its nblocks) -- one early table, asserted above)
-                fb = sum(t.nblocks for t in {id(t): t for t in [e[0] for e in self.early_xchg.values()]
-                                             + ([self.xchg_end[0]] if self.xchg_end else [])
-                                             + ([self.xchg_fin[0]] if self.xchg_fin else [])}.values())
-                x3 = reducer.exchange_args(blo, bhi, btab.nblocks, fbase=fb, fused=True)
-                if x3 is not None:
-                    self.bucket_xchg[xk] = x3
         if self.comm_in_graph:
-            rccl_buckets = [k for k in range(len(bucket_groups)) if k != xk]
-            # fork the comm stream only when an RCCL bucket has later backward work to overlap
-            fork = tune("comm_fork", "")
-            self.comm_fork = ((fork not in ("0", "false", "False")) if fork
-                              else any(k < len(bucket_groups) - 1 for k in rccl_buckets))
-            if self.comm_fork:
-                self.comm_stream = torch.cuda.Stream(device=ex.device)
-            if xk is not None:
-                self.optim_on_comm = True
-            extra.append(("allreduce_b%d", lambda k: None if k == xk else
-                          (lambda s: reducer.launch(k, ex.store.grad, s)), "comm"))
-            if self.optim_on_comm:
-                extra.append(("optim_b%d", lambda k: None if k == xk else
-                              (lambda s: self._launch_optim_comm(k, s)), "comm"))
-            # the xGMI bucket: all-reduce + Keras update in one kernel on the main stream
-            # (xchg_at=end: the early range's exchange + update after the end-of-backward reduction)
-            extra.append(("xchg_early_b%d", lambda k: None if (k != xk or self.xchg_end is None) else
-                          (lambda s: K.reduce_optim(ex.store.grad.data_ptr(), self.xchg_end[0],
-                                                    ex._optim_args(False, defer_pack=True), s, self.xchg_end[1])),
-                          "main"))
-            # (the split exchange's finish half rides in the end-of-backward table launch; a launch
-            # of its own only when that table is not exchanged)
-            extra.append(("xchg_fin_b%d", lambda k: None if (k != xk or self.xchg_fin is None
-                                                            or k in self.bucket_xchg) else
-                          (lambda s: K.reduce_optim(ex.store.grad.data_ptr(), self.xchg_fin[0],
-                                                    ex._optim_args(False, defer_pack=True), s, self.xchg_fin[1])),
-                          "main"))
-            extra.append(("xgmi_allreduce_optim_b%d", lambda k: None if (k != xk or k in self.bucket_xchg) else
-                          (lambda s: reducer.launch_fused(ex.store.grad, ex._optim_args(False, defer_pack=True), s,
-                                                          pushed=getattr(self, "pushed", None),
-                                                          exchanged=getattr(self, "exchanged", False))),
-                          "main"))
+            xk = getattr(reducer, "xgmi_bucket", None)
+            self._plan_bucket_exchange(reducer, xk, bucket_groups, dp_early)
+            extra = self._comm_launches(reducer, xk, len(bucket_groups))
         self.launches, self.bucket_ready = splice_bucket_launches(
             self.launches, inserts,
             [("reduce_b%d", lambda k: (lambda s: self._launch_bucket_reduce(k, s)), "side")] + extra)
+        spans = [(lo, hi) for lo, hi, _ in self.bucket_tables]
         if self.comm_in_graph and self.optim_on_comm:
             # a comm-stream optimizer writes its layers' packs: never while a later
             # main-stream launch (a wide conv's separate dgrad) still reads one of them
-            self.launches = defer_after_readers(self.launches, "optim_b%d",
-                                                [(lo, hi) for lo, hi, _ in self.bucket_tables],
-                                                self.pack_readers)
-        spans = [(lo, hi) for lo, hi, _ in self.bucket_tables]
+            self.launches = defer_after_readers(self.launches, "optim_b%d", spans, self.pack_readers)
         # (data parallel: every early reduction lies inside its all-reduce bucket's span)
         if reducer is None:
-            spans += [e[1] for e in (self.early_red or {}).values()]
+            spans = spans + [e[1] for e in self.early_red.values()]
         check_bucket_cover(spans, ex.store.numel)
+
+    def _assign_buckets(self):
+        """Single GPU: the groups of each bucket (lists of red_groups indices), less the groups
+        an early reduction takes; decides optim_fused."""
+        # single stream, no all-reduce to overlap: ONE reduction launch at the end of the
+        # backward (each launch boundary costs ~5 us here), if the descriptors fit a table
+        ndesc = sum(len(grp.descs) for grp in self.red_groups)
+        one = ndesc <= tune("red_desc_max", 16)       # (RedTable capacity, MAX_RED)
+        limit = 1 << 62 if one else int(os.environ.get("INTML_BUCKET_BYTES", 1 << 20))
+        # ... with the optimizer fused into it when its table covers every parameter
+        covered = sum(d.numel for grp in self.red_groups for d in grp.descs)
+        covered += sum(n for _, n in self.dense_fused_opt)
+        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim", True)
+        if not self.optim_fused:
+            # the step ends with a full optimizer launch after all: the dense layers keep
+            # writing their gradient in place, but leave the update -- and the bf16 pack
+            # writes that go with it -- to it, so they also store the gradient it reads
+            for wa, _ in self.dense_fused_opt:
+                wa.opt_w, wa.opt_b = -1, -1
+                wa.pk_fwd, wa.pk_bwd = -1, -1
+                wa.opt_nograd = 0
+            self.dense_fused_opt = []
+        early = self._early_groups() if self.optim_fused else []
+        bucket_groups, cur, nb = [], [], 0
+        for gi, grp in enumerate(self.red_groups):
+            if gi in early:
+                continue
+            cur.append(gi)
+            nb += (grp.hi - grp.lo) * 4
+            if nb >= limit:
+                bucket_groups.append(cur)
+                cur, nb = [], 0
+        if cur:
+            bucket_groups.append(cur)
+        return bucket_groups
+
+    def _assign_buckets_dp(self, reducer):
+        """Data parallel: the reducer's buckets, and the groups reduced early inside the
+        backward (with their xGMI push / exchange planned).  Returns (bucket groups, early groups)."""
+        bucket_groups = reducer.configure([(grp.lo, grp.hi) for grp in self.red_groups])
+        # one bucket at the end of the backward (the adaptive plan for gradients <= 16 MB):
+        # the groups final before the first dual launch (head, dense -- the single-GPU
+        # step's early bucket) are REDUCED early there (grad_only: no update), so the
+        # end-of-backward reduction ahead of the all-reduce only has the conv layers' slabs
+        # left (the update stays behind the all-reduce)
+        # one rank (the N = 1 data-parallel step): nothing to exchange -- the early groups
+        # are reduced AND updated in that launch, as on a single GPU (xchg_p1: keep the
+        # exchange structure, to measure its fixed cost)
+        solo = reducer.size == 1 and getattr(reducer, "xgmi", None) is not None and not tune("xchg_p1", False)
+        if not (len(bucket_groups) == 1 and self.comm_in_graph and tune("dp_early", True)):
+            return bucket_groups, []
+        dp_early = self._early_groups(grad_only=not solo)
+        if solo and self.early_red:
+            self.xchg.pushed = next(iter(self.early_red.values()))[1]
+            self.xchg.exchanged = True
+        # producer push (xGMI plane): the early groups' reduced gradient goes straight to
+        # its owners' inboxes from the launch that reduces it, inside the backward, and
+        # the fused all-reduce kernel skips those elements in its phase 1
+        # ... and (exchange) the NEXT dual launch finishes that range's all-reduce and
+        # applies its update in extra workgroups of its own, so the fused kernel after
+        # the backward is left with the conv layers only
+        if tune("xgmi_push", True) and not solo:
+            # every early table would start at block-flag slot 0 (fbase) and the pushed /
+            # exchanged range is ONE span: _early_groups caps them at one dual launch
+            assert len(self.early_red) <= 1, "exchange: one early table per step (flag slots, pushed range)"
+            for nm, (tab, span, grad_only) in self.early_red.items():
+                if grad_only:
+                    self._plan_early_exchange(reducer, nm, tab, *span)
+        return bucket_groups, dp_early
+
+    def _plan_early_exchange(self, reducer, nm, tab, elo, ehi):
+        """How the early range [elo, ehi), reduced by dual launch ``nm`` through ``tab``, crosses
+        the xGMI plane: split exchange, else unsplit exchange, else producer push only."""
+        x = self.xchg
+        # (xchg_at=end: the exchange as a launch of its own after the end-of-
+        # backward reduction instead of extra workgroups of the next dual launch)
+        at_end = tune("xchg_at", "dual") == "end"
+        nxt = (("end" if at_end else self._xchg_launch(nm, elo, ehi))
+               if tune("xgmi_xchg", True) else None)
+        # split exchange (default): the owner half (wait for the senders, sum,
+        # push the sums back: mode 4) in extra workgroups of the next dual launch,
+        # covering only the table blocks this rank owns part of (none at one
+        # rank), and the finish half (wait for the other owners, update: mode 5)
+        # beside the end-of-backward table in ONE launch -- every wait is on a
+        # flag raised in an EARLIER launch, and no conv-sized workgroup holds a
+        # CU slot for the update (xchg_split=0: both halves in the dual launch)
+        if nxt and not at_end and tune("xchg_split", True):
+            trip = reducer.exchange_args(elo, ehi, tab.nblocks, table=tab)
+            if trip is not None:
+                x.early_push[nm] = trip[0]
+                if trip[1].b_hi > trip[1].b_lo:
+                    x.early_xchg[nxt] = (tab, trip[1])
+                x.xchg_fin = (tab, trip[2])
+                x.pushed, x.exchanged = (elo, ehi), True
+                return
+        # unsplit exchange: the whole finish in the next dual launch (or at the end)
+        pair = reducer.exchange_args(elo, ehi, tab.nblocks) if nxt else None
+        if pair is not None:
+            x.early_push[nm] = pair[0]
+            if at_end:
+                x.xchg_end = (tab, pair[1])
+            else:
+                x.early_xchg[nxt] = (tab, pair[1])
+            x.pushed, x.exchanged = (elo, ehi), True
+            return
+        # push only: the fused all-reduce kernel finishes the range
+        xp = reducer.push_args(elo, ehi)
+        if xp is not None:
+            x.early_push[nm], x.pushed = xp, (elo, ehi)
+
+    def _plan_bucket_exchange(self, reducer, xk, bucket_groups, dp_early):
+        """xGMI exchange of the end-of-backward table too (XgmiPush mode 3): its launch reduces the
+        conv layers' slabs, pushes them to their owners, finishes their all-reduce and applies
+        the update -- with the early range exchanged inside the backward, the whole step's
+        all-reduce + optimizer then runs in table launches and the fused kernel is not launched."""
+        x = self.xchg
+        if xk is None or not tune("xgmi_xchg", True) or not (x.exchanged or not dp_early):
+            return
+        blo, bhi, btab = self.bucket_tables[xk]
+        rlo, rhi = reducer.buckets[xk]
+        early_n = (x.pushed[1] - x.pushed[0]) if x.exchanged else 0
+        tab_n = sum(self.red_groups[i].hi - self.red_groups[i].lo for i in bucket_groups[xk] if i not in dp_early)
+        if btab.nblocks > 0 and early_n + tab_n == rhi - rlo:
+            # (the early table's flag slots [0, its nblocks) -- one early table, asserted above)
+            fb = sum(t.nblocks for t in {id(t): t for t in [e[0] for e in x.early_xchg.values()]
+                                         + ([x.xchg_end[0]] if x.xchg_end else [])
+                                         + ([x.xchg_fin[0]] if x.xchg_fin else [])}.values())
+            x3 = reducer.exchange_args(blo, bhi, btab.nblocks, fbase=fb, fused=True)
+            if x3 is not None:
+                x.bucket_xchg[xk] = x3
+
+    def _comm_launches(self, reducer, xk, nbuckets):
+        """The per-bucket launches behind each bucket's slab reduction when the all-reduces are
+        captured with the step: [(name pattern, factory k -> fn(stream) or None, stream tag)]."""
+        ex, K, x = self.ex, self.ex.K, self.xchg
+        rccl_buckets = [k for k in range(nbuckets) if k != xk]
+        # fork the comm stream only when an RCCL bucket has later backward work to overlap
+        fork = tune("comm_fork", "")
+        self.comm_fork = ((fork not in ("0", "false", "False")) if fork
+                          else any(k < nbuckets - 1 for k in rccl_buckets))
+        if self.comm_fork:
+            self.comm_stream = torch.cuda.Stream(device=ex.device)
+        if xk is not None:
+            self.optim_on_comm = True
+        grad = ex.store.grad
+
+        def xchg_optim(pair):     # an exchange launch of its own: (RedTable, XgmiPush)
+            return lambda s: K.reduce_optim(grad.data_ptr(), pair[0], ex._optim_args(False, defer_pack=True), s,
+                                            pair[1])
+        extra = [("allreduce_b%d", lambda k: None if k == xk else (lambda s: reducer.launch(k, grad, s)), "comm")]
+        if self.optim_on_comm:
+            extra.append(("optim_b%d", lambda k: None if k == xk else
+                          (lambda s: self._launch_optim_comm(k, s)), "comm"))
+        # the xGMI bucket: all-reduce + Keras update in one kernel on the main stream
+        # (xchg_at=end: the early range's exchange + update after the end-of-backward reduction)
+        extra.append(("xchg_early_b%d", lambda k: None if (k != xk or x.xchg_end is None) else
+                      xchg_optim(x.xchg_end), "main"))
+        # (the split exchange's finish half rides in the end-of-backward table launch; a launch
+        # of its own only when that table is not exchanged)
+        extra.append(("xchg_fin_b%d", lambda k: None if (k != xk or x.xchg_fin is None or k in x.bucket_xchg) else
+                      xchg_optim(x.xchg_fin), "main"))
+        extra.append(("xgmi_allreduce_optim_b%d", lambda k: None if (k != xk or k in x.bucket_xchg) else
+                      (lambda s: reducer.launch_fused(grad, ex._optim_args(False, defer_pack=True), s,
+                                                      pushed=x.pushed, exchanged=x.exchanged)),
+                      "main"))
+        return extra
 
     def _early_groups(self, grad_only: bool = False):
         """Single-GPU fused-optimizer step: slab groups whose gradients are final before a dual
@@ -1232,19 +1229,18 @@ class BatchPlan(GeometryMixin):
         for t in duals:
             late_readers = [] if grad_only else [(rlo, rhi) for nm, rlo, rhi in self.pack_readers
                                                  if nm not in names[:t]]
-            grp = [gi for gi in range(len(self.red_groups)) if gi not in taken and self.red_ready[gi] <= t
-                   and not any(rlo < self.red_groups[gi][1] and rhi > self.red_groups[gi][0]
-                               for rlo, rhi in late_readers)]
+            grp = [gi for gi, rg in enumerate(self.red_groups) if gi not in taken and rg.ready <= t
+                   and not any(rlo < rg.hi and rhi > rg.lo for rlo, rhi in late_readers)]
             if not grp:
                 continue
-            lo = min(self.red_groups[gi][0] for gi in grp)
-            hi = max(self.red_groups[gi][1] for gi in grp)
-            descs = [d for gi in grp for d in self.red_groups[gi][2]]
-            if (sum(self.red_groups[gi][1] - self.red_groups[gi][0] for gi in grp) != hi - lo
+            lo = min(self.red_groups[gi].lo for gi in grp)
+            hi = max(self.red_groups[gi].hi for gi in grp)
+            descs = [d for gi in grp for d in self.red_groups[gi].descs]
+            if (sum(self.red_groups[gi].hi - self.red_groups[gi].lo for gi in grp) != hi - lo
                     or not descs or len(descs) > 16):
                 continue                                   # not one contiguous span / table
             tab = self.ex.K.RedTable()
-            for d in sorted(descs, key=lambda d: -d[2]):
+            for d in sorted(descs, key=lambda d: -d.S):
                 tab.add(*d)
             self.early_red[names[t]] = (tab, (lo, hi), grad_only)
             taken += grp
@@ -1273,8 +1269,6 @@ class BatchPlan(GeometryMixin):
         a = ex._optim_args(False, defer_pack=True)   # built at capture time: grad_scale = 1/size
         a.lo, a.n = lo, hi - lo
         ex.tile_routes(a)
-        if getattr(self, "_no_packs", None) is None:
-            self._no_packs = ex.K.PackTable()
         ex.K.optim(a, self._no_packs, stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
 
     # ---------------------------------------------------------------- execution
@@ -1286,7 +1280,7 @@ class BatchPlan(GeometryMixin):
         if skip:
             drop = set(skip.split("/"))
             items = [it for it in items if it[0] not in drop]
-        tags = [it[2] if len(it) > 2 else "main" for it in items]
+        tags = [it.tag for it in items]
         streams = {"main": torch.cuda.current_stream(), "comm": self.comm_stream}
         for op in stream_program(tags, comm=self.comm_stream is not None):
             if op[0] == "wait":
@@ -1300,8 +1294,7 @@ class BatchPlan(GeometryMixin):
     def _launch_bucket_reduce(self, k, s):
         lo, hi, tab = self.bucket_tables[k]
         ex = self.ex
-        xp = (getattr(self, "bucket_xchg", None) or {}).get(k)
-        fin = getattr(self, "xchg_fin", None)
+        xp, fin = self.xchg.bucket_xchg.get(k), self.xchg.xchg_fin
         if xp is not None and fin is not None:   # + the early range's exchange finish (mode 5)
             ex.K.reduce_optim_end(ex.store.grad.data_ptr(), tab, ex._optim_args(False, defer_pack=True), s, xp,
                                   fin[0], fin[1])

@@ -5,11 +5,13 @@ executor_hip.BatchPlan (split out of it to keep the step-program logic and the g
 apart); every method reads the plan's executor (``self.ex``) and batch size."""
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 
-from ..ops.rng import keep_threshold
 from ..utils.env import tune
 from . import lds_layout
+from .step_program import dropout_pair
 
 
 def cdiv(a, b):
@@ -27,7 +29,25 @@ def _pow2_le(x, cap):
     return p
 
 
+class Wgrad(NamedTuple):
+    """A prepared weight-gradient launch: its WgradArgs, the kernel's two tile parameters
+    (wgrad_tile: (ntc, None); wgrad_halo: (MT, NTT); wgrad: (ktw, ntt); dense_wgrad: (kg, ntt)),
+    the split count, and the partial slabs the splits write (slab None: written in place)."""
+    a: object
+    tiles: tuple
+    splits: int
+    slab: Optional[torch.Tensor]
+    bslab: Optional[torch.Tensor]
+
+    @property
+    def cfg(self):
+        """(tile, tile, splits): the launchers' three integers after the WgradArgs."""
+        return self.tiles + (self.splits,)
+
+
 class GeometryMixin:
+    """Reads the plan's executor and batch size, and the plan state BatchPlan.__init__ creates
+    before any of these run: early_red, xchg, wgrad_slabs, _ncu, _zero16."""
     LDS_LIMIT = 160 * 1024
 
     def _conv_stack_args(self, training: bool):
@@ -83,8 +103,7 @@ class GeometryMixin:
             L.pool, L.relu = int(g.pool), int(g.relu)
             L.Hp, L.Wp = g.Hp, g.Wp
             if training and g.rate > 0:
-                L.drop_thr = keep_threshold(g.rate)
-                L.drop_scale = 1.0 / (1.0 - g.rate)
+                L.drop_thr, L.drop_scale = dropout_pair(g.rate)
             L.stream_id = g.stream
             L.wpk = ex.arena.data_ptr() + 2 * g.pack_fwd
             L.bias = store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
@@ -188,7 +207,7 @@ class GeometryMixin:
 
     def _cu_count(self):
         """Compute units of the executor's device (256 on MI355X; CPU / no device: 256)."""
-        if getattr(self, "_ncu", None) is None:
+        if self._ncu is None:
             try:
                 self._ncu = int(torch.cuda.get_device_properties(self.ex.device).multi_processor_count)
             except Exception:          # noqa: BLE001
@@ -197,7 +216,7 @@ class GeometryMixin:
 
     def _zero_buf(self):
         """Zero bytes for the LDS-DMA kernels: padded rows read from here (DMA cannot zero-fill)."""
-        if getattr(self, "_zero16", None) is None:
+        if self._zero16 is None:
             self._zero16 = torch.zeros(64, dtype=torch.bfloat16, device=self.ex.device)
         return self._zero16
 
@@ -254,11 +273,11 @@ class GeometryMixin:
 
     def _dual(self, a, ntc, wa, cfg, s, name=None):
         K, ex = self.ex.K, self.ex
-        early = (self.early_red or {}).get(name)
-        xp = (getattr(self, "early_push", None) or {}).get(name)   # producer push (xGMI plane)
+        early = self.early_red.get(name)
+        xp = self.xchg.early_push.get(name)   # producer push (xGMI plane)
         # exchange (xGMI plane): this launch finishes an earlier launch's pushed range -- its
         # all-reduce + Keras update in extra workgroups (XgmiPush mode 2)
-        xe = (getattr(self, "early_xchg", None) or {}).get(name)
+        xe = self.xchg.early_xchg.get(name)
         kw = {}
         if early is not None:   # this launch also carries an early bucket's reduction (+ optimizer)
             kw.update(rt=early[0], ro=self._early_ro(early), rgrad=ex.store.grad.data_ptr(),
@@ -331,26 +350,51 @@ class GeometryMixin:
             raise NotImplementedError("conv halo stage too large (%d bytes)" % lds)
         return ntc
 
-    def _wgrad_tile_args(self, xin, g, bs, bias):
-        """Tiled wgrad for wide convs: 128(k) x ntc*16(n) tiles, split-K over pixel ranges."""
-        K, dev = self.ex.K, self.ex.device
-        a = K.WgradArgs()
+    def _wgrad_base(self, xin, H, W, Cs_in, Ho, Wo, taps, dy, Cs_dy, NT, pool=None):
+        """WgradArgs with what every weight-gradient kernel reads: the input activations, the
+        conv geometry (``taps`` = (KH, KW, stride, pad_t, pad_l); None: a dense GEMM whose
+        kernel reads none of them), dY -- with ``pool`` = (codes, Hp, Wp) rebuilt on load from
+        the pooled gradient -- and the n-tile / pixel counts."""
+        a = self.ex.K.WgradArgs()
         a.x = xin.data_ptr()
-        a.B, a.H, a.W, a.Cs_in = bs, g.H, g.W, g.Cs_in
-        a.Ho, a.Wo, a.KH, a.KW, a.stride, a.pad_t, a.pad_l = g.Ho, g.Wo, g.KH, g.KW, g.stride, g.pad_t, g.pad_l
-        a.Ktiles = cdiv(g.KH * g.KW * g.Cs_in, 16)
-        a.dy = self.conv_dy[g.i].data_ptr()
-        a.Cs_dy = g.Cs_out
-        if g.pool:
-            a.dy_code = self.conv_code[g.i].data_ptr()
-            a.dHp, a.dWp = g.Hp, g.Wp
-        a.NT = g.NT
+        a.B, a.H, a.W, a.Cs_in = self.bs, H, W, Cs_in
+        a.Ho, a.Wo = Ho, Wo
+        if taps is not None:
+            a.KH, a.KW, a.stride, a.pad_t, a.pad_l = taps
+        a.Ktiles = cdiv((taps[0] * taps[1] if taps else 1) * Cs_in, 16)
+        a.dy = dy.data_ptr()
+        a.Cs_dy = Cs_dy
+        if pool is not None:
+            a.dy_code, a.dHp, a.dWp = pool[0].data_ptr(), pool[1], pool[2]
+        a.NT = NT
+        a.P = self.bs * Ho * Wo
+        return a
+
+    def _conv_wgrad_base(self, xin, g):
+        return self._wgrad_base(xin, g.H, g.W, g.Cs_in, g.Ho, g.Wo, (g.KH, g.KW, g.stride, g.pad_t, g.pad_l),
+                                self.conv_dy[g.i], g.Cs_out, g.NT,
+                                (self.conv_code[g.i], g.Hp, g.Wp) if g.pool else None)
+
+    def _wgrad_slabs(self, a, S, bias, direct=None):
+        """The S partial slabs (and bias slabs) of a wgrad launch, entered into ``a`` and
+        plan.wgrad_slabs; ``direct``: the one-split kernel writes the gradient at that address
+        instead of a slab."""
+        dev, ld = self.ex.device, a.NT * 16
+        slab = None if direct else torch.zeros(S, a.Ktiles * 16, ld, dtype=torch.float32, device=dev)
+        bslab = torch.zeros(S, ld, dtype=torch.float32, device=dev) if bias else None
+        a.slab = direct if direct else slab.data_ptr()
+        a.bslab = bslab.data_ptr() if bslab is not None else 0
+        self.wgrad_slabs.append((slab, bslab))
+        return slab, bslab
+
+    def _wgrad_tile_args(self, xin, g, bias):
+        """Tiled wgrad for wide convs: 128(k) x ntc*16(n) tiles, split-K over pixel ranges."""
+        a = self._conv_wgrad_base(xin, g)
         ntc = 8 if g.NT > 4 else (4 if g.NT > 2 else 2)
         ntc = min(ntc, tune("wgrad_tile_ntc", ntc))
         if tune("conv_glds", True):
             a.zero = self._zero_buf().data_ptr()
-        P = bs * g.Ho * g.Wo
-        a.P = P
+        P = a.P
         tiles = cdiv(a.Ktiles * 16, 128) * cdiv(g.NT, ntc)
         per_split_bytes = a.Ktiles * 16 * g.NT * 16 * 4
         # split count: as many workgroups as fit the machine AT ONCE (64 KB of LDS each: two per
@@ -364,28 +408,12 @@ class GeometryMixin:
                        (tune("wgrad_tile_slab_mb", 64) << 20) // per_split_bytes, cdiv(P, 256)))
         a.px_per_split = cdiv(cdiv(P, S), 64) * 64
         S = cdiv(P, a.px_per_split)
-        slab = torch.zeros(S, a.Ktiles * 16, g.NT * 16, dtype=torch.float32, device=dev)
-        bslab = torch.zeros(S, g.NT * 16, dtype=torch.float32, device=dev) if bias else None
-        a.slab = slab.data_ptr()
-        a.bslab = bslab.data_ptr() if bslab is not None else 0
-        self.wgrad_slabs.append((slab, bslab))
-        return a, (ntc, None, S), slab, bslab
+        return Wgrad(a, (ntc, None), S, *self._wgrad_slabs(a, S, bias))
 
-    def _wgrad_halo_args(self, xin, g, bs, bias):
-        K, dev = self.ex.K, self.ex.device
-        a = K.WgradArgs()
-        a.x = xin.data_ptr()
-        a.B, a.H, a.W, a.Cs_in = bs, g.H, g.W, g.Cs_in
-        a.Ho, a.Wo, a.KH, a.KW, a.stride, a.pad_t, a.pad_l = g.Ho, g.Wo, g.KH, g.KW, g.stride, g.pad_t, g.pad_l
-        a.Ktiles = cdiv(g.KH * g.KW * g.Cs_in, 16)
-        a.dy = self.conv_dy[g.i].data_ptr()
-        a.Cs_dy = g.Cs_out
-        if g.pool:
-            a.dy_code = self.conv_code[g.i].data_ptr()
-            a.dHp, a.dWp = g.Hp, g.Wp
+    def _wgrad_halo_args(self, xin, g, bias):
+        K, bs = self.ex.K, self.bs
+        a = self._conv_wgrad_base(xin, g)
         NT = g.NT
-        a.NT = NT
-        a.P = bs * g.Ho * g.Wo
         NTT = _pow2_le(NT, 8)
         # each wave owns <= 4 m-tiles x NTT n-tiles (<= 16 accumulator tiles)
         mt_cap = (8 if NTT == 8 else 16) - (1 if bias else 0)
@@ -434,10 +462,7 @@ class GeometryMixin:
         lds = K.wgrad_halo_lds_bytes(a, MT, NTT)
         if lds > 150 * 1024:
             raise NotImplementedError("wgrad halo stage too large (%d bytes)" % lds)
-        slab = torch.zeros(S, a.Ktiles * 16, NT * 16, dtype=torch.float32, device=dev)
-        bslab = torch.zeros(S, NT * 16, dtype=torch.float32, device=dev) if bias else None
-        a.slab = slab.data_ptr()
-        a.bslab = bslab.data_ptr() if bslab is not None else 0
+        slab, bslab = self._wgrad_slabs(a, S, bias)
         # write-through slabs (16-byte sc1 stores, byte offsets < 2 GB)
         a.wt = int(bool(int(tune("wt", 7)) & 4) and slab.numel() * 4 < (1 << 31))
         # layer-signature instances (geometry fixed at compile time, csrc/kernels/wgrad_sig.h)
@@ -445,25 +470,15 @@ class GeometryMixin:
         # The split count above is sized by the GENERIC instance's residency either way, so the
         # slab layout and the reduction order do not depend on this switch.
         a.spec = int(tune("wgrad_spec", 1))
-        self.wgrad_slabs.append((slab, bslab))
-        return a, (MT, NTT, S), slab, bslab
+        return Wgrad(a, (MT, NTT), S, slab, bslab)
 
-    def _wgrad_args(self, xin, H, W, Cs_in, Ho, Wo, KH, KW, stride, pad_t, pad_l, dy, Cs_dy, N, bs, bias,
-                    direct=None):
-        K, dev = self.ex.K, self.ex.device
-        a = K.WgradArgs()
-        a.x = xin.data_ptr()
-        a.B, a.H, a.W, a.Cs_in = bs, H, W, Cs_in
-        a.Ho, a.Wo, a.KH, a.KW, a.stride, a.pad_t, a.pad_l = Ho, Wo, KH, KW, stride, pad_t, pad_l
-        if not (Cs_in == 4 or Cs_in % 8 == 0):
-            raise NotImplementedError("wgrad needs Cs_in == 4 or a multiple of 8 (got %d)" % Cs_in)
-        a.Ktiles = cdiv(KH * KW * Cs_in, 16)
-        a.dy = dy.data_ptr()
-        a.Cs_dy = Cs_dy
+    def _wgrad_args(self, xin, width, dy, Cs_dy, N, bias, direct=None):
+        """Dense weight gradient on the generic split-K wgrad kernel (a 1x1 conv over a 1x1 grid)."""
+        if not (width == 4 or width % 8 == 0):
+            raise NotImplementedError("wgrad needs Cs_in == 4 or a multiple of 8 (got %d)" % width)
         NT = cdiv(N, 16)
-        a.NT = NT
-        P = bs * Ho * Wo
-        a.P = P
+        a = self._wgrad_base(xin, 1, 1, width, 1, 1, (1, 1, 1, 0, 0), dy, Cs_dy, NT)
+        P = a.P
         ntt = _pow2_le(NT, 8)
         ktw = 4 if ntt <= 4 else 2
         while ktw > 1 and 4 * (ktw // 2) >= a.Ktiles:
@@ -479,28 +494,14 @@ class GeometryMixin:
         pps = cdiv(cdiv(P, S), 32) * 32
         S = cdiv(P, pps)
         a.px_per_split = pps
-        slab = None if direct else torch.zeros(S, a.Ktiles * 16, NT * 16, dtype=torch.float32, device=dev)
-        bslab = torch.zeros(S, NT * 16, dtype=torch.float32, device=dev) if bias else None
-        a.slab = direct if direct else slab.data_ptr()
-        a.bslab = bslab.data_ptr() if bslab is not None else 0
-        self.wgrad_slabs.append((slab, bslab))
-        return a, (ktw, ntt, S), slab, bslab
+        return Wgrad(a, (ktw, ntt), S, *self._wgrad_slabs(a, S, bias, direct))
 
-    def _dense_wgrad_args(self, xin, width, dh, Ns, N, bs, bias, direct=None):
+    def _dense_wgrad_args(self, xin, width, dh, Ns, N, bias, direct=None):
         """Dense weight gradient on dense_wgrad_kernel: KG*16 features x NTT*16 outputs per
         workgroup, the batch split into row ranges of >= 128 rows (one 32-row chunk per wave)
         until the launch has ~256 workgroups or the partial slabs reach their byte budget."""
-        K, dev = self.ex.K, self.ex.device
-        a = K.WgradArgs()
-        a.x = xin.data_ptr()
-        a.B, a.H, a.W, a.Cs_in = bs, 1, 1, width
-        a.Ho, a.Wo = 1, 1
-        a.Ktiles = cdiv(width, 16)
-        a.dy = dh.data_ptr()
-        a.Cs_dy = Ns
-        NT = cdiv(N, 16)
-        a.NT = NT
-        a.P = bs
+        bs, NT = self.bs, cdiv(N, 16)
+        a = self._wgrad_base(xin, 1, 1, width, 1, 1, None, dh, Ns, NT)
         # (at most 4 n-tiles: twice the workgroups of 8 -- RPV +0.6 %, MNIST +1.2 %,
         # profiles/r4s_ab_rpv.txt, r4s_ab_mnist.txt)
         ntt = _pow2_le(NT, min(8, tune("dw_ntt", 4)))
@@ -513,12 +514,7 @@ class GeometryMixin:
         pps = cdiv(cdiv(bs, S), 32) * 32
         S = cdiv(bs, pps)
         a.px_per_split = pps
-        slab = None if direct else torch.zeros(S, a.Ktiles * 16, NT * 16, dtype=torch.float32, device=dev)
-        bslab = torch.zeros(S, NT * 16, dtype=torch.float32, device=dev) if bias else None
-        a.slab = direct if direct else slab.data_ptr()
-        a.bslab = bslab.data_ptr() if bslab is not None else 0
-        self.wgrad_slabs.append((slab, bslab))
-        return a, (kg, ntt, S), slab, bslab
+        return Wgrad(a, (kg, ntt), S, *self._wgrad_slabs(a, S, bias, direct))
 
     @staticmethod
     def _dense_dx_ntc(a):

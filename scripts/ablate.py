@@ -52,7 +52,7 @@ for item in bp.launches:
     t = timeit(fn)
     total += t
     line = "%-16s %9.2f" % (name, t)
-    args = fn.__defaults__[0] if fn.__defaults__ else None
+    args = next((v for v in item.args.values() if hasattr(v, "dbg")), None)
     if hasattr(args, "dbg"):
         res = []
         for dbg in (1, 2, 4, 7):
@@ -62,12 +62,12 @@ for item in bp.launches:
         line += " | " + "  ".join("%9.2f" % v for v in res)
     print(line, flush=True)
 K = ex.K
-for gi, (lo, hi, descs) in enumerate(bp.red_groups):
+for gi, (lo, hi, descs, _ready) in enumerate(bp.red_groups):
     for d in descs:
         tab = K.RedTable()
         tab.add(*d)
         t = timeit(lambda st, tab=tab: K.slab_reduce(ex.store.grad.data_ptr(), 0, 0, tab, st))
-        print("  reduce grp%d type%d S=%d numel=%d: %.2f us" % (gi, d[6], d[2], d[5], t))
+        print("  reduce grp%d type%d S=%d numel=%d: %.2f us" % (gi, d.type, d.S, d.numel, t))
 t = timeit(lambda st: bp._launch_optim())
 total += t
 print("%-16s %9.2f" % ("optim", t))

@@ -41,14 +41,10 @@ def stats(v):
     return "med %6.2f p90 %6.2f max %6.2f" % (np.median(v), np.percentile(v, 90), v.max())
 
 
-for name, fn, *_ in bp.launches:
+for name, fn, _tag, roles in bp.launches:
     if not (name.startswith("wgrad_dgrad") or name.startswith("wgrad_conv")):
         continue
-    dfl = fn.__defaults__
-    if name.startswith("wgrad_dgrad"):
-        ca, ntc, wa, cfg = dfl[:4]
-    else:
-        ca, ntc, (wa, cfg) = None, None, dfl[:2]
+    ca, ntc, wa, cfg = roles.get("ca"), roles.get("ntc"), roles["wa"], roles["cfg"]
     MT, NTT, S = cfg
     n_w = S * cdiv(wa.NT, NTT) * cdiv(wa.Ktiles, MT)
     n_c = 0
@@ -117,10 +113,10 @@ def _t(fn, reps=40):
 
 
 variants = [int(v) for v in os.environ.get("AB_DBG", "0,16").split(",")]
-for name, fn, *_ in bp.launches:
+for name, fn, _tag, roles in bp.launches:
     if not name.startswith("wgrad_dgrad"):
         continue
-    ca, wa = fn.__defaults__[0], fn.__defaults__[2]
+    ca, wa = roles["ca"], roles["wa"]
     res = {v: [] for v in variants}
     for _ in range(5):
         for v in variants:

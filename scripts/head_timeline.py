@@ -27,8 +27,8 @@ ex.train_step(d, torch.arange(d.n, device=dev), 0, B)
 torch.cuda.synchronize()
 bp = ex._plans[(B, "train")]
 s = torch.cuda.current_stream().cuda_stream
-fn = [f for (n, f, *_) in bp.launches if n == "head"][0]
-a = fn.__defaults__[0]
+it = [it for it in bp.launches if it.name == "head"][0]
+fn, a = it.fn, it.args["head"]
 ts = torch.zeros(B * 8, dtype=torch.int64, device=dev)
 a.ts = ts.data_ptr()
 for _ in range(10):

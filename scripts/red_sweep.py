@@ -44,7 +44,7 @@ def timeit(fn, reps=40):
 for name, fn, *_ in bp.launches:
     if name.startswith("reduce"):
         print("%s (as captured): %.2f us" % (name, timeit(fn)))
-for gi, (lo, hi, descs) in enumerate(bp.red_groups):
+for gi, (lo, hi, descs, _ready) in enumerate(bp.red_groups):
     for dsc in descs:
         row = []
         for tpe in (1, 4, 8, 16, 32, 64, 128, 256):
@@ -57,20 +57,20 @@ for gi, (lo, hi, descs) in enumerate(bp.red_groups):
         print("grp%d type%d S=%d numel=%d  tpe:us  %s" % (gi, dsc[6], dsc[2], dsc[5], "  ".join(row)), flush=True)
 
 # fused reduce+optimizer launch over subsets of the descriptors
-descs = [d for (_, _, ds) in bp.red_groups for d in ds]
+descs = [d for grp in bp.red_groups for d in grp.descs]
 oa = ex._optim_args(False, defer_pack=True)
 
 
 def table(sel):
     tab = K.RedTable()
-    for d in sorted(sel, key=lambda d: -d[2]):
+    for d in sorted(sel, key=lambda d: -d.S):
         tab.add(*d)
     return tab
 
 
-for label, sel in (("all", descs), ("no dense W", [d for d in descs if d[6] != 2]),
-                   ("dense W only", [d for d in descs if d[6] == 2]),
-                   ("conv W only", [d for d in descs if d[6] == 0])):
+for label, sel in (("all", descs), ("no dense W", [d for d in descs if d.type != 2]),
+                   ("dense W only", [d for d in descs if d.type == 2]),
+                   ("conv W only", [d for d in descs if d.type == 0])):
     tab = table(sel)
     t = timeit(lambda st, tab=tab: K.reduce_optim(ex.store.grad.data_ptr(), tab, oa, st))
     print("reduce_optim [%s] %d WGs: %.2f us" % (label, tab.nblocks if hasattr(tab, "nblocks") else -1, t), flush=True)

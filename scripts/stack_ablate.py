@@ -56,7 +56,7 @@ for item in bp.launches:
     t = timeit(fn)
     total += t
     line = "%-20s %8.2f" % (name, t)
-    structs = [v for v in (fn.__defaults__ or ()) if hasattr(v, "dbg")]
+    structs = [v for v in item.args.values() if hasattr(v, "dbg")]
     if structs:
         res = []
         for dbg in (1, 2, 4, 8, 15):

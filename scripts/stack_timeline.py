@@ -30,8 +30,8 @@ ex.train_step(d, perm, 0, B)
 torch.cuda.synchronize()
 bp = ex._plans[(B, "train")]
 s = torch.cuda.current_stream().cuda_stream
-fn = [f for (n, f, *_) in bp.launches if n == "conv_stack_fwd"][0]
-a = fn.__defaults__[0]
+it = [it for it in bp.launches if it.name == "conv_stack_fwd"][0]
+fn, a = it.fn, it.args["stack"]
 nblk = a.B * a.splits
 print("conv_stack: B=%d splits=%d blocks=%d lds_bytes=%d layers=%d" % (a.B, a.splits, nblk, a.lds_bytes, a.n))
 nw = ex.K.STACK_THREADS // 64                 # waves per workgroup (stamp rows per block)

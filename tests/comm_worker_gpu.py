@@ -80,7 +80,7 @@ def main(out):
         results[name] = {"reducer": type(red).__name__, "buckets": [list(b) for b in red.buckets]}
         plan = next(iter(m._executor._plans.values()))
         results[name]["comm_in_graph"] = bool(plan.comm_in_graph)
-        results[name]["n_comm_launches"] = sum(1 for it in plan.launches if len(it) > 2 and it[2] == "comm")
+        results[name]["n_comm_launches"] = sum(1 for it in plan.launches if it.tag == "comm")
         results[name]["max_abs_diff"] = float(np.abs(w - wb).max())
         results[name]["p999_abs_diff"] = float(np.quantile(np.abs(w - wb), 0.999))
         results[name]["w"] = w
@@ -94,7 +94,7 @@ def main(out):
     plan = next(iter(m._executor._plans.values()))
     results["xgmi"] = {"active": m._executor.reducer.xgmi is not None,
                        "launches": [it[0] for it in plan.launches if "xgmi" in it[0] or "allreduce" in it[0]],
-                       "bucket_xchg": sorted((getattr(plan, "bucket_xchg", None) or {}).keys()),
+                       "bucket_xchg": sorted(plan.xchg.bucket_xchg.keys()),
                        "max_abs_diff": float(np.abs(w - wb).max()),
                        "p999_abs_diff": float(np.quantile(np.abs(w - wb), 0.999))}
     # hybrid plane: bucket 0 (head + dense) over RCCL on the comm stream with its optimizer,
@@ -109,7 +109,7 @@ def main(out):
     plan = next(iter(m._executor._plans.values()))
     red = m._executor.reducer
     results["hybrid"] = {"xgmi_bucket": red.xgmi_bucket, "buckets": [list(b) for b in red.buckets],
-                         "launches": [(it[0], it[2] if len(it) > 2 else "main") for it in plan.launches
+                         "launches": [(it.name, it.tag) for it in plan.launches
                                       if "xgmi" in it[0] or "allreduce" in it[0] or it[0].startswith("optim")],
                          "comm_fork": bool(plan.comm_fork),
                          "max_abs_diff": float(np.abs(w - wb).max()),

@@ -90,15 +90,16 @@ def run(opt, lr, outdir, r, P, dev):
     rep["fused_launches"] = [it[0] for it in plan.launches if "xgmi" in it[0] or "allreduce" in it[0]]
     # producer push: the launches that reduce the early (head / dense) groups inside the
     # backward and push them to their owners' inboxes, and the range the all-reduce skips
-    rep["push_launches"] = sorted((getattr(plan, "early_push", None) or {}).keys())
-    rep["pushed"] = list(getattr(plan, "pushed", None) or [])
-    rep["xchg_launches"] = sorted((getattr(plan, "early_xchg", None) or {}).keys())
-    rep["exchanged"] = bool(getattr(plan, "exchanged", False))
-    rep["xchg_fin"] = getattr(plan, "xchg_fin", None) is not None     # split exchange: finish half at the end
-    rep["bucket_xchg"] = sorted((getattr(plan, "bucket_xchg", None) or {}).keys())
+    xchg = plan.xchg
+    rep["push_launches"] = sorted(xchg.early_push.keys())
+    rep["pushed"] = list(xchg.pushed or [])
+    rep["xchg_launches"] = sorted(xchg.early_xchg.keys())
+    rep["exchanged"] = bool(xchg.exchanged)
+    rep["xchg_fin"] = xchg.xchg_fin is not None     # split exchange: finish half at the end
+    rep["bucket_xchg"] = sorted(xchg.bucket_xchg.keys())
     # exchange geometry: looping workgroups (nx > 0, ranks sharing a GPU) or one per block (0)
-    rep["xchg_nx"] = sorted({int(v[1].nx) for v in (getattr(plan, "early_xchg", None) or {}).values()}
-                            | {int(v.nx) for v in (getattr(plan, "bucket_xchg", None) or {}).values()})
+    rep["xchg_nx"] = sorted({int(v[1].nx) for v in xchg.early_xchg.values()}
+                            | {int(v.nx) for v in xchg.bucket_xchg.values()})
     rep["shared"] = bool(red.xgmi.shared) if red.xgmi is not None else None
     rep["err"] = int(red.xgmi.err[0].item()) if red.xgmi is not None else -1
     rep["digest"] = hashlib.sha256(w.tobytes()).hexdigest()

@@ -190,3 +190,52 @@ def test_comm_optimizer_waits_for_later_pack_readers():
     # nothing to defer: the RPV step's order is unchanged
     rpv, _, sp = _fake_step()
     assert defer_after_readers(rpv, "optim_b%d", sp, [("dense_bwd0", 23584, 547712)]) == rpv
+
+
+def test_splice_and_defer_take_tuples_and_launches():
+    """splice_bucket_launches / defer_after_readers index by position: they accept plain
+    3-tuples mixed with Launch records, create Launch records, and move entries untouched
+    (tag and args included)."""
+    from cori_intml_examples_amd.models.executor_hip import Launch, defer_after_readers
+    wa, fn = object(), (lambda s: None)
+    base = [("head", None, "main"),
+            Launch("wgrad_conv1", fn, "side", {"wa": wa, "cfg": (4, 2, 7)}),
+            ("dgrad_conv1", None, "main"),
+            Launch("wgrad_conv0", fn, "side", {"wa": wa, "cfg": (3, 1, 5)})]
+    per = [("reduce_b%d", lambda k: fn, "side"), ("allreduce_b%d", lambda k: fn, "comm"),
+           ("optim_b%d", lambda k: (fn if k == 0 else None), "comm")]
+    out, ready = splice_bucket_launches(base, [(2, 0), (4, 1)], per)
+    assert [it[0] for it in out] == ["head", "wgrad_conv1", "reduce_b0", "allreduce_b0", "optim_b0", "dgrad_conv1",
+                                     "wgrad_conv0", "reduce_b1", "allreduce_b1"]
+    assert ready == [5, 9]
+    created = [it for it in out if it[0][:-1] in ("reduce_b", "allreduce_b", "optim_b")]
+    assert len(created) == 5 and all(type(it) is Launch for it in created)
+    assert [it.tag for it in created] == ["side", "comm", "comm", "side", "comm"]
+    assert all(it.fn is fn and it.args == {} for it in created)
+    assert out[0] is base[0] and out[1] is base[1] and out[5] is base[2] and out[6] is base[3]
+    # optim_b0 writes conv1's pack, which dgrad_conv1 reads: moved behind it, as the same object
+    moved = defer_after_readers(out, "optim_b%d", [(10, 20), (0, 10)], [("dgrad_conv1", 10, 20)])
+    assert [it[0] for it in moved] == ["head", "wgrad_conv1", "reduce_b0", "allreduce_b0", "dgrad_conv1", "optim_b0",
+                                       "wgrad_conv0", "reduce_b1", "allreduce_b1"]
+    assert moved[5] is out[4] and moved[4] is base[2]
+    assert moved[1] is base[1] and moved[1].tag == "side" and moved[1].args == {"wa": wa, "cfg": (4, 2, 7)}
+    assert moved[1].args["wa"] is wa
+    assert len(out) == 9 and out[4][0] == "optim_b0"          # the input list is not modified
+
+
+def test_red_desc_unpacks_in_red_table_add_order():
+    """RedDesc is the argument list of RedTable.add (bindings.cpp): twelve fields in its order,
+    the layout fields zero unless given."""
+    from cori_intml_examples_amd.models.executor_hip import RedDesc, RedGroup
+    assert RedDesc._fields == ("slab", "stride_s", "S", "ld", "dst_off", "numel", "type",
+                               "KH", "KW", "Cin", "Cout", "Cs")
+    got = []
+    d = RedDesc(0x7f00, 4096, 14, 64, 448, 4640, 0, 3, 3, 16, 32, 16)
+    (lambda *a: got.extend(a))(*d)
+    assert got == [0x7f00, 4096, 14, 64, 448, 4640, 0, 3, 3, 16, 32, 16]
+    assert (d.S, d.numel, d.type, d.Cs) == (14, 4640, 0, 16) and d[2] == 14 and d[5] == 4640
+    b = RedDesc(0x7f00, 64, 14, 64, 5088, 32, 1)
+    assert tuple(b) == (0x7f00, 64, 14, 64, 5088, 32, 1, 0, 0, 0, 0, 0)
+    g = RedGroup(448, 5120, [d, b], 7)
+    lo, hi, descs, ready = g
+    assert (lo, hi, ready) == (448, 5120, 7) and descs == [d, b] and g.ready == 7

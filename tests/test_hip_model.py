@@ -546,8 +546,7 @@ def test_conv_stack_specialised_bit_identical(kind, drop, cin, hw, monkeypatch):
         ex.train_steps(d, perm, 0, 128, 2)
         torch.cuda.synchronize()
         plan = ex._plans[(128, "train")]
-        stack = [f for it in plan.launches if it[0] == "conv_stack_fwd" for f in (it[1].__defaults__ or ())
-                 if hasattr(f, "spec")]
+        stack = [it.args["stack"] for it in plan.launches if it[0] == "conv_stack_fwd"]
         assert len(stack) == 1
         res.append((m.store.master[:m.store.numel].clone(), ex.read_metrics(), ex.K.conv_stack_variant(stack[0])))
     assert res[0][2] > 0 and res[1][2] > 0 and res[2][2] == 0, [r[2] for r in res]

@@ -54,12 +54,11 @@ def _run(kind, opt, drop, cin, bs, tunes, monkeypatch):
     K = ex.K
     info = {}
     for it in plan.launches:
-        dfl = it[1].__defaults__ or ()
         if it[0].startswith("wgrad_conv"):
-            wa, cfg = dfl[0], dfl[1]
+            wa, cfg = it.args["wa"], it.args["cfg"]
             info[it[0][len("wgrad_conv"):]] = (K.wgrad_halo_variant(wa, cfg[0], cfg[1]), wa.blocks_per_split, cfg[2])
         elif it[0].startswith("wgrad_dgrad_conv"):
-            ca, ntc, wa, cfg = dfl[0], dfl[1], dfl[2], dfl[3]
+            ca, ntc, wa, cfg = (it.args[r] for r in ("ca", "ntc", "wa", "cfg"))
             info[it[0][len("wgrad_dgrad_conv"):]] = (K.dual_halo_variant(ca, ntc, wa, cfg[0], cfg[1]),
                                                      wa.blocks_per_split, cfg[2])
     slabs = [t.clone() for pair in plan.wgrad_slabs for t in pair if t is not None]
