@@ -25,7 +25,8 @@ import torch
 
 from ..ops.hip import kernels
 from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, fill_kernel_args
-from ..utils.env import env_flag, tune
+from ..utils.env import env_flag
+from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin, cdiv, r8  # noqa: F401  (cdiv: re-exported for tests)
 from .plan import Plan
@@ -110,7 +111,7 @@ class HipExecutor(Executor):
     def __init__(self, plan: Plan, store, optimizer, seed: int):
         super().__init__(plan, store, optimizer, seed)
         self.K = kernels()
-        self.K.set_red_lanes(int(tune("red_lanes", 16)))   # slab partials per reduction split-lane
+        self.K.set_red_lanes(int(tune("red_lanes")))   # slab partials per reduction split-lane
         self.device = store.device
         if self.device.type != "cuda":
             raise RuntimeError("HipExecutor needs a GPU device")
@@ -242,7 +243,7 @@ class HipExecutor(Executor):
                            g.NT, g.NTb if g.KSb else 0, g.pack_fwd, g.pack_bwd if g.KSb else -1))
         # (a dense layer whose optimizer runs inside its wgrad kernel writes its packs there
         # too -- WgradArgs.pk_fwd -- or is not fused: see BatchPlan._dense_wgrad)
-        self.routes_ok = bool(routes) and len(routes) <= K.MAX_ROUTES and tune("opt_packs", True)
+        self.routes_ok = bool(routes) and len(routes) <= K.MAX_ROUTES and tune("opt_packs")
         self.routes = None
         self.route_list = routes
         if self.routes_ok:
@@ -284,7 +285,7 @@ class HipExecutor(Executor):
         padding, N % 32 == 0, K % 8 == 0) are updated by 2-D tile blocks that write whole
         16-byte pack vectors (the flat blocks' scattered 2-byte pack stores cost the legacy
         model's 33.5M-weight dense layer ~190 us per update)."""
-        if self.routes is None or not tune("opt_tiles", True):
+        if self.routes is None or not tune("opt_tiles"):
             return a
         span = a.lo + a.n - (a.lo & ~3)
         flat = cdiv(cdiv(span, 4), 256)
@@ -506,7 +507,7 @@ class BatchPlan(GeometryMixin):
         # their own comm stream) and captured with the rest of the step into ONE HIP graph.
         red = ex.reducer
         self.comm_in_graph = (self.training and red is not None and getattr(red, "capturable", False)
-                              and red.active and tune("comm_capture", True))
+                              and red.active and tune("comm_capture"))
         # tune comm_fork=0: the captured all-reduces stay on the main stream (a linear graph:
         # no cross-queue edges, whose graph-launch cost is several us each, but no overlap)
         # (default: fork only when there is more than one bucket to overlap; set in _comm_launches)
@@ -515,7 +516,7 @@ class BatchPlan(GeometryMixin):
         # ... and each bucket's optimizer update follows its all-reduce on the comm stream (the
         # 1/size average folded in), so the dense bucket's update overlaps the conv backward and
         # only the last bucket's (small) update is on the step's tail
-        self.optim_on_comm = self.comm_in_graph and tune("dp_optim_on_comm", True)
+        self.optim_on_comm = self.comm_in_graph and tune("dp_optim_on_comm")
         z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=dev)
         self.xb = z(bs, ex.in_H * ex.in_W * ex.in_Cs)
         self.yb = z(bs, ex.plan.head.N, dt=torch.float32)
@@ -534,11 +535,11 @@ class BatchPlan(GeometryMixin):
             if K.dense_big(g.NT, g.KS):
                 # large weights: ~256 workgroups (one per CU) of >= 8 k-steps; each owns
                 # 128 rows x 8 n-tiles, so every weight byte streams from HBM once
-                splits = max(1, min(cdiv(tune("dense_big_wgs", 256), K.dense_groups(bs, g.NT, g.KS)),
-                                    cdiv(g.KS, tune("dense_big_minks", 8))))
+                splits = max(1, min(cdiv(tune("dense_big_wgs"), K.dense_groups(bs, g.NT, g.KS)),
+                                    cdiv(g.KS, tune("dense_big_minks"))))
             else:
                 # ~2048 16x16-tile waves: latency-bound small layers want parallelism
-                splits = max(1, min(g.KS, tune("dense_waves", 2048) // max(1, K.dense_groups(bs, g.NT, g.KS))))
+                splits = max(1, min(g.KS, tune("dense_waves") // max(1, K.dense_groups(bs, g.NT, g.KS))))
             kps = cdiv(g.KS, splits)
             splits = cdiv(g.KS, kps)
             self.dense_splits.append((splits, kps))
@@ -599,7 +600,7 @@ class BatchPlan(GeometryMixin):
         bt.seed, bt.stream_id = ex.seed, stream
         # write-through gradient stores (16-byte sc1; byte offsets < 2 GB)
         dyb = self.conv_dy[g.i] if src.kind == "conv" else self.dense_dh[g.j]
-        bt.wt = int(bool(int(tune("wt", 7)) & 2) and dyb.numel() * 2 < (1 << 31))
+        bt.wt = int(bool(int(tune("wt")) & 2) and dyb.numel() * 2 < (1 << 31))
         return bt
 
     # ---------------------------------------------------------------- step program: forward
@@ -644,13 +645,13 @@ class BatchPlan(GeometryMixin):
         # one prologue launch: gather + the previous update's weight re-pack (training: always,
         # except with per-bucket optimizers that pack themselves; eval/predict: only if an
         # optimizer ran since the last pack) + the step bookkeeping
-        stack = self._conv_stack_args(training) if tune("conv_stack", True) else None
+        stack = self._conv_stack_args(training) if tune("conv_stack") else None
         # Prologue-free step (conv stack + a hidden dense layer + optimizer-written packs): the
         # stack reads its images straight from the dataset through the cursor and permutation
         # (recording each image's dataset row for the first layer's wgrad and the head's
         # targets), the optimizer keeps the bf16 packs current, and the first dense launch runs
         # the step bookkeeping -- the step has no prologue launch
-        self.pro_free = bool(stack is not None and ex.denses and ex.routes_ok and tune("pro_free", True))
+        self.pro_free = bool(stack is not None and ex.denses and ex.routes_ok and tune("pro_free"))
         if self.pro_free:
             self.srcidx = torch.zeros(max(bs, 1), dtype=torch.int32, device=ex.device)
             stack.from_data, stack.training, stack.step_inc = 1, int(training), int(training)
@@ -660,7 +661,7 @@ class BatchPlan(GeometryMixin):
         pa.gather_gx = 1 if ga.skip_x else K.gather_gx(ga.R)
         pa.gather_blocks = pa.gather_gx * bs
         pa.pack_mode = 1 if training else 2
-        pro_dbg = tune("pro_dbg", 0)          # timing ablation only: 1 no re-pack, 2 no gather
+        pro_dbg = tune("pro_dbg")          # timing ablation only: 1 no re-pack, 2 no gather
         if pro_dbg == 1:
             pa.pack_mode = 0
         elif pro_dbg == 2:
@@ -731,7 +732,7 @@ class BatchPlan(GeometryMixin):
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head", True)):
+                    and tune("fuse_head")):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
@@ -761,7 +762,7 @@ class BatchPlan(GeometryMixin):
         if head_epi is not None:
             h.epi = head_epi
         h.training = int(training)
-        h.generic = int(tune("head_generic", False))
+        h.generic = int(tune("head_generic"))
         h.inv_bs = 1.0 / self.bs
         h.st = ex.state.data_ptr()
         if self.probs is not None:
@@ -807,8 +808,8 @@ class BatchPlan(GeometryMixin):
         # the legacy model's 33.5M-weight Dense(512)): their update moves ~1 GB either way, and
         # fusing it saves the gradient's own write + re-read (legacy 1.269 -> 1.238 ms/step,
         # profiles/r4c_ab_legacy.txt); "1" = every one-split layer; "0" = off
-        dense_opt = str(tune("dense_opt", "auto")).lower()
-        self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim", True)
+        dense_opt = str(tune("dense_opt")).lower()
+        self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim")
                              and dense_opt not in ("0", "false", "off", "no")
                              and ex.opt.kind not in STANDALONE_KINDS)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
@@ -822,7 +823,7 @@ class BatchPlan(GeometryMixin):
         direct_ptr = (store.grad.data_ptr() + 4 * sp.offset) if direct else None
         # dense_bwd.hip kernels (per-wave pipelined wgrad, vectorised dX epilogue) where the
         # 8-element alignment they assume holds; the generic wgrad / split-K path otherwise
-        bwd2 = tune("dense_bwd2", True) and g.src.width % 8 == 0 and g.Ns % 8 == 0
+        bwd2 = tune("dense_bwd2") and g.src.width % 8 == 0 and g.Ns % 8 == 0
         if not bwd2:
             w = self._wgrad_args(xin, g.src.width, self.dense_dh[g.j], g.Ns, g.N, ds.dense.use_bias, direct_ptr)
             return w, (lambda s, a=w.a, c=w.cfg: K.wgrad(a, *c, s)), False, False
@@ -847,7 +848,7 @@ class BatchPlan(GeometryMixin):
             # legacy Dense(512): 1.107 -> 1.097 ms/step, with dw_order 1.101 -> 1.086,
             # profiles/r6_dense_wgrad_ab.txt) -- this layer's gradient is then not
             # readable through the store (store.view(..., grad=True)); opt_nograd=0 keeps it
-            wa.opt_nograd = int(tune("opt_nograd", True))
+            wa.opt_nograd = int(tune("opt_nograd"))
             if ex.routes_ok:
                 wa.pk_fwd, wa.pk_NT = g.pack_fwd, g.NT
                 wa.pk_bwd, wa.pk_NTb = (g.pack_bwd, g.NTb) if g.KSb else (-1, 0)
@@ -856,8 +857,8 @@ class BatchPlan(GeometryMixin):
                 wa.opt_b = store.spec(ds.dense, "bias").offset
         # grid order 1: the n groups of one feature group consecutive (whole rows of the
         # weight / optimizer-state arrays per resident wave of workgroups; legacy -5 us)
-        dw_order = int(tune("dw_order", 1))
-        dw_late = bool(tune("dw_late", True))     # 4 waves / SIMD: legacy 1.070 -> 1.059 ms
+        dw_order = int(tune("dw_order"))
+        dw_late = bool(tune("dw_late"))     # 4 waves / SIMD: legacy 1.070 -> 1.059 ms
         wl = lambda s, a=wa, c=w.cfg, o=dw_order, l=dw_late: K.dense_wgrad(a, *c, s, o, l)
         return w, wl, fused_opt, True
 
@@ -894,7 +895,7 @@ class BatchPlan(GeometryMixin):
         wname, dname = "wgrad_dense%d" % g.j, "dense_dx%d" % g.j
         da, ntc, dl = self._dense_dx(g, bwd2) if g.KSb else (None, 0, None)
         dx_first = da is not None and fused_opt
-        dual = da is not None and not fused_opt and tune("dual_dense", True)
+        dual = da is not None and not fused_opt and tune("dual_dense")
         if dx_first:
             # the wgrad's fused optimizer rewrites this layer's backward pack: its dX (that
             # pack's reader) runs first, as a launch of its own on the same stream -- never
@@ -948,8 +949,8 @@ class BatchPlan(GeometryMixin):
         a.mode, a.flat_out = 1, 0
         a.st = ex.state.data_ptr()
         a.bt = self._bt_for(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
-        a.tm = tune("dgrad_tm%d" % g.i, 0)      # co-scheduled dgrad m-tiles per wave per pass
-        a.dbg = tune("dgrad_dbg", 0)            # A/B switches (ConvMMArgs::dbg; exact ones only)
+        a.tm = tune("dgrad_tm", layer=g.i)      # co-scheduled dgrad m-tiles per wave per pass
+        a.dbg = tune("dgrad_dbg")            # A/B switches (ConvMMArgs::dbg; exact ones only)
         return a
 
     def _build_conv_bwd(self, g, cs):
@@ -967,7 +968,7 @@ class BatchPlan(GeometryMixin):
                 w.a.xidx, w.a.xst = self.srcidx.data_ptr(), ex.state.data_ptr()
             wl = lambda s, a=w.a, c=w.cfg: K.wgrad_halo(a, *c, s)
         ca = self._dgrad_args(g) if g.i > 0 else None
-        dual = (ca is not None and tune("dual_halo", True)
+        dual = (ca is not None and tune("dual_halo")
                 and not wide and not self._wide(ca.Cs_in, ca.KS, g.NTd))
         dname = "dgrad_conv%d" % g.i
         if dual:
@@ -1039,12 +1040,12 @@ class BatchPlan(GeometryMixin):
         # single stream, no all-reduce to overlap: ONE reduction launch at the end of the
         # backward (each launch boundary costs ~5 us here), if the descriptors fit a table
         ndesc = sum(len(grp.descs) for grp in self.red_groups)
-        one = ndesc <= tune("red_desc_max", 16)       # (RedTable capacity, MAX_RED)
+        one = ndesc <= tune("red_desc_max")       # (RedTable capacity, MAX_RED)
         limit = 1 << 62 if one else int(os.environ.get("INTML_BUCKET_BYTES", 1 << 20))
         # ... with the optimizer fused into it when its table covers every parameter
         covered = sum(d.numel for grp in self.red_groups for d in grp.descs)
         covered += sum(n for _, n in self.dense_fused_opt)
-        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim", True)
+        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim")
         if not self.optim_fused:
             # the step ends with a full optimizer launch after all: the dense layers keep
             # writing their gradient in place, but leave the update -- and the bf16 pack
@@ -1080,8 +1081,8 @@ class BatchPlan(GeometryMixin):
         # one rank (the N = 1 data-parallel step): nothing to exchange -- the early groups
         # are reduced AND updated in that launch, as on a single GPU (xchg_p1: keep the
         # exchange structure, to measure its fixed cost)
-        solo = reducer.size == 1 and getattr(reducer, "xgmi", None) is not None and not tune("xchg_p1", False)
-        if not (len(bucket_groups) == 1 and self.comm_in_graph and tune("dp_early", True)):
+        solo = reducer.size == 1 and getattr(reducer, "xgmi", None) is not None and not tune("xchg_p1")
+        if not (len(bucket_groups) == 1 and self.comm_in_graph and tune("dp_early")):
             return bucket_groups, []
         dp_early = self._early_groups(grad_only=not solo)
         if solo and self.early_red:
@@ -1093,7 +1094,7 @@ class BatchPlan(GeometryMixin):
         # ... and (exchange) the NEXT dual launch finishes that range's all-reduce and
         # applies its update in extra workgroups of its own, so the fused kernel after
         # the backward is left with the conv layers only
-        if tune("xgmi_push", True) and not solo:
+        if tune("xgmi_push") and not solo:
             # every early table would start at block-flag slot 0 (fbase) and the pushed /
             # exchanged range is ONE span: _early_groups caps them at one dual launch
             assert len(self.early_red) <= 1, "exchange: one early table per step (flag slots, pushed range)"
@@ -1108,9 +1109,9 @@ class BatchPlan(GeometryMixin):
         x = self.xchg
         # (xchg_at=end: the exchange as a launch of its own after the end-of-
         # backward reduction instead of extra workgroups of the next dual launch)
-        at_end = tune("xchg_at", "dual") == "end"
+        at_end = tune("xchg_at") == "end"
         nxt = (("end" if at_end else self._xchg_launch(nm, elo, ehi))
-               if tune("xgmi_xchg", True) else None)
+               if tune("xgmi_xchg") else None)
         # split exchange (default): the owner half (wait for the senders, sum,
         # push the sums back: mode 4) in extra workgroups of the next dual launch,
         # covering only the table blocks this rank owns part of (none at one
@@ -1118,7 +1119,7 @@ class BatchPlan(GeometryMixin):
         # beside the end-of-backward table in ONE launch -- every wait is on a
         # flag raised in an EARLIER launch, and no conv-sized workgroup holds a
         # CU slot for the update (xchg_split=0: both halves in the dual launch)
-        if nxt and not at_end and tune("xchg_split", True):
+        if nxt and not at_end and tune("xchg_split"):
             trip = reducer.exchange_args(elo, ehi, tab.nblocks, table=tab)
             if trip is not None:
                 x.early_push[nm] = trip[0]
@@ -1148,7 +1149,7 @@ class BatchPlan(GeometryMixin):
         the update -- with the early range exchanged inside the backward, the whole step's
         all-reduce + optimizer then runs in table launches and the fused kernel is not launched."""
         x = self.xchg
-        if xk is None or not tune("xgmi_xchg", True) or not (x.exchanged or not dp_early):
+        if xk is None or not tune("xgmi_xchg") or not (x.exchanged or not dp_early):
             return
         blo, bhi, btab = self.bucket_tables[xk]
         rlo, rhi = reducer.buckets[xk]
@@ -1169,7 +1170,7 @@ class BatchPlan(GeometryMixin):
         ex, K, x = self.ex, self.ex.K, self.xchg
         rccl_buckets = [k for k in range(nbuckets) if k != xk]
         # fork the comm stream only when an RCCL bucket has later backward work to overlap
-        fork = tune("comm_fork", "")
+        fork = tune("comm_fork")
         self.comm_fork = ((fork not in ("0", "false", "False")) if fork
                           else any(k < nbuckets - 1 for k in rccl_buckets))
         if self.comm_fork:
@@ -1212,7 +1213,7 @@ class BatchPlan(GeometryMixin):
         self.early_red = {}
         # (the extras choose the optimizer at run time among five kinds: the others' head and
         # dense groups stay in the end-of-step / per-bucket reduce_optim_kernel<KIND> launch)
-        if not tune("early_reduce", True) or self.ex.opt.kind in STANDALONE_KINDS:
+        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous
@@ -1276,7 +1277,7 @@ class BatchPlan(GeometryMixin):
         """Launch [lo, hi) on the streams ``stream_program`` assigns (concurrent chains that
         join main at the end)."""
         items = self.launches[lo:hi]
-        skip = tune("skip", "")          # timing ablation only (wrong results): "name/name"
+        skip = tune("skip")          # timing ablation only (wrong results): "name/name"
         if skip:
             drop = set(skip.split("/"))
             items = [it for it in items if it[0] not in drop]

@@ -19,7 +19,7 @@ import torch
 
 from ..ops import reference as R
 from ..ops.rng import dropout_keep
-from ..utils.env import tune
+from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .plan import Plan
 
@@ -33,7 +33,7 @@ class RefExecutor(Executor):
         self.m_schedule = 1.0
         self._acc = torch.zeros(3, dtype=torch.float64)
         self._last = (0.0, 0.0)
-        self.emulate_bf16 = bool(tune("ref_bf16", False))
+        self.emulate_bf16 = bool(tune("ref_bf16"))
 
     # ------------------------------------------------------------------------------ data
     def upload(self, x, y, w=None):

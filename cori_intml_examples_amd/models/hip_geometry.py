@@ -9,7 +9,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ..utils.env import tune
+from ..utils.tune import tune
 from . import lds_layout
 from .step_program import dropout_pair
 
@@ -63,7 +63,7 @@ class GeometryMixin:
                 return None
 
         # row bands per image: enough workgroups to cover the 256 CUs at small batches
-        want = tune("stack_splits", 0) or cdiv(256, self.bs)
+        want = tune("stack_splits") or cdiv(256, self.bs)
         splits = max(1, min(K.MAX_STACK_SPLIT, want))
         while splits > 1 and self._stack_rows(convs, splits) is None:
             splits -= 1
@@ -80,13 +80,13 @@ class GeometryMixin:
         a.B, a.n, a.seed, a.st = self.bs, n, ex.seed, ex.state.data_ptr()
         a.off_w, (a.off_codes, a.off_codes2), a.lds_bytes = off_w, off_codes, lds
         a.off_bias = off_bias
-        a.dbg = tune("stack_dbg", 0)
-        a.k16 = int(tune("stack_k16", True))
-        a.wt = int(bool(int(tune("wt", 7)) & 1))      # write-through stage outputs / codes
+        a.dbg = tune("stack_dbg")
+        a.k16 = int(tune("stack_k16"))
+        a.wt = int(bool(int(tune("wt")) & 1))      # write-through stage outputs / codes
         # a layer-signature-specialised instance when one matches (conv_stack.hip kStackSigs):
         # 1 = 12-wave instances, 2 (default: +0.4 %, profiles/r5e_ab.txt) = a 16-wave instance first
         # where one exists, 0 = generic
-        a.spec = int(tune("stack_spec", 2))
+        a.spec = int(tune("stack_spec"))
         a.set_buf_offsets(off_b0, off_b1)
         a.splits = splits
         for l in range(n):
@@ -193,7 +193,7 @@ class GeometryMixin:
         for g in convs:
             Wi = g.Wo + g.KW - 1
             rows_path = g.pool and g.Wp % 4 == 0 and g.KH == 3 and g.KW == 3
-            if tune("lds_layout", True):
+            if tune("lds_layout"):
                 out.append(lds_layout.stack_layout(g.Cs_in, Wi, g.Wo, bool(rows_path), g.KS))
             else:
                 out.append((g.Cs_in, Wi))
@@ -227,13 +227,13 @@ class GeometryMixin:
             if K.conv_tile_lds_bytes(ntc) > 150 * 1024:
                 raise NotImplementedError("conv tile LDS")
             big = False
-            if tune("conv_glds", True):
+            if tune("conv_glds"):
                 a.zero = self._zero_buf().data_ptr()
                 # 256-row / 8-wave blocks (all 256 channels of a wide layer per block: NTC 16)
                 # when the grid keeps >= 512 blocks: half the L2 traffic per MFMA
-                if tune("conv_big", True) and a.in_code == 0:
+                if tune("conv_big") and a.in_code == 0:
                     for nb in ((16, 8) if NT >= 16 else (8,)):
-                        if NT >= nb and K.conv_tile_big_blocks(a, nb) >= tune("conv_big_min", 512):
+                        if NT >= nb and K.conv_tile_big_blocks(a, nb) >= tune("conv_big_min"):
                             ntc, big = nb, True
                             break
                 # stride-1 layers (and the parity classes of a strided dgrad) with whole-row
@@ -242,27 +242,27 @@ class GeometryMixin:
                 # (8 n-tiles per block: 116 VGPRs and 80 KB of LDS -- two blocks per CU; the
                 # all-256-channel NTC 16 block, one per CU, measured no faster than conv_gl;
                 # a 64-channel strided dgrad takes 4-tile blocks)
-                hs = int(tune("conv_hs_ntc", 8))
+                hs = int(tune("conv_hs_ntc"))
                 if NT < hs:
                     hs = 4 if NT >= 4 and a.in_dil > 1 else 0
-                dil_ok = a.in_dil <= 1 or tune("conv_hs_dil", True)
-                if tune("conv_hs", True) and hs and dil_ok:
+                dil_ok = a.in_dil <= 1 or tune("conv_hs_dil")
+                if tune("conv_hs") and hs and dil_ok:
                     # 16 waves / 512-row blocks where the shape tiles into them (half the weight
                     # DMA per MFMA), else 8 waves / 256 rows
-                    for wv in ((16, 8) if tune("conv_hs_wv", 8) == 16 else (8,)):
+                    for wv in ((16, 8) if tune("conv_hs_wv") == 16 else (8,)):
                         if K.conv_hs_ok(a, hs, wv):
                             # (1: the n-blocks of a row block adjacent on one XCD -- legacy conv3
                             # forward 103.0 -> 101.6 us, profiles/r6_conv_hs_order_ab.txt)
-                            o = int(tune("conv_hs_order", 1))
+                            o = int(tune("conv_hs_order"))
                             return lambda s, a=a, n=hs, w=wv, o=o: K.conv_hs(a, n, s, w, o)
-            nbuf = int(tune("conv_gl_nbuf", 3))
+            nbuf = int(tune("conv_gl_nbuf"))
             return lambda s, a=a, n=ntc, b=big, nb=nbuf: K.conv_tile(a, n, s, b, nb)
         ntc = self._halo_cfg(a, NT, pool)
         if not a.tm:
             # 4-tile blocks: two m-tiles per wave per pass -- half the epilogue staging LDS, four
             # workgroups per CU instead of three (legacy first conv 37.7 -> 26.8 us,
             # profiles/r6_halo_tm_ab.txt); halo_tm=4 restores the four-tile pass
-            a.tm = int(tune("halo_tm", 2))
+            a.tm = int(tune("halo_tm"))
         return lambda s, a=a, n=ntc: K.conv_halo(a, n, s)
 
     def _dense_dual(self, wa, cfg, da, s):
@@ -281,12 +281,12 @@ class GeometryMixin:
         kw = {}
         if early is not None:   # this launch also carries an early bucket's reduction (+ optimizer)
             kw.update(rt=early[0], ro=self._early_ro(early), rgrad=ex.store.grad.data_ptr(),
-                      rfirst=int(tune("early_rfirst", 0)))   # (0: last in the grid, 1: first, 2: interleaved)
+                      rfirst=int(tune("early_rfirst")))   # (0: last in the grid, 1: first, 2: interleaved)
             if xp is not None:
                 kw["xp"] = xp
         elif xe is not None:
             kw.update(rt=xe[0], ro=ex._optim_args(False, defer_pack=True), rgrad=ex.store.grad.data_ptr(), xp=xe[1],
-                      rfirst=int(tune("xchg_rfirst", 1)))   # (dispatched first: their waits overlap the convs)
+                      rfirst=int(tune("xchg_rfirst")))   # (dispatched first: their waits overlap the convs)
         ok = K.dual_halo(a, ntc, wa, cfg[0], cfg[1], cfg[2], s, **kw)
         if not ok:   # unsupported combination
             K.wgrad_halo(wa, cfg[0], cfg[1], cfg[2], s)
@@ -306,11 +306,11 @@ class GeometryMixin:
         largest block that still leaves >= `want` workgroups (a dgrad co-scheduled with its
         wgrad in one launch wants fewer, longer workgroups: each stages the whole weight
         slice, and the launch should fit the CUs in one wave)."""
-        want = tune("dgrad_min_wgs", 256) if dual else tune("halo_min_wgs", 512)
+        want = tune("dgrad_min_wgs") if dual else tune("halo_min_wgs")
         KS = a.KS
         # co-scheduled dgrad: one n-tile per workgroup and whole-image blocks (measured on the
         # RPV stack: each workgroup stages half the weights, the launch fits the CUs in one wave)
-        ntc = tune("dgrad_ntc", 1) if dual else 8
+        ntc = tune("dgrad_ntc") if dual else 8
         while ntc > 1 and (ntc > NT or KS * ntc > 64):
             ntc //= 2
         if KS * ntc > 96:
@@ -318,7 +318,7 @@ class GeometryMixin:
         Wo, Ho = a.Wo, a.Ho
         W_in = (Wo - 1) * a.stride + a.KW
         step = 2 if pool else 1
-        a.kpipe = int(tune("conv_kpipe", True))
+        a.kpipe = int(tune("conv_kpipe"))
         gy = cdiv(NT, ntc)
 
         def rows(XP):
@@ -339,7 +339,7 @@ class GeometryMixin:
             return step
 
         best = rows(a.Cs_in)
-        if tune("lds_layout", True) and a.Cs_in % 8 == 0:
+        if tune("lds_layout") and a.Cs_in % 8 == 0:
             # the bank-conflict-free pixel stride, unless its larger halo costs block rows
             xp = lds_layout.conv_layout(a.Cs_in, W_in, Wo, bool(pool), a.KH, a.KW)
             if xp != a.Cs_in and rows(xp) >= best:
@@ -391,8 +391,8 @@ class GeometryMixin:
         """Tiled wgrad for wide convs: 128(k) x ntc*16(n) tiles, split-K over pixel ranges."""
         a = self._conv_wgrad_base(xin, g)
         ntc = 8 if g.NT > 4 else (4 if g.NT > 2 else 2)
-        ntc = min(ntc, tune("wgrad_tile_ntc", ntc))
-        if tune("conv_glds", True):
+        ntc = min(ntc, tune("wgrad_tile_ntc") or ntc)
+        if tune("conv_glds"):
             a.zero = self._zero_buf().data_ptr()
         P = a.P
         tiles = cdiv(a.Ktiles * 16, 128) * cdiv(g.NT, ntc)
@@ -402,10 +402,10 @@ class GeometryMixin:
         # waves runs a second wave for them and nearly doubles the launch (legacy conv3 wgrad
         # 113 us at 486 workgroups, 185 us at 522; profiles/r6_wgrad_splits_ab.txt).  The
         # reduction's slab bytes halve with it (end-of-step reduce + Adam 54 -> 35 us).
-        slots = tune("wgrad_tile_fill", 1) * self._cu_count() * 2
-        wgs = tune("wgrad_tile_wgs", 0)
+        slots = tune("wgrad_tile_fill") * self._cu_count() * 2
+        wgs = tune("wgrad_tile_wgs")
         S = max(1, min(cdiv(wgs, tiles) if wgs else max(1, slots // tiles),
-                       (tune("wgrad_tile_slab_mb", 64) << 20) // per_split_bytes, cdiv(P, 256)))
+                       (tune("wgrad_tile_slab_mb") << 20) // per_split_bytes, cdiv(P, 256)))
         a.px_per_split = cdiv(cdiv(P, S), 64) * 64
         S = cdiv(P, a.px_per_split)
         return Wgrad(a, (ntc, None), S, *self._wgrad_slabs(a, S, bias))
@@ -423,8 +423,8 @@ class GeometryMixin:
         # rows (measured best at batch 128 for the RPV and MNIST stacks; RPV first layer
         # 512 px = 8 rows: +0.2-0.5 %, profiles/r4m_ab_rpv.txt, r4n_ab_rpv.txt), bounded LDS
         W_in = (g.Wo - 1) * g.stride + g.KW
-        px = tune("wgrad_block_px%d" % g.i, tune("wgrad_block_px", 512 if g.i == 0 else 256))
-        R = max(1, min(g.Ho, px // max(1, g.Wo), tune("wgrad_max_rows%d" % g.i, tune("wgrad_max_rows", 8))))
+        px = tune("wgrad_block_px", layer=g.i)
+        R = max(1, min(g.Ho, px // max(1, g.Wo), tune("wgrad_max_rows", layer=g.i)))
         # prefer the largest R whose block staging fits the kernel's register pipeline
         # (<= 4 X-halo and 4 dY chunks per thread, wgrad_halo_body.h WH_PX / WH_PY)
         cpp = g.Cs_in // (4 if g.Cs_in == 4 else 8)
@@ -435,12 +435,12 @@ class GeometryMixin:
             nch_y = cdiv(r * g.Wo, 32) * 32 * NTT * 2
             return nch_x <= 1024 and nch_y <= 1024
         for r in range(R, 0, -1):
-            if fits(r) or not tune("wgrad_fit%d" % g.i, True):
+            if fits(r) or not tune("wgrad_fit", layer=g.i):
                 R = r
                 break
         # LDS layout from the bank-conflict model (pixel / row strides of the X halo, dY rows)
-        a.kperm = int(tune("wgrad_perm", True)) | (0 if tune("wgrad_fast", True) else 2)
-        if tune("lds_layout", True):
+        a.kperm = int(tune("wgrad_perm")) | (0 if tune("wgrad_fast") else 2)
+        if tune("lds_layout"):
             a.xpix, a.xrow, a.dyld = lds_layout.wgrad_layout(g.Cs_in, W_in, g.Wo, NTT, g.KH, g.KW, g.stride,
                                                              a.Ktiles, bool(a.kperm & 1))
         XP, XR = (a.xpix or g.Cs_in), (a.xrow or W_in)
@@ -450,11 +450,10 @@ class GeometryMixin:
         nblocks = bs * cdiv(g.Ho, R)
         groups = cdiv(NT, NTT) * cdiv(a.Ktiles, MT)
         per_split_bytes = a.Ktiles * 16 * NT * 16 * 4
-        s_budget = max(1, (tune("wgrad_slab_mb", 8) << 20) // per_split_bytes)
+        s_budget = max(1, (tune("wgrad_slab_mb") << 20) // per_split_bytes)
         # splits: one round of resident workgroups (occupancy x CUs), not more -- the
         # latency-bound blocks then all stream concurrently instead of a second thin round
-        cap = (tune("wgrad_splits%d" % g.i, 0) or tune("wgrad_splits", 0) or K.wgrad_halo_resident(a, MT, NTT, bool(bias))
-               or 768)
+        cap = tune("wgrad_splits", layer=g.i) or K.wgrad_halo_resident(a, MT, NTT, bool(bias)) or 768
         S = max(1, min(nblocks, s_budget, max(1, cap // groups)))
         bps = cdiv(nblocks, S)
         S = cdiv(nblocks, bps)
@@ -464,12 +463,12 @@ class GeometryMixin:
             raise NotImplementedError("wgrad halo stage too large (%d bytes)" % lds)
         slab, bslab = self._wgrad_slabs(a, S, bias)
         # write-through slabs (16-byte sc1 stores, byte offsets < 2 GB)
-        a.wt = int(bool(int(tune("wt", 7)) & 4) and slab.numel() * 4 < (1 << 31))
+        a.wt = int(bool(int(tune("wt")) & 4) and slab.numel() * 4 < (1 << 31))
         # layer-signature instances (geometry fixed at compile time, csrc/kernels/wgrad_sig.h)
         # where one matches; wgrad_spec=0: always the generic kernels (A/B, bit-identity tests).
         # The split count above is sized by the GENERIC instance's residency either way, so the
         # slab layout and the reduction order do not depend on this switch.
-        a.spec = int(tune("wgrad_spec", 1))
+        a.spec = int(tune("wgrad_spec"))
         return Wgrad(a, (MT, NTT), S, slab, bslab)
 
     def _wgrad_args(self, xin, width, dy, Cs_dy, N, bias, direct=None):
@@ -504,12 +503,12 @@ class GeometryMixin:
         a = self._wgrad_base(xin, 1, 1, width, 1, 1, None, dh, Ns, NT)
         # (at most 4 n-tiles: twice the workgroups of 8 -- RPV +0.6 %, MNIST +1.2 %,
         # profiles/r4s_ab_rpv.txt, r4s_ab_mnist.txt)
-        ntt = _pow2_le(NT, min(8, tune("dw_ntt", 4)))
+        ntt = _pow2_le(NT, min(8, tune("dw_ntt")))
         kg = 2
         groups = cdiv(a.Ktiles, kg) * cdiv(NT, ntt)
         per_split_bytes = a.Ktiles * 16 * NT * 16 * 4
-        s_budget = max(1, (tune("dw_slab_mb", 8) << 20) // per_split_bytes)
-        S = 1 if direct else max(1, min(s_budget, cdiv(tune("dw_min_wgs", 256), groups),
+        s_budget = max(1, (tune("dw_slab_mb") << 20) // per_split_bytes)
+        S = 1 if direct else max(1, min(s_budget, cdiv(tune("dw_min_wgs"), groups),
                                         cdiv(bs, 128)))
         pps = cdiv(cdiv(bs, S), 32) * 32
         S = cdiv(bs, pps)
@@ -520,11 +519,12 @@ class GeometryMixin:
     def _dense_dx_ntc(a):
         """n-tiles per wave of dense_dx_kernel: the most A-fragment reuse that still leaves
         >= tune dx_min_wgs workgroups (4 waves x 16 rows each)."""
-        if tune("dx_ntc", 0):
-            return tune("dx_ntc", 0)
+        ntc = tune("dx_ntc")
+        if ntc:
+            return ntc
         # (256: the RPV dense dX at 2 n-tiles per wave, 256 workgroups -- 3 us faster than
         # 512 one-tile workgroups, profiles/r4p_ab_rpv.txt)
-        want = tune("dx_min_wgs", 256)
+        want = tune("dx_min_wgs")
         for ntc in (4, 2):
             if cdiv(a.M, 64) * cdiv(a.NT, ntc) >= want:
                 return ntc

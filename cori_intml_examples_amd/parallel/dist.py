@@ -27,7 +27,7 @@ import torch.distributed as tdist
 
 from . import state as S
 from ..optim.optimizers import STANDALONE_KINDS
-from ..utils.env import tune
+from ..utils.tune import tune
 
 
 class DataParallelDivergence(RuntimeError):
@@ -389,7 +389,7 @@ def adaptive_bucket_bytes(groups: Sequence[Tuple[int, int]], size: int = 1) -> i
         # (opt-in: on the round-5 kernels the forked two-bucket step measured 135.7 us/step at
         # N = 1 against 103.0 for one bucket -- profiles/r5f_ab.txt; bench.py's probe times it
         # on the real fabric at N > 1 and keeps whichever plane is faster)
-        if size > 1 and total > (1 << 20) and tune("dp_overlap", False):
+        if size > 1 and total > (1 << 20) and tune("dp_overlap"):
             return 1 << 20
         return total + 1
     return max(16 << 20, total // 4)
@@ -628,7 +628,7 @@ class NativeGradReducer:
             # in the device count)
             keys = allgather(device_key(self.device))
             shared = len(set(keys)) < len(keys) or _st().local_size > max(1, torch.cuda.device_count())
-            max_wg = int(tune("xgmi_shared_wg", 8)) if shared else None
+            max_wg = int(tune("xgmi_shared_wg")) if shared else None
             # (shared goes into create(): the admission self-test runs the exchange geometry --
             # looping or one workgroup per block -- that training will use)
             self.xgmi = X.create(self.rank, self.size, n, self.device, allgather, max_wg=max_wg, shared=shared)

@@ -31,7 +31,7 @@ from typing import Callable, List, Optional
 import torch
 
 from ..ops.hip import kernels
-from ..utils.env import tune
+from ..utils.tune import tune
 
 _FLAG_WORDS = 256 * 8          # XGMI_MAX_WG x XGMI_MAX_RANKS
 XCHG_MAX_BLOCKS = 4096         # early-bucket exchange: table blocks with flags (x XGMI_MAX_RANKS)
@@ -96,7 +96,7 @@ class XgmiAllreduce:
         err = None
         torch.cuda.set_device(device)
         try:
-            self.buf = K.xgmi_alloc_uncached(self.nbytes, tune("xgmi_mem", "uncached") == "finegrained")
+            self.buf = K.xgmi_alloc_uncached(self.nbytes, tune("xgmi_mem") == "finegrained")
             handle = K.xgmi_ipc_handle(self.buf)
         except Exception as e:        # noqa: BLE001 -- reported through the vote below
             err, handle = "setup: %s" % e, b""
@@ -127,7 +127,7 @@ class XgmiAllreduce:
         # 1 (default): system-scope release + acquire around every flag (the HIP memory model;
         # the fence-free form 3 -- sc1 payload loads only -- stays opt-in until a
         # multi-GPU run shows parity); 2: agent-scope acquire; 0: none (xgmi.hip header)
-        a.fence = int(tune("xgmi_fence", 1))
+        a.fence = int(tune("xgmi_fence"))
         if err is None:
             for j, b in enumerate(bases):
                 a.set_peer(j, b + self.off_in, b + self.off_out, b + self.off_f1, b + self.off_f2, b + self.off_ab)
@@ -169,13 +169,13 @@ class XgmiAllreduce:
             # ranks sharing a GPU: a few workgroups looping over the blocks (one per block would
             # let one rank's spinning workgroups fill the CUs its peers' launches need);
             # xchg_nx (A/B): as many looping workgroups on separate GPUs too
-            x.nx = int(tune("xgmi_xchg_wg", 4)) if self.shared else int(tune("xchg_nx", 0))
+            x.nx = int(tune("xgmi_xchg_wg")) if self.shared else int(tune("xchg_nx"))
             x.nx = x.nx if mode >= 2 else 0
             if mode == 4:
                 x.b_lo, x.b_hi = blocks if blocks is not None else (0, nblk)
                 if x.nx:
                     x.nx = min(x.nx, max(1, x.b_hi - x.b_lo))
-            x.p1 = int(tune("xchg_p1", False))
+            x.p1 = int(tune("xchg_p1"))
             x.fence = 3 if self.args.fence == 3 else 1    # the exchange: release/acquire or none
         return x
 
@@ -235,7 +235,7 @@ class XgmiAllreduce:
                 bad = int((g != want).sum())
                 return "selftest: %d of %d elements wrong" % (bad, n)
         if stress is None:
-            stress = int(tune("xgmi_selftest_stress", 64))
+            stress = int(tune("xgmi_selftest_stress"))
         k = max(0, min(int(stress), (256 << 20) // max(1, 4 * n)))
         if k:
             gs = []

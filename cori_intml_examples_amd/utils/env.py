@@ -2,7 +2,8 @@
 
 Reference counterpart: the thread/env configuration of ``setup.sh:10-14`` and
 ``mlextras.configure_session`` (``mlextras.py:35-43``).  On MI355X the relevant
-knobs are device pinning (HIP_VISIBLE_DEVICES / LOCAL_RANK) and kernel switches.
+knobs are device pinning (HIP_VISIBLE_DEVICES / LOCAL_RANK); the kernel switches are the
+``INTML_TUNE`` table of ``utils/tune.py``.
 """
 from __future__ import annotations
 
@@ -19,35 +20,6 @@ def env_flag(name: str, default: bool) -> bool:
     if v is None:
         return default
     return v.strip().lower() not in ("0", "false", "no", "off", "")
-
-
-_TUNE = None
-
-
-def tune(key: str, default):
-    """Kernel-path / geometry tuning value ``key`` (executor switches and launch geometry):
-    ``default`` unless ``INTML_TUNE="key=value,key=value"`` overrides it (measurement sweeps
-    and A/B tests).  One knob for all of them instead of one environment variable each; the
-    value is parsed as the default's type (bool: 0/1/true/false)."""
-    global _TUNE
-    if _TUNE is None or _TUNE[0] != os.environ.get("INTML_TUNE", ""):
-        raw = os.environ.get("INTML_TUNE", "")
-        d = {}
-        for item in raw.split(","):
-            if "=" in item:
-                k, v = item.split("=", 1)
-                d[k.strip()] = v.strip()
-        _TUNE = (raw, d)
-    v = _TUNE[1].get(key)
-    if v is None:
-        return default
-    if isinstance(default, bool):
-        return v.lower() not in ("0", "false", "no", "off", "")
-    if isinstance(default, int):
-        return int(v)
-    if isinstance(default, float):
-        return float(v)
-    return v
 
 
 def default_device() -> torch.device:
