@@ -1,11 +1,18 @@
 """Step time of the RPV CNN ([16,32,64]/[128], 64x64x3, B=128) per optimizer on one GPU.
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
+                                        [--clipnorm C]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
 32-step graph replays, timed with device events after a settle run; the figure is the median of a
-model's rounds.  Prints one JSON line."""
+model's rounds.  Prints one JSON line.
+
+``--clipnorm C`` adds two more models per optimizer: ``<name>/unfused`` (the same optimizer built
+under ``INTML_TUNE=fuse_optim=0,early_reduce=0``: every slab reduction, then one optimizer launch
+-- the structure of a clipping step without the clip) and ``<name>/clipnorm`` (``clipnorm=C``: that
+structure plus the norm launch and the clipped load).  The difference between the two is the cost
+of gradient clipping."""
 import argparse
 import json
 import os
@@ -25,8 +32,41 @@ from cori_intml_examples_amd.utils import set_random_seed  # noqa: E402
 REPLAY = 32
 
 
-def make_opt(name):
-    return optim.Adam(amsgrad=True) if name == "AMSGrad" else getattr(optim, name)()
+UNFUSED = "fuse_optim=0,early_reduce=0"
+
+
+def make_opt(name, **kw):
+    return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
+
+
+def variants(names, clipnorm):
+    """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built)]"""
+    out = []
+    for nm in names:
+        out.append((nm, nm, {}, None))
+        if clipnorm is not None:
+            out.append((nm + "/unfused", nm, {}, UNFUSED))
+            out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None))
+    return out
+
+
+class tuned:
+    """INTML_TUNE set while a model's plan is built and captured (the knobs are read then)."""
+
+    def __init__(self, tv):
+        self.tv = tv
+
+    def __enter__(self):
+        self.old = os.environ.get("INTML_TUNE")
+        if self.tv is not None:
+            os.environ["INTML_TUNE"] = self.tv
+
+    def __exit__(self, *exc):
+        if self.tv is not None:
+            if self.old is None:
+                os.environ.pop("INTML_TUNE", None)
+            else:
+                os.environ["INTML_TUNE"] = self.old
 
 
 def main():
@@ -35,17 +75,21 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--clipnorm", type=float, default=None)
     a = ap.parse_args()
-    names = a.opts.split(",")
+    var = variants(a.opts.split(","), a.clipnorm)
+    names = [v[0] for v in var]
+    tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
     rs = np.random.RandomState(0)
     x = rs.rand(bs * REPLAY, 64, 64, 3).astype(np.float32)
     y = (rs.rand(bs * REPLAY) > 0.5).astype(np.float32)
     runs = {}
-    for nm in names:
+    for nm, oname, kw, tv in var:
         set_random_seed(1)
-        m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2, optimizer=make_opt(nm),
-                        lr=None, device="cuda:0")
+        with tuned(tv):
+            m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
+                            optimizer=make_opt(oname, **kw), lr=None, device="cuda:0")
         ex = m._executor
         d = ex.upload(x, y)
         perm = torch.arange(d.n, device=ex.device)
@@ -61,8 +105,9 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e3 / (n * REPLAY)      # us per step
 
-    for nm in names:                    # graph capture + clock settle
-        timed(nm, 4)
+    for nm in names:                    # plan + graph capture (under the model's knobs) + clock settle
+        with tuned(tunes[nm]):
+            timed(nm, 4)
     us = {nm: [] for nm in names}
     for _ in range(a.rounds):
         for nm in names:
@@ -71,6 +116,7 @@ def main():
     out = {"workload": "rpv_cnn 64x64x3 [16,32,64]/[128] B=%d" % bs, "steps_per_run": reps * REPLAY, "rounds": a.rounds,
            "us_per_step_median": {nm: round(statistics.median(v), 2) for nm, v in us.items()},
            "us_per_step_runs": {nm: [round(t, 2) for t in v] for nm, v in us.items()},
+           "optim_fused": {nm: bool(runs[nm][1]._plans[(bs, "train")].optim_fused) for nm in names},
            "launches": {nm: [it[0] for it in runs[nm][1]._plans[(bs, "train")].launches] for nm in names},
            "finite": {nm: bool(np.isfinite(runs[nm][0].store.master[:runs[nm][0].store.numel].sum().item()))
                       for nm in names}}

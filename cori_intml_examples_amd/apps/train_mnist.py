@@ -18,6 +18,8 @@ def build_parser():
     p.add_argument("--h3", type=int, default=16)
     p.add_argument("--dropout", type=float, default=0.2)
     p.add_argument("--optimizer", default="Adam")
+    p.add_argument("--clipnorm", type=float, default=None, help="Keras clipnorm: clip by the global gradient norm")
+    p.add_argument("--clipvalue", type=float, default=None, help="Keras clipvalue: clamp every gradient element")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--valid-frac", type=float, default=0.17)
@@ -31,11 +33,12 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     from ..parallel import hvd
     from .mnist import load_data
-    from .zoo import mnist_cnn
+    from .zoo import clipped_optimizer, mnist_cnn
     hvd.init()
     x, y, _, _ = load_data(n_train=a.n_train)
     x, y = x[:a.n_train], y[:a.n_train]
-    model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout, optimizer=a.optimizer, lr=a.lr,
+    model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout,
+                      optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
                       use_horovod=hvd.size() > 1)
     cbs = []
     if hvd.size() > 1:

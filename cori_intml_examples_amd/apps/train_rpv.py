@@ -38,6 +38,8 @@ def build_parser():
     p.add_argument("--lr", type=float, default=0.001)
     p.add_argument("--lr-scaling", choices=["linear"])
     p.add_argument("--optimizer", default="Adam")
+    p.add_argument("--clipnorm", type=float, default=None, help="Keras clipnorm: clip by the global gradient norm")
+    p.add_argument("--clipvalue", type=float, default=None, help="Keras clipvalue: clamp every gradient element")
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--n-epochs", type=int, default=4)
     p.add_argument("--fom", choices=["best", "last"])
@@ -59,6 +61,7 @@ def main(argv=None):
     from ..parallel import hvd
     from ..utils import set_random_seed
     from .rpv import build_model, load_dataset, train_model
+    from .zoo import clipped_optimizer
 
     st = hvd.init(shard_data=args.shard)
     print("[train_rpv] rank %d/%d (local %d) on %s, data plane %s" % (
@@ -82,7 +85,9 @@ def main(argv=None):
 
     lr = args.lr * hvd.size() if args.lr_scaling == "linear" else args.lr
     model = build_model(train_input.shape[1:], conv_sizes=[args.h1, args.h2, args.h3], fc_sizes=[args.h4],
-                        dropout=args.dropout, optimizer=args.optimizer, lr=lr, use_horovod=True)
+                        dropout=args.dropout,
+                        optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
+                        use_horovod=True)
     if hvd.rank() == 0:
         model.summary()
 

@@ -12,6 +12,17 @@ from ..models import Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model
 from .. import optim as optimizers
 
 
+def clipped_optimizer(optimizer: str, lr=None, clipnorm=None, clipvalue=None):
+    """The training CLIs' ``--clipnorm`` / ``--clipvalue``: the optimizer name itself when neither
+    is given (nothing changes), else the optimizer object built with them (Keras keywords)."""
+    kw = {k: v for k, v in (("clipnorm", clipnorm), ("clipvalue", clipvalue)) if v is not None}
+    if not kw:
+        return optimizer
+    if lr is not None:
+        kw["lr"] = lr
+    return type(optimizers.get(optimizer))(**kw)      # (any name optimizers.get knows: "Adam", "adam")
+
+
 def _opt(optimizer, lr, use_horovod):
     if isinstance(optimizer, str):
         opt = getattr(optimizers, optimizer)(lr=lr) if lr is not None else optimizers.get(optimizer)

@@ -70,6 +70,34 @@ struct OptimArgs {
   // third state buffer (AMSGrad's running maximum of v): read and written by the OPT_AMSGRAD
   // instances only
   float* s2 = nullptr;
+  // gradient clipping (the CLIP instances of the optimizer launch and grad_clip_apply_kernel;
+  // both off by default): clip != null -> every gradient element is first multiplied by
+  // clip[CLIP_FACTOR], the factor grad_sqnorm_kernel wrote for this step (Keras clipnorm);
+  // clipvalue > 0 -> then clamped to [-clipvalue, clipvalue] (Keras clipvalue)
+  const float* clip = nullptr;
+  float clipvalue = 0.f;
+};
+
+// Global-norm gradient clipping (clip.hip).  The clip state is a small buffer of its own
+// (StepState's layout is read by host-side offsets): [CLIP_NORM] the step's global gradient
+// norm, [CLIP_FACTOR] c / norm when norm >= c else 1, [CLIP_TICKET] the arrival counter of
+// grad_sqnorm_kernel's workgroups (as unsigned; zero between launches).
+#define CLIP_NORM 0
+#define CLIP_FACTOR 1
+#define CLIP_TICKET 2
+#define CLIP_STATE_WORDS 4
+#define CLIP_THREADS 256
+#define CLIP_VEC_PER_THREAD 8                                  // float4 loads per thread
+#define CLIP_CHUNK (CLIP_THREADS * 4 * CLIP_VEC_PER_THREAD)   // elements per workgroup
+struct ClipArgs {
+  float* g = nullptr;            // flat gradient, elements [0, n); 4-byte aligned is enough
+  int n = 0;
+  float clipnorm = 0.f;          // c (grad_sqnorm: factor = norm >= c ? c / norm : 1)
+  float clipvalue = 0.f;         // grad_clip_apply: > 0 -> clamp after the norm factor
+  int use_norm = 0;              // grad_clip_apply: multiply by state[CLIP_FACTOR]
+  float* partials = nullptr;     // grad_sqnorm: one partial sum per workgroup
+  int npartials = 0;             // capacity of partials (host check)
+  float* state = nullptr;        // CLIP_STATE_WORDS words
 };
 
 // Implicit-GEMM convolution / 1x1 "dense as conv" (fwd, dgrad, dense-dX).

@@ -57,6 +57,9 @@ void launch_reduce_optim(float* grad, const RedTable& tab, const OptimArgs& a, h
                          const XgmiPush* xp = nullptr);
 void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s);
 void launch_pack(const float* master, bf16* arena, const PackTable& tab, hipStream_t s);
+void launch_grad_sqnorm(const ClipArgs& a, hipStream_t s);
+void launch_grad_clip_apply(const ClipArgs& a, hipStream_t s);
+int clip_blocks(const ClipArgs& a);
 int xgmi_grid(const XgmiArgs& a);
 void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s);
 uintptr_t xgmi_alloc_uncached(size_t bytes, bool finegrained);
@@ -226,7 +229,7 @@ PYBIND11_MODULE(_kernels, m) {
       PTR(OptimArgs, p) PTR(OptimArgs, g) PTR(OptimArgs, s0) PTR(OptimArgs, s1) PTR(OptimArgs, s2) RW(OptimArgs, n) RW(OptimArgs, lo)
       PTR(OptimArgs, st) RW(OptimArgs, kind) RW(OptimArgs, beta1) RW(OptimArgs, beta2) RW(OptimArgs, eps)
       RW(OptimArgs, rho) RW(OptimArgs, momentum) RW(OptimArgs, nesterov) RW(OptimArgs, grad_scale)
-      RW(OptimArgs, grad_only)
+      RW(OptimArgs, grad_only) PTR(OptimArgs, clip) RW(OptimArgs, clipvalue)
       RW(OptimArgs, pack_only) RW(OptimArgs, defer_pack) PTR(OptimArgs, arena) PTR(OptimArgs, routes)
       RW(OptimArgs, nroutes) RW(OptimArgs, ntile) RW(OptimArgs, flat_blocks)
       .def("set_tile", [](OptimArgs& a, int i, int route, int b0) {
@@ -455,6 +458,21 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("slab_reduce", [](uintptr_t grad, int lo, int hi, const RedTable& t, uintptr_t s) {
     launch_slab_reduce(reinterpret_cast<float*>(grad), lo, hi, t, S(s)); check_last("slab_reduce"); });
   m.def("optim", [](const OptimArgs& a, const PackTable& t, uintptr_t s) { launch_optim(a, t, S(s)); check_last("optim"); });
+  // gradient clipping (clip.hip): the global-norm launch and the in-place clip of the data-parallel step
+  py::class_<ClipArgs>(m, "ClipArgs")
+      .def(py::init<>())
+      PTR(ClipArgs, g) RW(ClipArgs, n) RW(ClipArgs, clipnorm) RW(ClipArgs, clipvalue) RW(ClipArgs, use_norm)
+      PTR(ClipArgs, partials) RW(ClipArgs, npartials) PTR(ClipArgs, state);
+  m.attr("CLIP_CHUNK") = CLIP_CHUNK;
+  m.attr("CLIP_THREADS") = CLIP_THREADS;
+  m.attr("CLIP_VEC_PER_THREAD") = CLIP_VEC_PER_THREAD;
+  m.attr("CLIP_STATE_WORDS") = CLIP_STATE_WORDS;
+  m.attr("CLIP_NORM") = CLIP_NORM;
+  m.attr("CLIP_FACTOR") = CLIP_FACTOR;
+  m.attr("CLIP_TICKET") = CLIP_TICKET;
+  m.def("clip_blocks", &clip_blocks);
+  m.def("grad_sqnorm", [](const ClipArgs& a, uintptr_t s) { launch_grad_sqnorm(a, S(s)); check_last("grad_sqnorm"); });
+  m.def("grad_clip_apply", [](const ClipArgs& a, uintptr_t s) { launch_grad_clip_apply(a, S(s)); check_last("grad_clip_apply"); });
   m.def("pack", [](uintptr_t master, uintptr_t arena, const PackTable& t, uintptr_t s) {
     launch_pack(reinterpret_cast<const float*>(master), reinterpret_cast<bf16*>(arena), t, S(s)); check_last("pack"); });
 

@@ -233,7 +233,7 @@ int gather_gx(int R) {
 // forward vector each (8 consecutive k of one n: a column of the slice), lanes 32..63 one
 // backward vector each (8 consecutive n of one k: a row segment).  Same per-element math as
 // the flat path (bit-identical weights), 16-byte pack stores.
-template <int KIND>
+template <int KIND, bool CLIP = false>
 __device__ __forceinline__ void optim_tile_block(const OptimArgs& a, int tb, bf16 (*tile)[8][40]) {
   int i = 0;
 #pragma unroll
@@ -252,6 +252,7 @@ __device__ __forceinline__ void optim_tile_block(const OptimArgs& a, int tb, bf1
   const int e = R.lo + (row0 + r) * N + col0 + c4;
   float4 p, g, s0, s1, s2;
   opt_load4<KIND>(a, e, p, s0, s1, s2, &g);
+  if constexpr (CLIP) g = clip4(a, g, clip_factor(a));
   opt_update4<KIND>(a, a.st, p, g, s0, s1, s2);
   opt_store4<KIND>(a, e, p, s0, s1, s2);
   bf16 (*sl)[40] = tile[wave];
@@ -285,11 +286,14 @@ __device__ __forceinline__ bool in_tiled_route(const OptimArgs& a, int e) {
   return false;
 }
 
-template <int KIND>
-__global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
-  __shared__ __attribute__((aligned(16))) bf16 tile[4][8][40];
+// The launch's body.  CLIP (optim_clip_kernel): every gradient goes through clip_elem -- the
+// step's global-norm factor, read once per thread, and the clipvalue clamp -- before the update,
+// in the flat float4 path, the boundary groups and the tile blocks alike; the CLIP = false
+// instances (optim_kernel) are the code they were without it.
+template <int KIND, bool CLIP = false>
+__device__ __forceinline__ void optim_body(const OptimArgs& a, bf16 (*tile)[8][40]) {
   if (a.ntile && (int)blockIdx.x >= a.flat_blocks) {
-    optim_tile_block<KIND>(a, (int)blockIdx.x - a.flat_blocks, tile);
+    optim_tile_block<KIND, CLIP>(a, (int)blockIdx.x - a.flat_blocks, tile);
     return;
   }
   const int base = a.lo & ~3, end = a.lo + a.n;
@@ -300,6 +304,7 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
   const StepState* st = a.st;
   float4 p, g, s0, s1, s2;
   opt_load4<KIND>(a, e, p, s0, s1, s2, &g);
+  if constexpr (CLIP) g = clip4(a, g, clip_factor(a));
   if (e >= a.lo && e + 4 <= end) {
     opt_update4<KIND>(a, st, p, g, s0, s1, s2);
   } else {   // a boundary group: the elements outside the range are written back unchanged
@@ -323,6 +328,18 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
   if (a.defer_pack && !a.nroutes && blockIdx.x == 0 && threadIdx.x == 0) a.st->packs_stale = 1;
 }
 
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
+  __shared__ __attribute__((aligned(16))) bf16 tile[4][8][40];
+  optim_body<KIND, false>(a, tile);
+}
+// the clipped form (a kernel name of its own: optim_kernel<KIND> stays the name of the unclipped one)
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_clip_kernel(const OptimArgs a) {
+  __shared__ __attribute__((aligned(16))) bf16 tile[4][8][40];
+  optim_body<KIND, true>(a, tile);
+}
+
 // the state buffers a kind's instances read and write unconditionally
 static void check_state_slots(const OptimArgs& a) {
   const OptKindRow* row = opt_kind_row(a.kind);
@@ -342,8 +359,11 @@ void launch_optim(const OptimArgs& a, const PackTable& tab, hipStream_t s) {
     const int flat = ((span + 3) / 4 + 255) / 256;
     if (a.ntile && a.flat_blocks != flat) throw std::invalid_argument("optim: flat_blocks mismatch");
     const dim3 grid(flat + (a.ntile ? a.tile_b0[a.ntile] : 0));
+    // the CLIP instance only when a clip is on: an optimizer without one runs optim_kernel<KIND>
+    const bool clip = a.clip != nullptr || a.clipvalue > 0.f;
     opt_dispatch_all("optim", a.kind, [&](auto k) {
-      hipLaunchKernelGGL(optim_kernel<decltype(k)::kind>, grid, dim3(256), 0, s, a);
+      if (clip) hipLaunchKernelGGL(optim_clip_kernel<decltype(k)::kind>, grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(optim_kernel<decltype(k)::kind>, grid, dim3(256), 0, s, a);
     });
   }
   if (!a.defer_pack || a.pack_only)

@@ -71,6 +71,28 @@ __device__ __forceinline__ void opt_update(const OptimArgs& a, const StepState* 
   }
 }
 
+// Keras gradient clipping of ONE element (Optimizer.get_gradients): the global-norm factor
+// first (c / norm when norm >= c, else exactly 1: the quotient is formed once per step by
+// grad_sqnorm_kernel), then the clamp to [-v, v] when v > 0.  Comparisons, not fminf / fmaxf:
+// a NaN gradient stays NaN.  No fp contraction: the product is a rounding of its own whatever
+// consumes it, so a factor of 1 and v = inf-like bounds leave the update's bits unchanged.
+__device__ __forceinline__ float clip_elem(float g, float factor, float v) {
+#pragma clang fp contract(off)
+  g = g * factor;
+  if (v > 0.f) g = g < -v ? -v : (g > v ? v : g);
+  return g;
+}
+// the clip factor and bound of a launch (CLIP instances): read once per thread
+__device__ __forceinline__ float clip_factor(const OptimArgs& a) { return a.clip ? a.clip[CLIP_FACTOR] : 1.f; }
+__device__ __forceinline__ float4 clip4(const OptimArgs& a, float4 g, float factor) {
+  const float v = a.clipvalue;
+  g.x = clip_elem(g.x, factor, v);
+  g.y = clip_elem(g.y, factor, v);
+  g.z = clip_elem(g.z, factor, v);
+  g.w = clip_elem(g.w, factor, v);
+  return g;
+}
+
 // The same for four consecutive elements at e (16-byte aligned): load p and the state (s0 / s1
 // optional; s2 is touched by the OPT_AMSGRAD instances only and dead in every other one; with
 // g also the gradient at a.g + e), update with the gradient scaled by grad_scale, store back.

@@ -6,6 +6,8 @@ boundaries"), captured once per batch size into a HIP graph and replayed:
   prologue(gather + re-pack + bookkeeping) -> conv_mm(fwd) x C -> [dense split-K + epilogue] x D -> head
   -> [wgrad(dense) + conv_mm(dX, bwd-through)] x D -> [wgrad(conv) + conv_mm(dgrad,
   bwd-through)] x C -> slab_reduce (per DP bucket) -> [RCCL all-reduce] -> optim
+  (a clipping optimizer: slab_reduce -> grad_sqnorm -> clipped optim on one GPU; data parallel
+  slab_reduce -> grad_sqnorm -> grad_clip_apply -> RCCL all-reduce -> optim)
 
 Activations are bf16 NHWC with channel strides padded to 8 (input: 4); weights live in
 ONE fp32 master buffer (Keras layout) and are mirrored into bf16 fragment-major packs by
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 from ..ops.hip import kernels
-from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, fill_kernel_args
+from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, clip_pair, fill_clip_args, fill_kernel_args
 from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
@@ -127,6 +129,22 @@ class HipExecutor(Executor):
         self.opt = base
         n_slots = getattr(base, "n_slots", 0)
         self.slots = [torch.zeros(store.capacity, dtype=torch.float32, device=self.device) for _ in range(n_slots)]
+        # Keras gradient clipping (clipnorm over the global norm, then clipvalue), read HERE like the
+        # other hyper-parameters except lr: the values go into kernel arguments of the captured
+        # step, so a later change of optimizer.clipnorm / clipvalue takes a new compile().  A clipping
+        # optimizer's step has the fuse_optim=0 structure whatever its kind -- every slab
+        # reduction, the norm launch, then the clipped optimizer launch -- gated like
+        # STANDALONE_KINDS: no early reduction, no fused dense update, RCCL plane only.  The clip
+        # scalars (norm, factor, the norm kernel's ticket) live in a buffer of their own.
+        self.clipnorm, self.clipvalue = clip_pair(base)
+        self.clips = bool(self.clipnorm or self.clipvalue)
+        self.clip_state = self.clip_partials = None
+        if self.clips:
+            K = self.K
+            self.clip_state = torch.zeros(K.CLIP_STATE_WORDS, dtype=torch.float32, device=self.device)
+            self.clip_state[K.CLIP_FACTOR] = 1.0
+            self.clip_partials = torch.zeros(cdiv(store.numel + 3, K.CLIP_CHUNK) + 1, dtype=torch.float32,
+                                             device=self.device)
         self._build_geometry()
         self._build_packs()
         self._plans: Dict[Tuple[int, str], "BatchPlan"] = {}
@@ -257,7 +275,20 @@ class HipExecutor(Executor):
             self.routes = torch.from_numpy(arr).to(self.device)
 
     # ------------------------------------------------------------------ params / optimizer
-    def _optim_args(self, pack_only: bool, defer_pack: bool = False):
+    def _clip_args(self):
+        """ClipArgs over the whole flat gradient: the norm launch's and the in-place clip's."""
+        c = self.K.ClipArgs()
+        c.g = self.store.grad.data_ptr()
+        c.n = self.store.numel
+        c.clipnorm, c.clipvalue, c.use_norm = self.clipnorm, self.clipvalue, int(bool(self.clipnorm))
+        c.partials, c.npartials = self.clip_partials.data_ptr(), self.clip_partials.numel()
+        c.state = self.clip_state.data_ptr()
+        return c
+
+    def _optim_args(self, pack_only: bool, defer_pack: bool = False, clip: bool = False):
+        """clip: the clipped optimizer launch (single-GPU step of a clipping optimizer); every
+        other user of these args -- the fused reductions, the data-parallel update behind the
+        all-reduce of already clipped gradients -- leaves the clip fields off."""
         K = self.K
         a = K.OptimArgs()
         a.p = self.store.master.data_ptr()
@@ -275,6 +306,8 @@ class HipExecutor(Executor):
         a.pack_only = int(pack_only)
         a.defer_pack = int(defer_pack)
         a.arena = self.arena.data_ptr()
+        if clip and self.clips:
+            fill_clip_args(self.opt, a, self.clip_state.data_ptr())
         if self.routes is not None and not pack_only:
             a.routes = self.routes.data_ptr()
             a.nroutes = self.routes.numel() * 4 // K.PACK_ROUTE_BYTES
@@ -811,7 +844,7 @@ class BatchPlan(GeometryMixin):
         dense_opt = str(tune("dense_opt")).lower()
         self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim")
                              and dense_opt not in ("0", "false", "off", "no")
-                             and ex.opt.kind not in STANDALONE_KINDS)
+                             and ex.opt.kind not in STANDALONE_KINDS and not ex.clips)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
 
     def _dense_wgrad(self, g, ds, direct):
@@ -1017,13 +1050,28 @@ class BatchPlan(GeometryMixin):
             self.bucket_tables.append((lo, hi, tab))
             inserts.append((max(self.red_groups[i].ready for i in bg), k))
         extra = []
+        if reducer is not None and ex.clips:
+            # data parallel: each rank clips its OWN reduced gradient by its own norm, in memory,
+            # ahead of the all-reduce (Horovod's order: clip, then average); the update behind
+            # the all-reduce is the ordinary unclipped one with grad_scale = 1 / size
+            ca = ex._clip_args()
+            if ex.clipnorm:
+                extra.append(("grad_sqnorm_b%d", lambda k: (lambda s: ex.K.grad_sqnorm(ca, s)), "main"))
+            extra.append(("grad_clip_apply_b%d", lambda k: (lambda s: ex.K.grad_clip_apply(ca, s)), "main"))
         if self.comm_in_graph:
             xk = getattr(reducer, "xgmi_bucket", None)
+            if ex.clips and xk is not None:
+                raise AssertionError("gradient clipping runs on the RCCL plane only")
             self._plan_bucket_exchange(reducer, xk, bucket_groups, dp_early)
-            extra = self._comm_launches(reducer, xk, len(bucket_groups))
+            extra += self._comm_launches(reducer, xk, len(bucket_groups))
         self.launches, self.bucket_ready = splice_bucket_launches(
             self.launches, inserts,
             [("reduce_b%d", lambda k: (lambda s: self._launch_bucket_reduce(k, s)), "side")] + extra)
+        if reducer is None and ex.clipnorm:
+            # single GPU: the norm of the whole reduced gradient, after the last slab reduction
+            # and ahead of the clipped optimizer launch (_launch_optim) -- inside the captured step
+            ca = ex._clip_args()
+            self._add("grad_sqnorm", lambda s, a=ca: ex.K.grad_sqnorm(a, s), clip=ca)
         spans = [(lo, hi) for lo, hi, _ in self.bucket_tables]
         if self.comm_in_graph and self.optim_on_comm:
             # a comm-stream optimizer writes its layers' packs: never while a later
@@ -1045,7 +1093,8 @@ class BatchPlan(GeometryMixin):
         # ... with the optimizer fused into it when its table covers every parameter
         covered = sum(d.numel for grp in self.red_groups for d in grp.descs)
         covered += sum(n for _, n in self.dense_fused_opt)
-        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim")
+        # (a clipping optimizer: the global norm needs every reduced gradient before any update)
+        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim") and not self.ex.clips
         if not self.optim_fused:
             # the step ends with a full optimizer launch after all: the dense layers keep
             # writing their gradient in place, but leave the update -- and the bf16 pack
@@ -1072,7 +1121,10 @@ class BatchPlan(GeometryMixin):
     def _assign_buckets_dp(self, reducer):
         """Data parallel: the reducer's buckets, and the groups reduced early inside the
         backward (with their xGMI push / exchange planned).  Returns (bucket groups, early groups)."""
+        # (a clipping optimizer: the reducers' configure gives ONE bucket, from optimizer.clips)
         bucket_groups = reducer.configure([(grp.lo, grp.hi) for grp in self.red_groups])
+        if self.ex.clips and len(bucket_groups) != 1:
+            raise AssertionError("gradient clipping: the data-parallel step needs ONE bucket")
         # one bucket at the end of the backward (the adaptive plan for gradients <= 16 MB):
         # the groups final before the first dual launch (head, dense -- the single-GPU
         # step's early bucket) are REDUCED early there (grad_only: no update), so the
@@ -1213,7 +1265,8 @@ class BatchPlan(GeometryMixin):
         self.early_red = {}
         # (the extras choose the optimizer at run time among five kinds: the others' head and
         # dense groups stay in the end-of-step / per-bucket reduce_optim_kernel<KIND> launch)
-        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS:
+        # (nor with gradient clipping: no update before the global norm of every gradient)
+        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS or self.ex.clips:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous
@@ -1309,7 +1362,9 @@ class BatchPlan(GeometryMixin):
     def _launch_optim(self):
         ex = self.ex
         # the re-pack of the updated weights is done by the next step's prologue launch
-        ex.K.optim(ex.tile_routes(ex._optim_args(False, defer_pack=True)), ex.pack_table,
+        # (a clipping optimizer: the clipped launch on one GPU -- store.grad keeps the unclipped
+        # reduced gradient; behind a reducer the gradient in memory is already clipped)
+        ex.K.optim(ex.tile_routes(ex._optim_args(False, defer_pack=True, clip=ex.reducer is None)), ex.pack_table,
                    torch.cuda.current_stream().cuda_stream)
 
     def _body(self, with_optim: bool):

@@ -19,6 +19,7 @@ import torch
 
 from ..ops import reference as R
 from ..ops.rng import dropout_keep
+from ..optim.optimizers import clip_pair
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .plan import Plan
@@ -203,6 +204,11 @@ class RefExecutor(Executor):
             z, a_head, saved = self._forward(x, True, step)
             loss, dz, corr = self._head_loss(z, y, w)
             self._backward(dz / bs, a_head, saved)
+            # Keras clipping of this rank's own gradient (Horovod's DistributedOptimizer clips
+            # locally, then all-reduces): before the reducer, never on the average
+            cn, cv = clip_pair(base)
+            if cn or cv:
+                R.clip_gradients(self.store.grad[:self.store.numel], cn, cv)
             if self.reducer is not None:
                 if not getattr(self, "_buckets_configured", False):
                     # same bucketing as the GPU executor: per-layer flat ranges in backward

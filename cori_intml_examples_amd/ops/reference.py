@@ -153,6 +153,22 @@ def apply_weights(loss: torch.Tensor, dz: torch.Tensor, w: torch.Tensor):
 
 
 # --------------------------------------------------------------------------- optimizers (Keras 2.2)
+def clip_gradients(g_flat: torch.Tensor, clipnorm=None, clipvalue=None):
+    """Keras 2.2.4 ``Optimizer.get_gradients`` clipping of the flat fp32 gradient, in place.
+    clipnorm = c > 0: with n the GLOBAL norm sqrt(sum g^2) over every parameter, g *= c / n when
+    n >= c (the quotient formed first); n == 0 and a NaN norm fail the comparison and leave g
+    unchanged.  clipvalue = v > 0: g = min(max(g, -v), v), applied after the norm clip.
+    None or <= 0 means off.  Returns the norm (None without clipnorm)."""
+    norm = None
+    if clipnorm is not None and clipnorm > 0:
+        norm = torch.sqrt((g_flat * g_flat).sum())
+        if bool(norm >= clipnorm):
+            g_flat.mul_(torch.tensor(clipnorm, dtype=g_flat.dtype) / norm)
+    if clipvalue is not None and clipvalue > 0:
+        g_flat.clamp_(-clipvalue, clipvalue)
+    return norm
+
+
 def adam_update(p, g, m, v, t: int, lr: float, beta_1=0.9, beta_2=0.999, eps=EPS):
     lr_t = lr * math.sqrt(1.0 - beta_2 ** t) / (1.0 - beta_1 ** t)
     m.mul_(beta_1).add_(g, alpha=1.0 - beta_1)

@@ -76,6 +76,32 @@ def fill_kernel_args(opt, args, kind_field: str = "kind"):
     return args
 
 
+def fill_clip_args(opt, args, clip_state_ptr: int):
+    """Write ``opt``'s gradient clipping into OptimArgs ``args``: the clip-state buffer the norm
+    launch writes its factor to (clipnorm) and the clamp bound (clipvalue).  Nothing is written
+    for an optimizer without clipping (the fields' defaults mean off)."""
+    cn, cv = clip_pair(opt)
+    if cn:
+        args.clip = clip_state_ptr
+    if cv:
+        args.clipvalue = cv
+    return args
+
+
+def _clip_arg(v) -> float:
+    """A clipnorm / clipvalue argument as the kernels take it: None or <= 0 means off (0.0)."""
+    if v is None:
+        return 0.0
+    v = float(v)
+    return v if v > 0 else 0.0
+
+
+def clip_pair(opt):
+    """(clipnorm, clipvalue) of an optimizer or its DistributedOptimizer wrapper, 0.0 = off."""
+    base = getattr(opt, "_base_optimizer", opt)
+    return _clip_arg(getattr(base, "clipnorm", None)), _clip_arg(getattr(base, "clipvalue", None))
+
+
 def get_value(x) -> float:
     return x.get() if isinstance(x, KVariable) else float(x)
 
@@ -92,6 +118,14 @@ class Optimizer:
     default_lr = 0.01
 
     def __init__(self, lr=None, decay=0.0, learning_rate=None, **kw):
+        # Keras 2.2.4 Optimizer.get_gradients: clipnorm = c > 0 scales every gradient by c / n
+        # when the GLOBAL norm n (over all trainable parameters) is >= c; clipvalue = v > 0 then
+        # clamps every element to [-v, v].  Kept only when given (get_config); <= 0 / None = off.
+        # (other unknown keywords are accepted and ignored, as before)
+        for key in ("clipnorm", "clipvalue"):
+            if key in kw:
+                v = kw[key]
+                setattr(self, key, None if v is None else float(v))
         if lr is None:
             lr = learning_rate if learning_rate is not None else self.default_lr
         self.lr = KVariable(lr, "lr")
@@ -111,9 +145,18 @@ class Optimizer:
     def hparams(self) -> dict:
         return {}
 
+    @property
+    def clips(self) -> bool:
+        """True when clipnorm or clipvalue is on (the step then runs the clipping plan)."""
+        return any(clip_pair(self))
+
+    def _clip_config(self) -> dict:
+        return {k: getattr(self, k) for k in ("clipnorm", "clipvalue") if hasattr(self, k)}
+
     def get_config(self) -> dict:
         cfg = {"lr": self.lr.get(), "decay": self.decay}
         cfg.update(self.hparams())
+        cfg.update(self._clip_config())
         return cfg
 
     @classmethod
@@ -232,6 +275,7 @@ class Nadam(Optimizer):
     def get_config(self):
         cfg = {"lr": self.lr.get()}
         cfg.update(self.hparams())
+        cfg.update(self._clip_config())
         return cfg
 
 

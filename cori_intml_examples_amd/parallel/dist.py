@@ -303,6 +303,13 @@ def merge_buckets(groups: Sequence[Tuple[int, int]], bucket_bytes: int):
     return buckets, spans
 
 
+def one_bucket_for(optimizer) -> bool:
+    """True when ``optimizer`` (or the one a DistributedOptimizer wraps) clips gradients: its global
+    norm needs every local reduction before the first all-reduce, so both reducers configure the
+    whole gradient as ONE bucket."""
+    return bool(getattr(getattr(optimizer, "_base_optimizer", optimizer), "clips", False))
+
+
 class GradReducer:
     """Bucketed gradient all-reduce over the flat grad buffer (torch.distributed data plane).
 
@@ -313,8 +320,9 @@ class GradReducer:
     """
     capturable = False
 
-    def __init__(self, store, compression=None, bucket_bytes: int = 4 << 20):
+    def __init__(self, store, compression=None, bucket_bytes: int = 4 << 20, optimizer=None):
         self.store = store
+        self.optimizer = optimizer      # (one_bucket_for: a clipping optimizer's single bucket)
         self.compression = compression
         self.bucket_bytes = bucket_bytes
         self.size = size()
@@ -328,7 +336,8 @@ class GradReducer:
 
     def configure(self, groups: Sequence[Tuple[int, int]]) -> List[List[int]]:
         """Merge backward-ordered groups into buckets; returns group indices per bucket."""
-        self.bucket_groups, self.buckets = merge_buckets(groups, self.bucket_bytes or (4 << 20))
+        bb = (1 << 62) if one_bucket_for(getattr(self, "optimizer", None)) else (self.bucket_bytes or (4 << 20))
+        self.bucket_groups, self.buckets = merge_buckets(groups, bb)
         return self.bucket_groups
 
     def start(self, bucket: int, grad: torch.Tensor):
@@ -521,11 +530,21 @@ RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-
 
 def plane_for_optimizer(plane: str, optimizer, forced: bool) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
-    for RCCL_ONLY_KINDS when it was merely chosen (auto / a recorded verdict), and is a
-    ValueError when it was forced (INTML_XGMI, or a job without an RCCL communicator)."""
+    for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``) -- when it was
+    merely chosen (auto / a recorded verdict), and is a ValueError when it was forced (INTML_XGMI,
+    or a job without an RCCL communicator)."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
-    if plane not in ("xgmi", "hybrid") or getattr(base, "kind", None) not in RCCL_ONLY_KINDS:
+    clips = bool(getattr(base, "clips", False))
+    if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips):
         return plane
+    if forced and clips:
+        # gradient clipping: the local gradient is clipped in memory ahead of the all-reduce,
+        # which only the RCCL plane's step does (the xGMI kernels reduce and exchange in one launch)
+        cfg = ", ".join("%s=%g" % (k, getattr(base, k)) for k in ("clipnorm", "clipvalue")
+                        if getattr(base, k, None))
+        raise ValueError("optimizer %s(%s): gradient clipping has no kernels for the %r data plane (the "
+                         "clipped gradient is all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
+                         % (type(base).__name__, cfg, plane))
     if forced:
         name = type(base).__name__ + ("(amsgrad=True)" if getattr(base, "amsgrad", False) else "")
         raise ValueError("optimizer %s has no kernels for the %r data plane (its update runs behind an RCCL "
@@ -583,8 +602,10 @@ class NativeGradReducer:
             # must not split the job between planes)
             self.plane = broadcast_object(self.plane, 0)
         bb = self.bucket_bytes
-        if self.plane == "xgmi":
-            bb = 1 << 62                    # the whole gradient is ONE fused xGMI bucket
+        if self.plane == "xgmi" or one_bucket_for(getattr(self, "optimizer", None)):
+            # the whole gradient is ONE bucket: the fused xGMI kernel's, or a clipping
+            # optimizer's (the global norm needs every local reduction before any all-reduce)
+            bb = 1 << 62
         elif self.plane == "hybrid" and not bb:
             bb = 1 << 20                    # dense bucket(s) over RCCL, the conv tail over xGMI
         bg, spans = merge_buckets(groups, bb or adaptive_bucket_bytes(groups, self.size))
@@ -760,4 +781,4 @@ def make_reducer(executor, optimizer):
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
                                  device=executor.store.device, optimizer=optimizer)
-    return GradReducer(executor.store, comp, bb)
+    return GradReducer(executor.store, comp, bb, optimizer=optimizer)

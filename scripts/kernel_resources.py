@@ -3,7 +3,7 @@
 
     python scripts/kernel_resources.py [file.hip ...] [--filter SUBSTR] [-j N]
 
-Prints one row per kernel instance: VGPRs, AGPRs, SGPR spills, VGPR spills, scratch bytes per
+Prints one row per kernel instance: VGPRs, SGPRs, AGPRs, SGPR spills, VGPR spills, scratch bytes per
 lane, LDS bytes, occupancy (waves/SIMD).  Exit status 1 if any kernel needs scratch (a private
 copy of a by-value argument or spilled registers in memory: tests/test_kernel_resources.py)."""
 import argparse
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KDIR = os.path.join(ROOT, "cori_intml_examples_amd", "csrc", "kernels")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + KDIR, "-munsafe-fp-atomics",
          "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
-FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
+FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "ScratchSize [bytes/lane]": "scratch", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occ"}
 
 
@@ -61,12 +61,12 @@ def main():
             rows += rs
     names = demangle([r["name"] for r in rows])
     bad = 0
-    print("%-6s %-5s %-6s %-6s %-7s %-6s %-4s  %s" % ("VGPR", "AGPR", "SSpill", "VSpill", "scratch", "LDS", "occ", "kernel (file)"))
+    print("%-6s %-6s %-5s %-6s %-6s %-7s %-6s %-4s  %s" % ("VGPR", "SGPR", "AGPR", "SSpill", "VSpill", "scratch", "LDS", "occ", "kernel (file)"))
     for r, n in zip(rows, names):
         if args.filter and args.filter not in n:
             continue
         bad += r.get("scratch", 0) > 0
-        print("%-6d %-5d %-6d %-6d %-7d %-6d %-4d  %s (%s)" % (r["vgpr"], r.get("agpr", 0), r.get("sgpr_spill", 0),
+        print("%-6d %-6d %-5d %-6d %-6d %-7d %-6d %-4d  %s (%s)" % (r["vgpr"], r.get("sgpr", 0), r.get("agpr", 0), r.get("sgpr_spill", 0),
                                                            r.get("vgpr_spill", 0), r.get("scratch", 0), r.get("lds", 0),
                                                            r.get("occ", 0), n[:150], r["file"]))
     return 1 if bad else 0
