@@ -1,7 +1,7 @@
 """Step time of the RPV CNN ([16,32,64]/[128], 64x64x3, B=128) per optimizer on one GPU.
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
-                                        [--clipnorm C]
+                                        [--clipnorm C] [--l2 X]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -12,7 +12,11 @@ model's rounds.  Prints one JSON line.
 under ``INTML_TUNE=fuse_optim=0,early_reduce=0``: every slab reduction, then one optimizer launch
 -- the structure of a clipping step without the clip) and ``<name>/clipnorm`` (``clipnorm=C``: that
 structure plus the norm launch and the clipped load).  The difference between the two is the cost
-of gradient clipping."""
+of gradient clipping.
+
+``--l2 X`` likewise adds ``<name>/unfused`` and ``<name>/l2`` (an l2 kernel regularizer ``X`` on
+every Conv2D / Dense: that structure plus the one ``weight_reg`` launch).  The difference between
+the two is the cost of the weight regularizers."""
 import argparse
 import json
 import os
@@ -39,14 +43,17 @@ def make_opt(name, **kw):
     return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
 
 
-def variants(names, clipnorm):
-    """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built)]"""
+def variants(names, clipnorm, l2=None):
+    """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2)]"""
     out = []
     for nm in names:
-        out.append((nm, nm, {}, None))
+        out.append((nm, nm, {}, None, 0.0))
+        if clipnorm is not None or l2:
+            out.append((nm + "/unfused", nm, {}, UNFUSED, 0.0))
         if clipnorm is not None:
-            out.append((nm + "/unfused", nm, {}, UNFUSED))
-            out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None))
+            out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None, 0.0))
+        if l2:
+            out.append((nm + "/l2", nm, {}, None, l2))
     return out
 
 
@@ -76,8 +83,9 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--clipnorm", type=float, default=None)
+    ap.add_argument("--l2", type=float, default=None)
     a = ap.parse_args()
-    var = variants(a.opts.split(","), a.clipnorm)
+    var = variants(a.opts.split(","), a.clipnorm, a.l2)
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -85,11 +93,11 @@ def main():
     x = rs.rand(bs * REPLAY, 64, 64, 3).astype(np.float32)
     y = (rs.rand(bs * REPLAY) > 0.5).astype(np.float32)
     runs = {}
-    for nm, oname, kw, tv in var:
+    for nm, oname, kw, tv, l2 in var:
         set_random_seed(1)
         with tuned(tv):
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
-                            optimizer=make_opt(oname, **kw), lr=None, device="cuda:0")
+                            optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}))
         ex = m._executor
         d = ex.upload(x, y)
         perm = torch.arange(d.n, device=ex.device)

@@ -10,6 +10,13 @@ from __future__ import annotations
 
 from ..models import Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model, Sequential
 from .. import optim as optimizers
+from .. import regularizers
+
+
+def _kernel_l2(l2):
+    """Layer keywords of the builders' ``l2=``: an l2 kernel regularizer on every Conv2D / Dense
+    (not on biases); nothing at all for 0 -- exactly the unregularized model."""
+    return {"kernel_regularizer": regularizers.l2(l2)} if l2 else {}
 
 
 def clipped_optimizer(optimizer: str, lr=None, clipnorm=None, clipvalue=None):
@@ -35,34 +42,36 @@ def _opt(optimizer, lr, use_horovod):
 
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
-              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None):
+              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, l2=0.0):
+    reg = _kernel_l2(l2)
     m = Sequential(device=device)
-    m.add(Conv2D(h1, (3, 3), activation="relu", input_shape=input_shape))
-    m.add(Conv2D(h2, (3, 3), activation="relu"))
+    m.add(Conv2D(h1, (3, 3), activation="relu", input_shape=input_shape, **reg))
+    m.add(Conv2D(h2, (3, 3), activation="relu", **reg))
     m.add(MaxPooling2D(pool_size=(2, 2)))
     m.add(Dropout(dropout))
     m.add(Flatten())
-    m.add(Dense(h3, activation="relu"))
+    m.add(Dense(h3, activation="relu", **reg))
     m.add(Dropout(dropout if dropout2 is None else dropout2))
-    m.add(Dense(n_classes, activation="softmax"))
+    m.add(Dense(n_classes, activation="softmax", **reg))
     m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy",
               metrics=["accuracy"])
     return m
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
-            use_horovod=False, device=None):
+            use_horovod=False, device=None, l2=0.0):
+    reg = _kernel_l2(l2)
     inputs = Input(shape=input_shape)
     h = inputs
     for c in conv_sizes:
-        h = Conv2D(c, kernel_size=(3, 3), activation="relu", padding="same")(h)
+        h = Conv2D(c, kernel_size=(3, 3), activation="relu", padding="same", **reg)(h)
         h = MaxPooling2D(pool_size=(2, 2))(h)
     h = Dropout(dropout)(h)
     h = Flatten()(h)
     for f in fc_sizes:
-        h = Dense(f, activation="relu")(h)
+        h = Dense(f, activation="relu", **reg)(h)
         h = Dropout(dropout)(h)
-    outputs = Dense(1, activation="sigmoid")(h)
+    outputs = Dense(1, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
     model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
     return model

@@ -100,6 +100,41 @@ struct ClipArgs {
   float* state = nullptr;        // CLIP_STATE_WORDS words
 };
 
+// Keras L1 / L2 weight regularizers (reg.hip, weight_reg_kernel): one launch per step adds
+// l1 * sgn(w) + 2 * l2 * w to the flat gradient over every regularized parameter range and sums
+// the penalty P = sum l1 * |w| + l2 * w * w into the step's loss.  The reg state is a small buffer
+// of its own (StepState's layout is read by host-side offsets): [REG_PENALTY] the launch's P,
+// [REG_TICKET] the arrival counter of the launch's workgroups (as unsigned; zero between launches).
+#define MAX_REG_RANGES 16
+#define REG_PENALTY 0
+#define REG_TICKET 1
+#define REG_STATE_WORDS 4
+#define REG_THREADS 256
+#define REG_VEC_PER_THREAD 8                                // float4 groups per thread
+#define REG_CHUNK (REG_THREADS * 4 * REG_VEC_PER_THREAD)    // elements per workgroup
+struct RegRange {
+  int lo, hi;                    // elements [lo, hi) of p / g
+  float l1, l2x2, l2;            // l2x2 = 2 * l2, formed on the host (exact in fp32)
+};
+struct RegArgs {
+  const float* p = nullptr;      // master weights (read only), elements [0, n); 4-byte aligned is
+  float* g = nullptr;            // enough, but p and g must share their offset in a 16-byte line
+  int n = 0;
+  int nranges = 0;               // ascending, disjoint (set_ranges)
+  RegRange r[MAX_REG_RANGES];
+  // the launch covers only the chunks of the 16-byte-aligned view that touch a range: workgroups
+  // [seg_b0[s], seg_b0[s + 1]) take the chunks from seg_c0[s] on (set_ranges / reg_plan)
+  int nseg = 0;
+  int seg_b0[MAX_REG_RANGES + 1];
+  int seg_c0[MAX_REG_RANGES];
+  float rows = 0.f;              // the plan's batch size: the metric words take P * rows
+  int add_grad = 0;              // 1: store g (training step); 0: penalty only (eval step)
+  float* partials = nullptr;     // one partial sum per workgroup
+  int npartials = 0;             // capacity of partials (host check)
+  StepState* st = nullptr;       // metric_slots[0]: += P * rows in the head's fixed point
+  float* state = nullptr;        // REG_STATE_WORDS words
+};
+
 // Implicit-GEMM convolution / 1x1 "dense as conv" (fwd, dgrad, dense-dX).
 struct ConvMMArgs {
   const bf16* x = nullptr;       // input activations [B, H, W, Cs_in]

@@ -60,6 +60,9 @@ void launch_pack(const float* master, bf16* arena, const PackTable& tab, hipStre
 void launch_grad_sqnorm(const ClipArgs& a, hipStream_t s);
 void launch_grad_clip_apply(const ClipArgs& a, hipStream_t s);
 int clip_blocks(const ClipArgs& a);
+void launch_weight_reg(const RegArgs& a, hipStream_t s);
+int reg_blocks(const RegArgs& a);
+void reg_set_ranges(RegArgs& a, const int* lo, const int* hi, const float* l1, const float* l2, int count);
 int xgmi_grid(const XgmiArgs& a);
 void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s);
 uintptr_t xgmi_alloc_uncached(size_t bytes, bool finegrained);
@@ -473,6 +476,36 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("clip_blocks", &clip_blocks);
   m.def("grad_sqnorm", [](const ClipArgs& a, uintptr_t s) { launch_grad_sqnorm(a, S(s)); check_last("grad_sqnorm"); });
   m.def("grad_clip_apply", [](const ClipArgs& a, uintptr_t s) { launch_grad_clip_apply(a, S(s)); check_last("grad_clip_apply"); });
+  // Keras L1 / L2 weight regularizers (reg.hip): the per-step gradient term + penalty launch
+  py::class_<RegArgs>(m, "RegArgs")
+      .def(py::init<>())
+      PTR(RegArgs, p) PTR(RegArgs, g) RW(RegArgs, n) RW(RegArgs, rows) RW(RegArgs, add_grad)
+      PTR(RegArgs, partials) RW(RegArgs, npartials) PTR(RegArgs, st) PTR(RegArgs, state)
+      .def_readonly("nranges", &RegArgs::nranges)
+      // [(lo, hi, l1, l2)] ascending and disjoint; l2x2 = 2 * l2 is formed here
+      .def("set_ranges", [](RegArgs& a, const std::vector<std::tuple<int, int, float, float>>& rs) {
+        std::vector<int> lo, hi;
+        std::vector<float> l1, l2;
+        for (const auto& r : rs) {
+          lo.push_back(std::get<0>(r)); hi.push_back(std::get<1>(r));
+          l1.push_back(std::get<2>(r)); l2.push_back(std::get<3>(r));
+        }
+        reg_set_ranges(a, lo.data(), hi.data(), l1.data(), l2.data(), (int)rs.size());
+      })
+      .def("ranges", [](const RegArgs& a) {
+        std::vector<std::tuple<int, int, float, float, float>> out;
+        for (int i = 0; i < a.nranges; ++i) out.emplace_back(a.r[i].lo, a.r[i].hi, a.r[i].l1, a.r[i].l2x2, a.r[i].l2);
+        return out;
+      });
+  m.attr("MAX_REG_RANGES") = MAX_REG_RANGES;
+  m.attr("REG_CHUNK") = REG_CHUNK;
+  m.attr("REG_THREADS") = REG_THREADS;
+  m.attr("REG_VEC_PER_THREAD") = REG_VEC_PER_THREAD;
+  m.attr("REG_STATE_WORDS") = REG_STATE_WORDS;
+  m.attr("REG_PENALTY") = REG_PENALTY;
+  m.attr("REG_TICKET") = REG_TICKET;
+  m.def("reg_blocks", &reg_blocks);
+  m.def("weight_reg", [](const RegArgs& a, uintptr_t s) { launch_weight_reg(a, S(s)); check_last("weight_reg"); });
   m.def("pack", [](uintptr_t master, uintptr_t arena, const PackTable& t, uintptr_t s) {
     launch_pack(reinterpret_cast<const float*>(master), reinterpret_cast<bf16*>(arena), t, S(s)); check_last("pack"); });
 

@@ -7,7 +7,9 @@ boundaries"), captured once per batch size into a HIP graph and replayed:
   -> [wgrad(dense) + conv_mm(dX, bwd-through)] x D -> [wgrad(conv) + conv_mm(dgrad,
   bwd-through)] x C -> slab_reduce (per DP bucket) -> [RCCL all-reduce] -> optim
   (a clipping optimizer: slab_reduce -> grad_sqnorm -> clipped optim on one GPU; data parallel
-  slab_reduce -> grad_sqnorm -> grad_clip_apply -> RCCL all-reduce -> optim)
+  slab_reduce -> grad_sqnorm -> grad_clip_apply -> RCCL all-reduce -> optim; a model with weight
+  regularizers: slab_reduce -> weight_reg -> [grad_sqnorm ..] as above, and head -> weight_reg in
+  an evaluation step)
 
 Activations are bf16 NHWC with channel strides padded to 8 (input: 4); weights live in
 ONE fp32 master buffer (Keras layout) and are mirrored into bf16 fragment-major packs by
@@ -145,6 +147,23 @@ class HipExecutor(Executor):
             self.clip_state[K.CLIP_FACTOR] = 1.0
             self.clip_partials = torch.zeros(cdiv(store.numel + 3, K.CLIP_CHUNK) + 1, dtype=torch.float32,
                                              device=self.device)
+        # Keras weight regularizers [(lo, hi, l1, l2)] over the flat store, read HERE like the clip
+        # values (they go into kernel arguments of the captured step).  A regularized model's step
+        # is gated exactly like a clipping one's: the term joins the whole reduced gradient in ONE
+        # weight_reg launch (reg.hip) behind the last slab reduction and ahead of the norm launch
+        # and the update, so no early reduction, no fused dense update, optim_fused = False, RCCL
+        # plane only.  reg_state[REG_PENALTY] is the last step's penalty P.
+        self.regs = store.regularized_ranges()
+        self.reg_state = self.reg_partials = None
+        if self.regs:
+            K = self.K
+            if len(self.regs) > K.MAX_REG_RANGES:
+                raise ValueError("%d regularized weight tensors (layers %s): the regularizer kernel takes at most "
+                                 "MAX_REG_RANGES = %d" % (len(self.regs), ", ".join(store.regularized_layers()),
+                                                          K.MAX_REG_RANGES))
+            self.reg_state = torch.zeros(K.REG_STATE_WORDS, dtype=torch.float32, device=self.device)
+            self.reg_partials = torch.zeros(cdiv(store.numel + 3, K.REG_CHUNK) + 1, dtype=torch.float32,
+                                            device=self.device)
         self._build_geometry()
         self._build_packs()
         self._plans: Dict[Tuple[int, str], "BatchPlan"] = {}
@@ -284,6 +303,19 @@ class HipExecutor(Executor):
         c.partials, c.npartials = self.clip_partials.data_ptr(), self.clip_partials.numel()
         c.state = self.clip_state.data_ptr()
         return c
+
+    def _reg_args(self, rows: int, add_grad: bool):
+        """RegArgs of a step of ``rows`` rows: the gradient term (training) and the penalty."""
+        r = self.K.RegArgs()
+        r.p = self.store.master.data_ptr()
+        r.g = self.store.grad.data_ptr()
+        r.n = self.store.numel
+        r.set_ranges([tuple(x) for x in self.regs])
+        r.rows, r.add_grad = float(rows), int(add_grad)
+        r.partials, r.npartials = self.reg_partials.data_ptr(), self.reg_partials.numel()
+        r.st = self.state.data_ptr()
+        r.state = self.reg_state.data_ptr()
+        return r
 
     def _optim_args(self, pack_only: bool, defer_pack: bool = False, clip: bool = False):
         """clip: the clipped optimizer launch (single-GPU step of a clipping optimizer); every
@@ -648,6 +680,10 @@ class BatchPlan(GeometryMixin):
         head_epi = self._build_dense_fwd(sb)
         self._build_head(head_epi)
         if not self.training:
+            if self.mode == "eval" and ex.regs:
+                # an evaluation batch reports L_data + P too: the penalty only, after the head
+                ra = ex._reg_args(self.bs, False)
+                self._add("weight_reg", lambda s, a=ra: ex.K.weight_reg(a, s), reg=ra)
             return
         self._begin_backward()
         for g, ds in reversed(list(zip(ex.denses, ex.plan.denses))):
@@ -844,7 +880,8 @@ class BatchPlan(GeometryMixin):
         dense_opt = str(tune("dense_opt")).lower()
         self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim")
                              and dense_opt not in ("0", "false", "off", "no")
-                             and ex.opt.kind not in STANDALONE_KINDS and not ex.clips)
+                             and ex.opt.kind not in STANDALONE_KINDS and not ex.clips
+                             and not ex.regs)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
 
     def _dense_wgrad(self, g, ds, direct):
@@ -1050,6 +1087,12 @@ class BatchPlan(GeometryMixin):
             self.bucket_tables.append((lo, hi, tab))
             inserts.append((max(self.red_groups[i].ready for i in bg), k))
         extra = []
+        if reducer is not None and ex.regs:
+            # data parallel: every rank adds the regularizers' term to its OWN reduced gradient
+            # (weights are identical on all ranks: the average is avg(g) + reg'(w)), ahead of its
+            # clip and of the all-reduce; every rank's loss takes the penalty
+            ra = ex._reg_args(self.bs, True)
+            extra.append(("weight_reg_b%d", lambda k: (lambda s: ex.K.weight_reg(ra, s)), "main"))
         if reducer is not None and ex.clips:
             # data parallel: each rank clips its OWN reduced gradient by its own norm, in memory,
             # ahead of the all-reduce (Horovod's order: clip, then average); the update behind
@@ -1060,13 +1103,19 @@ class BatchPlan(GeometryMixin):
             extra.append(("grad_clip_apply_b%d", lambda k: (lambda s: ex.K.grad_clip_apply(ca, s)), "main"))
         if self.comm_in_graph:
             xk = getattr(reducer, "xgmi_bucket", None)
-            if ex.clips and xk is not None:
-                raise AssertionError("gradient clipping runs on the RCCL plane only")
+            if (ex.clips or ex.regs) and xk is not None:
+                raise AssertionError("gradient clipping / weight regularizers run on the RCCL plane only")
             self._plan_bucket_exchange(reducer, xk, bucket_groups, dp_early)
             extra += self._comm_launches(reducer, xk, len(bucket_groups))
         self.launches, self.bucket_ready = splice_bucket_launches(
             self.launches, inserts,
             [("reduce_b%d", lambda k: (lambda s: self._launch_bucket_reduce(k, s)), "side")] + extra)
+        if reducer is None and ex.regs:
+            # single GPU: the regularizers' term joins the whole reduced gradient (in place:
+            # store.grad holds the regularized gradient) after the last slab reduction, ahead of
+            # the norm launch and the update -- inside the captured step
+            ra = ex._reg_args(self.bs, True)
+            self._add("weight_reg", lambda s, a=ra: ex.K.weight_reg(a, s), reg=ra)
         if reducer is None and ex.clipnorm:
             # single GPU: the norm of the whole reduced gradient, after the last slab reduction
             # and ahead of the clipped optimizer launch (_launch_optim) -- inside the captured step
@@ -1094,7 +1143,9 @@ class BatchPlan(GeometryMixin):
         covered = sum(d.numel for grp in self.red_groups for d in grp.descs)
         covered += sum(n for _, n in self.dense_fused_opt)
         # (a clipping optimizer: the global norm needs every reduced gradient before any update)
-        self.optim_fused = one and covered == self.ex.store.numel and tune("fuse_optim") and not self.ex.clips
+        # (weight regularizers: their term joins the whole reduced gradient before any update)
+        self.optim_fused = (one and covered == self.ex.store.numel and tune("fuse_optim") and not self.ex.clips
+                            and not self.ex.regs)
         if not self.optim_fused:
             # the step ends with a full optimizer launch after all: the dense layers keep
             # writing their gradient in place, but leave the update -- and the bf16 pack
@@ -1121,10 +1172,11 @@ class BatchPlan(GeometryMixin):
     def _assign_buckets_dp(self, reducer):
         """Data parallel: the reducer's buckets, and the groups reduced early inside the
         backward (with their xGMI push / exchange planned).  Returns (bucket groups, early groups)."""
-        # (a clipping optimizer: the reducers' configure gives ONE bucket, from optimizer.clips)
+        # (a clipping optimizer or a regularized model: the reducers' configure gives ONE bucket,
+        # from optimizer.clips / the needs_local_gradient flag make_reducer passes)
         bucket_groups = reducer.configure([(grp.lo, grp.hi) for grp in self.red_groups])
-        if self.ex.clips and len(bucket_groups) != 1:
-            raise AssertionError("gradient clipping: the data-parallel step needs ONE bucket")
+        if (self.ex.clips or self.ex.regs) and len(bucket_groups) != 1:
+            raise AssertionError("gradient clipping / weight regularizers: the data-parallel step needs ONE bucket")
         # one bucket at the end of the backward (the adaptive plan for gradients <= 16 MB):
         # the groups final before the first dual launch (head, dense -- the single-GPU
         # step's early bucket) are REDUCED early there (grad_only: no update), so the
@@ -1265,8 +1317,9 @@ class BatchPlan(GeometryMixin):
         self.early_red = {}
         # (the extras choose the optimizer at run time among five kinds: the others' head and
         # dense groups stay in the end-of-step / per-bucket reduce_optim_kernel<KIND> launch)
-        # (nor with gradient clipping: no update before the global norm of every gradient)
-        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS or self.ex.clips:
+        # (nor with gradient clipping: no update before the global norm of every gradient; nor with
+        # weight regularizers: no update before their term has joined the reduced gradient)
+        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS or self.ex.clips or self.ex.regs:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous

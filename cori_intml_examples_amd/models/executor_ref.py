@@ -35,6 +35,8 @@ class RefExecutor(Executor):
         self._acc = torch.zeros(3, dtype=torch.float64)
         self._last = (0.0, 0.0)
         self.emulate_bf16 = bool(tune("ref_bf16"))
+        # Keras weight regularizers [(lo, hi, l1, l2)], read here (at compile) like the clip values
+        self.regs = store.regularized_ranges()
 
     # ------------------------------------------------------------------------------ data
     def upload(self, x, y, w=None):
@@ -204,6 +206,11 @@ class RefExecutor(Executor):
             z, a_head, saved = self._forward(x, True, step)
             loss, dz, corr = self._head_loss(z, y, w)
             self._backward(dz / bs, a_head, saved)
+            # Keras weight regularizers: the penalty of the weights this forward used joins the
+            # batch loss (unweighted), its gradient joins this rank's gradient before the clip
+            penalty = self._penalty()
+            if self.regs:
+                R.add_regularization_grad(self.regs, self.store.master, self.store.grad)
             # Keras clipping of this rank's own gradient (Horovod's DistributedOptimizer clips
             # locally, then all-reduces): before the reducer, never on the average
             cn, cv = clip_pair(base)
@@ -218,10 +225,14 @@ class RefExecutor(Executor):
                     self._buckets_configured = True
                 self.reducer.reduce_all(self.store.grad)
             self._apply_update()
-        self._accumulate(loss, corr, bs)
+        self._accumulate(loss, corr, bs, penalty)
 
-    def _accumulate(self, loss, corr, bs):
-        ls, cs = float(loss.sum()), float(corr.sum())
+    def _penalty(self) -> float:
+        return float(R.regularization_penalty(self.regs, self.store.master)) if self.regs else 0.0
+
+    def _accumulate(self, loss, corr, bs, penalty=0.0):
+        # (a batch of bs rows reports L_data + P: it adds bs * P to the epoch's loss sum)
+        ls, cs = float(loss.sum()) + bs * penalty, float(corr.sum())
         self._acc += torch.tensor([ls, cs, bs], dtype=torch.float64)
         self._last = (ls / bs, cs / bs)
 
@@ -231,7 +242,7 @@ class RefExecutor(Executor):
         with torch.no_grad():
             z, _, _ = self._forward(x, False, 0)
             loss, _, corr = self._head_loss(z, y, w)
-        self._accumulate(loss, corr, bs)
+        self._accumulate(loss, corr, bs, self._penalty())
 
     def predict_step(self, data: DeviceData, pos: int, bs: int) -> torch.Tensor:
         with torch.no_grad():

@@ -15,6 +15,7 @@ import re
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence, Tuple
 
+from .. import regularizers
 from ..ops.reference import conv_out_size
 
 _name_counters: Dict[str, int] = defaultdict(int)
@@ -167,6 +168,32 @@ def Input(shape=None, batch_shape=None, name=None, dtype="float32") -> KTensor:
     return KTensor(tuple(shape), layer, None)
 
 
+class _Regularized:
+    """The regularizer keywords of Conv2D / Dense (Keras 2.2.4): ``kernel_regularizer`` and
+    ``bias_regularizer`` take what ``regularizers.get`` takes; ``L1L2(0, 0)`` counts as none.
+    ``activity_regularizer`` is not implemented and says so."""
+
+    def _set_regularizers(self, kernel_regularizer, bias_regularizer, activity_regularizer):
+        if activity_regularizer is not None:
+            raise NotImplementedError("layer %s: activity_regularizer is not implemented (kernel_regularizer "
+                                      "and bias_regularizer are)" % self.name)
+        self.kernel_regularizer = regularizers.get(kernel_regularizer) or None
+        self.bias_regularizer = regularizers.get(bias_regularizer) or None
+
+    def weight_regularizers(self):
+        """{weight short name: L1L2} of this layer's regularized tensors."""
+        out = {}
+        if self.kernel_regularizer is not None:
+            out["kernel"] = self.kernel_regularizer
+        if self.bias_regularizer is not None and self.use_bias:
+            out["bias"] = self.bias_regularizer
+        return out
+
+    def _regularizer_config(self):
+        return {"kernel_regularizer": regularizers.serialize(self.kernel_regularizer),
+                "bias_regularizer": regularizers.serialize(self.bias_regularizer)}
+
+
 def _check_act(act):
     if callable(act):
         act = getattr(act, "__name__", None)
@@ -175,11 +202,13 @@ def _check_act(act):
     return None if act == "linear" else act
 
 
-class Conv2D(Layer):
+class Conv2D(_Regularized, Layer):
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None,
                  dilation_rate=(1, 1), activation=None, use_bias=True,
-                 kernel_initializer="glorot_uniform", bias_initializer="zeros", **kw):
+                 kernel_initializer="glorot_uniform", bias_initializer="zeros", kernel_regularizer=None,
+                 bias_regularizer=None, activity_regularizer=None, **kw):
         super().__init__(**kw)
+        self._set_regularizers(kernel_regularizer, bias_regularizer, activity_regularizer)
         self.filters = int(filters)
         self.kernel_size = _pair(kernel_size)
         self.strides = _pair(strides)
@@ -227,13 +256,14 @@ class Conv2D(Layer):
                     "bias_initializer": {"class_name": "Zeros", "config": {}},
                     "kernel_regularizer": None, "bias_regularizer": None,
                     "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None})
+        cfg.update(self._regularizer_config())
         return cfg
 
     @classmethod
     def from_config(cls, cfg):
         cfg = {k: v for k, v in cfg.items() if k in (
             "name", "trainable", "filters", "kernel_size", "strides", "padding", "activation",
-            "use_bias", "batch_input_shape")}
+            "use_bias", "batch_input_shape", "kernel_regularizer", "bias_regularizer", "activity_regularizer")}
         return super().from_config(cfg)
 
 
@@ -302,10 +332,12 @@ class Flatten(Layer):
         return cls(name=cfg.get("name"))
 
 
-class Dense(Layer):
+class Dense(_Regularized, Layer):
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer="glorot_uniform",
-                 bias_initializer="zeros", **kw):
+                 bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None,
+                 activity_regularizer=None, **kw):
         super().__init__(**kw)
+        self._set_regularizers(kernel_regularizer, bias_regularizer, activity_regularizer)
         self.units = int(units)
         self.activation = _check_act(activation)
         self.use_bias = bool(use_bias)
@@ -332,12 +364,14 @@ class Dense(Layer):
                     "bias_initializer": {"class_name": "Zeros", "config": {}},
                     "kernel_regularizer": None, "bias_regularizer": None,
                     "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None})
+        cfg.update(self._regularizer_config())
         return cfg
 
     @classmethod
     def from_config(cls, cfg):
         cfg = {k: v for k, v in cfg.items() if k in (
-            "name", "trainable", "units", "activation", "use_bias", "batch_input_shape")}
+            "name", "trainable", "units", "activation", "use_bias", "batch_input_shape",
+            "kernel_regularizer", "bias_regularizer", "activity_regularizer")}
         return super().from_config(cfg)
 
 

@@ -140,6 +140,11 @@ class Model:
     def weights(self):
         return [w for l in self._chain for w in l.weights]
 
+    def regularized_ranges(self):
+        """[(lo, hi, l1, l2)]: the flat parameter store's ranges that carry a weight regularizer
+        (``kernel_regularizer`` / ``bias_regularizer`` of Conv2D / Dense), in store order."""
+        return self.store.regularized_ranges() if self.store is not None else []
+
     # ------------------------------------------------------------------ compile
     def compile(self, optimizer, loss=None, metrics=None, loss_weights=None, sample_weight_mode=None,
                 **kwargs):
@@ -162,7 +167,8 @@ class Model:
         base = getattr(self.optimizer, "_base_optimizer", self.optimizer)
         if getattr(self.optimizer, "distributed", False):
             from ..parallel import dist
-            dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda")
+            dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda",
+                                       tuple(self.store.regularized_layers()))
         if self._device.type == "cuda":
             from .executor_hip import HipExecutor
             self._executor = HipExecutor(self._plan, self.store, base, self._seed)

@@ -138,6 +138,24 @@ class ParamStore:
             host[s.offset:s.offset + s.numel] = t.reshape(-1)
         self.master.copy_(host.to(self.device))
 
+    def regularized_ranges(self) -> List[Tuple[int, int, float, float]]:
+        """[(lo, hi, l1, l2)]: the flat ranges whose tensor carries a Keras weight regularizer
+        (the layers' kernel_regularizer / bias_regularizer), in store order."""
+        out = []
+        for s in self.specs:
+            reg = getattr(s.layer, "weight_regularizers", dict)().get(s.short)
+            if reg is not None and s.numel:
+                out.append((s.offset, s.offset + s.numel, reg.l1, reg.l2))
+        return out
+
+    def regularized_layers(self) -> List[str]:
+        """Names of the layers with a regularized tensor, in store order."""
+        names = []
+        for s in self.specs:
+            if getattr(s.layer, "weight_regularizers", dict)().get(s.short) is not None and s.layer.name not in names:
+                names.append(s.layer.name)
+        return names
+
     def layer_ranges(self) -> Dict[str, Tuple[int, int]]:
         out: Dict[str, Tuple[int, int]] = {}
         for s in self.specs:

@@ -152,6 +152,29 @@ def apply_weights(loss: torch.Tensor, dz: torch.Tensor, w: torch.Tensor):
     return loss * f, dz * (f if dz.dim() == 1 else f.unsqueeze(-1))
 
 
+# --------------------------------------------------------------------------- regularizers (Keras 2.2)
+def regularization_penalty(ranges, master: torch.Tensor) -> torch.Tensor:
+    """Keras 2.2.4 ``L1L2`` penalty of the flat fp32 weights: the sum over ``ranges``
+    [(lo, hi, l1, l2)] of l1 * sum(|w|) + l2 * sum(w * w), as an fp32 scalar tensor."""
+    total = torch.zeros((), dtype=torch.float32)
+    for lo, hi, l1, l2 in ranges:
+        w = master[lo:hi].to(torch.float32)
+        total = total + (torch.tensor(l1, dtype=torch.float32) * w.abs()
+                         + torch.tensor(l2, dtype=torch.float32) * (w * w)).sum()
+    return total
+
+
+def add_regularization_grad(ranges, master: torch.Tensor, g_flat: torch.Tensor) -> None:
+    """g += l1 * sgn(w) + 2 * l2 * w over ``ranges`` [(lo, hi, l1, l2)], in place, in fp32 and in
+    the HIP kernel's operation order g + (l1 * sgn(w) + (2 * l2) * w); sgn(0) = 0 (TensorFlow's
+    gradient of abs).  Elements outside every range are untouched."""
+    for lo, hi, l1, l2 in ranges:
+        w = master[lo:hi]
+        c1 = torch.tensor(l1, dtype=torch.float32)
+        c2 = torch.tensor(l2, dtype=torch.float32) * 2.0
+        g_flat[lo:hi] = g_flat[lo:hi] + (c1 * torch.sign(w) + c2 * w)
+
+
 # --------------------------------------------------------------------------- optimizers (Keras 2.2)
 def clip_gradients(g_flat: torch.Tensor, clipnorm=None, clipvalue=None):
     """Keras 2.2.4 ``Optimizer.get_gradients`` clipping of the flat fp32 gradient, in place.

@@ -303,11 +303,13 @@ def merge_buckets(groups: Sequence[Tuple[int, int]], bucket_bytes: int):
     return buckets, spans
 
 
-def one_bucket_for(optimizer) -> bool:
+def one_bucket_for(optimizer, needs_local_gradient=False) -> bool:
     """True when ``optimizer`` (or the one a DistributedOptimizer wraps) clips gradients: its global
     norm needs every local reduction before the first all-reduce, so both reducers configure the
-    whole gradient as ONE bucket."""
-    return bool(getattr(getattr(optimizer, "_base_optimizer", optimizer), "clips", False))
+    whole gradient as ONE bucket.  ``needs_local_gradient`` (the executor's: a model with weight
+    regularizers, whose term joins the rank's whole local gradient in one launch ahead of the
+    all-reduce) asks for the same."""
+    return bool(needs_local_gradient) or bool(getattr(getattr(optimizer, "_base_optimizer", optimizer), "clips", False))
 
 
 class GradReducer:
@@ -320,9 +322,11 @@ class GradReducer:
     """
     capturable = False
 
-    def __init__(self, store, compression=None, bucket_bytes: int = 4 << 20, optimizer=None):
+    def __init__(self, store, compression=None, bucket_bytes: int = 4 << 20, optimizer=None,
+                 needs_local_gradient=()):
         self.store = store
         self.optimizer = optimizer      # (one_bucket_for: a clipping optimizer's single bucket)
+        self.needs_local_gradient = needs_local_gradient   # (... and a regularized model's: its layer names)
         self.compression = compression
         self.bucket_bytes = bucket_bytes
         self.size = size()
@@ -336,7 +340,8 @@ class GradReducer:
 
     def configure(self, groups: Sequence[Tuple[int, int]]) -> List[List[int]]:
         """Merge backward-ordered groups into buckets; returns group indices per bucket."""
-        bb = (1 << 62) if one_bucket_for(getattr(self, "optimizer", None)) else (self.bucket_bytes or (4 << 20))
+        one = one_bucket_for(getattr(self, "optimizer", None), getattr(self, "needs_local_gradient", ()))
+        bb = (1 << 62) if one else (self.bucket_bytes or (4 << 20))
         self.bucket_groups, self.buckets = merge_buckets(groups, bb)
         return self.bucket_groups
 
@@ -528,15 +533,23 @@ def auto_plane(grad_bytes: Optional[int] = None) -> str:
 RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-switch instance)
 
 
-def plane_for_optimizer(plane: str, optimizer, forced: bool) -> str:
+def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=()) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
-    for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``) -- when it was
-    merely chosen (auto / a recorded verdict), and is a ValueError when it was forced (INTML_XGMI,
-    or a job without an RCCL communicator)."""
+    for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``), and for a
+    model with weight regularizers (``needs_local_gradient``: the names of its regularized
+    layers) -- when it was merely chosen (auto / a recorded verdict), and is a ValueError when it
+    was forced (INTML_XGMI, or a job without an RCCL communicator)."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
     clips = bool(getattr(base, "clips", False))
-    if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips):
+    if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips
+                                               or needs_local_gradient):
         return plane
+    if forced and needs_local_gradient:
+        # weight regularizers: their term joins the local gradient in memory ahead of the
+        # all-reduce, which only the RCCL plane's step does
+        raise ValueError("weight regularizers (layers %s) have no kernels for the %r data plane (the regularized "
+                         "gradient is all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
+                         % (", ".join(needs_local_gradient), plane))
     if forced and clips:
         # gradient clipping: the local gradient is clipped in memory ahead of the all-reduce,
         # which only the RCCL plane's step does (the xGMI kernels reduce and exchange in one launch)
@@ -568,9 +581,11 @@ class NativeGradReducer:
     capturable = True
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
-                 rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None):
+                 rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None,
+                 needs_local_gradient=()):
         self.store, self.comm = store, comm
         self.optimizer = optimizer      # (plane_for_optimizer: kinds that stay off the xGMI planes)
+        self.needs_local_gradient = needs_local_gradient   # (a regularized model's layer names: the same)
         self.compression = compression
         self.bucket_bytes = bucket_bytes
         # comm None: the RCCL-free data plane (state.xgmi_only) -- the whole gradient is ONE
@@ -595,16 +610,19 @@ class NativeGradReducer:
     def configure(self, groups: Sequence[Tuple[int, int]]) -> List[List[int]]:
         self.plane = (data_plane(4 * sum(hi - lo for lo, hi in groups)) if self.comm is not None
                       else "xgmi")
+        local = getattr(self, "needs_local_gradient", ())
         self.plane = plane_for_optimizer(self.plane, getattr(self, "optimizer", None),
-                                         forced=self.comm is None or forced_plane() is not None)
+                                         forced=self.comm is None or forced_plane() is not None,
+                                         needs_local_gradient=local)
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
             self.plane = broadcast_object(self.plane, 0)
         bb = self.bucket_bytes
-        if self.plane == "xgmi" or one_bucket_for(getattr(self, "optimizer", None)):
+        if self.plane == "xgmi" or one_bucket_for(getattr(self, "optimizer", None), local):
             # the whole gradient is ONE bucket: the fused xGMI kernel's, or a clipping
-            # optimizer's (the global norm needs every local reduction before any all-reduce)
+            # optimizer's (the global norm needs every local reduction before any all-reduce),
+            # or a regularized model's (one weight_reg launch over the whole local gradient)
             bb = 1 << 62
         elif self.plane == "hybrid" and not bb:
             bb = 1 << 20                    # dense bucket(s) over RCCL, the conv tail over xGMI
@@ -755,17 +773,18 @@ class NativeGradReducer:
             grad[: self.store.numel].div_(self.size)
 
 
-def check_optimizer_plane(optimizer, on_gpu: bool) -> None:
-    """ValueError when the job pins a data plane ``optimizer`` has no kernels for (INTML_XGMI =
-    xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds the executor,
-    so nothing has been launched when it raises."""
+def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=()) -> None:
+    """ValueError when the job pins a data plane ``optimizer`` -- or a model with weight
+    regularizers (``needs_local_gradient``: its regularized layers' names) -- has no kernels for
+    (INTML_XGMI = xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds
+    the executor, so nothing has been launched when it raises."""
     if not is_initialized():
         init()
     st = _st()
     if on_gpu and st.comm is not None:
-        plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True)
+        plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient)
     elif on_gpu and st.xgmi_only and st.size > 1:
-        plane_for_optimizer("xgmi", optimizer, forced=True)
+        plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient)
 
 
 def make_reducer(executor, optimizer):
@@ -775,10 +794,13 @@ def make_reducer(executor, optimizer):
     bb = getattr(optimizer, "bucket_bytes", None) or st.bucket_bytes
     comp = getattr(optimizer, "compression", None)
     on_gpu = getattr(executor.store, "device", torch.device("cpu")).type == "cuda"
-    check_optimizer_plane(optimizer, on_gpu)
+    # a model with weight regularizers needs each rank's whole local gradient ahead of the
+    # all-reduce, as a clipping optimizer does: ONE bucket, RCCL plane (the layers' names, for errors)
+    local = tuple(executor.store.regularized_layers()) if getattr(executor, "regs", None) else ()
+    check_optimizer_plane(optimizer, on_gpu, local)
     if on_gpu and st.comm is not None:
-        return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer)
+        return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
-                                 device=executor.store.device, optimizer=optimizer)
-    return GradReducer(executor.store, comp, bb, optimizer=optimizer)
+                                 device=executor.store.device, optimizer=optimizer, needs_local_gradient=local)
+    return GradReducer(executor.store, comp, bb, optimizer=optimizer, needs_local_gradient=local)
