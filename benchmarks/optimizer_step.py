@@ -1,7 +1,7 @@
 """Step time of the RPV CNN ([16,32,64]/[128], 64x64x3, B=128) per optimizer on one GPU.
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
-                                        [--clipnorm C] [--l2 X]
+                                        [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -16,7 +16,14 @@ of gradient clipping.
 
 ``--l2 X`` likewise adds ``<name>/unfused`` and ``<name>/l2`` (an l2 kernel regularizer ``X`` on
 every Conv2D / Dense: that structure plus the one ``weight_reg`` launch).  The difference between
-the two is the cost of the weight regularizers."""
+the two is the cost of the weight regularizers.
+
+``--activation NAME[,NAME..]`` adds ``<name>/perlayer`` (the relu model built under
+``INTML_TUNE=conv_stack=0,fuse_head=0``: the per-layer structure a model with hidden activations
+takes, without the activation launches) and one ``<name>/<activation>`` model per name (that
+structure plus one ``act_fwd`` and one ``act_bwd`` launch per hidden stage).  The difference between
+those is the cost of the activation launches; the difference between ``<name>`` and
+``<name>/perlayer`` is the cost of leaving the fused conv stack."""
 import argparse
 import json
 import os
@@ -37,23 +44,29 @@ REPLAY = 32
 
 
 UNFUSED = "fuse_optim=0,early_reduce=0"
+PERLAYER = "conv_stack=0,fuse_head=0"
 
 
 def make_opt(name, **kw):
     return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
 
 
-def variants(names, clipnorm, l2=None):
-    """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2)]"""
+def variants(names, clipnorm, l2=None, activations=()):
+    """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
+    hidden activation)]"""
     out = []
     for nm in names:
-        out.append((nm, nm, {}, None, 0.0))
+        out.append((nm, nm, {}, None, 0.0, "relu"))
         if clipnorm is not None or l2:
-            out.append((nm + "/unfused", nm, {}, UNFUSED, 0.0))
+            out.append((nm + "/unfused", nm, {}, UNFUSED, 0.0, "relu"))
         if clipnorm is not None:
-            out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None, 0.0))
+            out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None, 0.0, "relu"))
         if l2:
-            out.append((nm + "/l2", nm, {}, None, l2))
+            out.append((nm + "/l2", nm, {}, None, l2, "relu"))
+        if activations:
+            out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
+        for act in activations:
+            out.append((nm + "/" + act, nm, {}, None, 0.0, act))
     return out
 
 
@@ -84,8 +97,9 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--clipnorm", type=float, default=None)
     ap.add_argument("--l2", type=float, default=None)
+    ap.add_argument("--activation", default="", help="comma-separated hidden activations to time")
     a = ap.parse_args()
-    var = variants(a.opts.split(","), a.clipnorm, a.l2)
+    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n])
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -93,11 +107,12 @@ def main():
     x = rs.rand(bs * REPLAY, 64, 64, 3).astype(np.float32)
     y = (rs.rand(bs * REPLAY) > 0.5).astype(np.float32)
     runs = {}
-    for nm, oname, kw, tv, l2 in var:
+    for nm, oname, kw, tv, l2, act in var:
         set_random_seed(1)
         with tuned(tv):
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
-                            optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}))
+                            optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
+                            **({"activation": act} if act != "relu" else {}))
         ex = m._executor
         d = ex.upload(x, y)
         perm = torch.arange(d.n, device=ex.device)

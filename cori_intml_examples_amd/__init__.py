@@ -7,6 +7,6 @@ random / genetic / grid hyper-parameter search with live monitoring widgets.
 """
 __version__ = "0.1.0"
 
-from . import models, optim, regularizers, train, utils  # noqa: F401
-from .models import (Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model, Sequential,  # noqa: F401
-                     load_model)
+from . import activations, models, optim, regularizers, train, utils  # noqa: F401
+from .models import (ELU, Activation, Conv2D, Dense, Dropout, Flatten, Input, LeakyReLU, MaxPooling2D,  # noqa: F401
+                     Model, Sequential, load_model)

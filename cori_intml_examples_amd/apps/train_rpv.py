@@ -41,6 +41,9 @@ def build_parser():
     p.add_argument("--clipnorm", type=float, default=None, help="Keras clipnorm: clip by the global gradient norm")
     p.add_argument("--clipvalue", type=float, default=None, help="Keras clipvalue: clamp every gradient element")
     p.add_argument("--l2", type=float, default=0.0, help="l2 kernel regularizer on every Conv2D / Dense (0: none)")
+    p.add_argument("--activation", default="relu",
+                   help="hidden activation of every Conv2D / Dense: relu, tanh, sigmoid, hard_sigmoid, elu, selu, "
+                        "softplus, softsign")
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--n-epochs", type=int, default=4)
     p.add_argument("--fom", choices=["best", "last"])
@@ -88,7 +91,7 @@ def main(argv=None):
     model = build_model(train_input.shape[1:], conv_sizes=[args.h1, args.h2, args.h3], fc_sizes=[args.h4],
                         dropout=args.dropout,
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
-                        use_horovod=True, l2=args.l2)
+                        use_horovod=True, l2=args.l2, activation=args.activation)
     if hvd.rank() == 0:
         model.summary()
 

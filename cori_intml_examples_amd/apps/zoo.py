@@ -42,15 +42,16 @@ def _opt(optimizer, lr, use_horovod):
 
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
-              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, l2=0.0):
+              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu", l2=0.0):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
     reg = _kernel_l2(l2)
     m = Sequential(device=device)
-    m.add(Conv2D(h1, (3, 3), activation="relu", input_shape=input_shape, **reg))
-    m.add(Conv2D(h2, (3, 3), activation="relu", **reg))
+    m.add(Conv2D(h1, (3, 3), activation=activation, input_shape=input_shape, **reg))
+    m.add(Conv2D(h2, (3, 3), activation=activation, **reg))
     m.add(MaxPooling2D(pool_size=(2, 2)))
     m.add(Dropout(dropout))
     m.add(Flatten())
-    m.add(Dense(h3, activation="relu", **reg))
+    m.add(Dense(h3, activation=activation, **reg))
     m.add(Dropout(dropout if dropout2 is None else dropout2))
     m.add(Dense(n_classes, activation="softmax", **reg))
     m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy",
@@ -59,17 +60,18 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
-            use_horovod=False, device=None, l2=0.0):
+            use_horovod=False, device=None, activation="relu", l2=0.0):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
     reg = _kernel_l2(l2)
     inputs = Input(shape=input_shape)
     h = inputs
     for c in conv_sizes:
-        h = Conv2D(c, kernel_size=(3, 3), activation="relu", padding="same", **reg)(h)
+        h = Conv2D(c, kernel_size=(3, 3), activation=activation, padding="same", **reg)(h)
         h = MaxPooling2D(pool_size=(2, 2))(h)
     h = Dropout(dropout)(h)
     h = Flatten()(h)
     for f in fc_sizes:
-        h = Dense(f, activation="relu", **reg)(h)
+        h = Dense(f, activation=activation, **reg)(h)
         h = Dropout(dropout)(h)
     outputs = Dense(1, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
@@ -78,14 +80,15 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
 
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
-                   use_horovod=False, device=None):
+                   use_horovod=False, device=None, activation="relu"):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
     inputs = Input(shape=input_shape)
-    h = Conv2D(h1, kernel_size=(3, 3), activation="relu", strides=1, padding="same")(inputs)
-    h = Conv2D(h2, kernel_size=(3, 3), activation="relu", strides=2, padding="same")(h)
-    h = Conv2D(h3, kernel_size=(3, 3), activation="relu", strides=1, padding="same")(h)
-    h = Conv2D(h4, kernel_size=(3, 3), activation="relu", strides=2, padding="same")(h)
+    h = Conv2D(h1, kernel_size=(3, 3), activation=activation, strides=1, padding="same")(inputs)
+    h = Conv2D(h2, kernel_size=(3, 3), activation=activation, strides=2, padding="same")(h)
+    h = Conv2D(h3, kernel_size=(3, 3), activation=activation, strides=1, padding="same")(h)
+    h = Conv2D(h4, kernel_size=(3, 3), activation=activation, strides=2, padding="same")(h)
     h = Flatten()(h)
-    h = Dense(h5, activation="relu")(h)
+    h = Dense(h5, activation=activation)(h)
     outputs = Dense(1, activation="sigmoid")(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
     model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])

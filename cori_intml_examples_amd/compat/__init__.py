@@ -5,7 +5,7 @@ names (``mnist.py:15-21``, ``rpv.py:15-16,64``, ``train_rpv.py:10``, ``mlextras.
 ``hpo_widgets.py:9``, ``CrayHPO_rpv.ipynb:44-45``).  ``install()`` registers this
 framework's implementations under those names *when the real package is absent*:
 
-    keras, keras.{layers,models,optimizers,regularizers,callbacks,losses,utils,backend,datasets.mnist,
+    keras, keras.{layers,models,optimizers,regularizers,activations,callbacks,losses,utils,backend,datasets.mnist,
                   wrappers.scikit_learn}
     horovod, horovod.keras, horovod.keras.callbacks      -> parallel.hvd (RCCL data parallelism)
     ipyparallel, ipyparallel.datapub, ipyparallel.error  -> farm (one-node task farm)
@@ -31,6 +31,7 @@ def _mod(name: str, doc: str = "", **attrs) -> types.ModuleType:
 def _keras_modules() -> Dict[str, types.ModuleType]:
     from .. import losses as _losses
     from .. import models as _models
+    from .. import activations as _act
     from .. import regularizers as _reg
     from ..hpo import sklearn as _skl
     from ..models import layers as _layers
@@ -56,7 +57,8 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
                    backend=lambda: "tensorflow", get_value=_opt.get_value, set_value=_opt.set_value)
     layers = _mod("keras.layers", **{k: getattr(_layers, k) for k in
                                      ("Input", "InputLayer", "Conv2D", "MaxPooling2D", "MaxPool2D", "Dropout",
-                                      "Flatten", "Dense", "Layer") if hasattr(_layers, k)})
+                                      "Flatten", "Dense", "Activation", "LeakyReLU", "ELU", "Layer")
+                                     if hasattr(_layers, k)})
     if not hasattr(layers, "MaxPool2D"):
         layers.MaxPool2D = _layers.MaxPooling2D
     models = _mod("keras.models", Sequential=_models.Sequential, Model=_models.Model,
@@ -68,9 +70,10 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
                   KerasRegressor=_skl.KerasRegressor)
     wrappers = _mod("keras.wrappers", scikit_learn=scikit)
     keras = _mod("keras", "MI355X-native Keras-2.2-shaped API", __version__="2.2.4", layers=layers,
-                 models=models, optimizers=_opt, regularizers=_reg, callbacks=_cb, losses=_losses, utils=utils, backend=backend,
+                 models=models, optimizers=_opt, regularizers=_reg, activations=_act, callbacks=_cb, losses=_losses, utils=utils, backend=backend,
                  datasets=datasets, wrappers=wrappers, Sequential=_models.Sequential, Model=_models.Model)
     return {"keras": keras, "keras.layers": layers, "keras.models": models, "keras.optimizers": _opt, "keras.regularizers": _reg,
+            "keras.activations": _act,
             "keras.callbacks": _cb, "keras.losses": _losses, "keras.utils": utils, "keras.backend": backend,
             "keras.datasets": datasets, "keras.datasets.mnist": mnist, "keras.wrappers": wrappers,
             "keras.wrappers.scikit_learn": scikit}

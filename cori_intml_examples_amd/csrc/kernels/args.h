@@ -539,3 +539,40 @@ struct SynthArgs {
   int n = 0, first = 0, H = 0, W = 0, C = 1, Cs = 1, ncls = 1, kind = 0;
   uint32_t seed = 0;
 };
+
+// Element-wise hidden activations (act.hip): one row per activation, X(enum name, code, Keras
+// name, 1 if it takes an alpha).  Code 0 is "none": relu / linear stay in the fused epilogues
+// and in BwdThrough.  Every function is non-decreasing and every derivative is a function of
+// the OUTPUT, so a stage keeps nothing but the output it already stores.
+#define ACT_TABLE(X)                                                                        \
+  X(ACT_TANH, 1, "tanh", 0) X(ACT_SIGMOID, 2, "sigmoid", 0) X(ACT_HARD_SIGMOID, 3, "hard_sigmoid", 0) \
+  X(ACT_ELU, 4, "elu", 1) X(ACT_SELU, 5, "selu", 0) X(ACT_SOFTPLUS, 6, "softplus", 0)       \
+  X(ACT_SOFTSIGN, 7, "softsign", 0) X(ACT_LEAKY_RELU, 8, "leaky_relu", 1)
+struct ActRow { int id; const char* name; int has_alpha; };
+#define X(id, value, name, has_alpha) id = value,
+enum ActKind { ACT_TABLE(X) };
+#undef X
+#define X(id, value, name, has_alpha) {id, name, has_alpha},
+constexpr ActRow ACT_KINDS[] = {ACT_TABLE(X)};
+#undef X
+
+// act_fwd_kernel / act_bwd_kernel over a stage buffer [rows][Cs] bf16 with C <= Cs real
+// channels (Cs % 8 == 0; rows = B * Hp * Wp of a conv stage, B of a dense stage); channels
+// >= C are written back as loaded.
+//   fwd, in place on the stage output x:  x = bf16(dropout(A(float(x))))  with the fused
+//        epilogues' counter dropout_keep((uint32)(row * C + c), seed, stream_id, st->t, drop_thr)
+//   bwd, in place on the stage's gradient x, reading the saved output y:
+//        x = bf16(float(x) * A'(float(y) * y_scale))   (y_scale = 1 - rate undoes the dropout scale)
+struct ActArgs {
+  bf16* x = nullptr;
+  const bf16* y = nullptr;         // bwd only
+  long long rows = 0;
+  int C = 0, Cs = 0;
+  int act = 0;                     // ActKind
+  float alpha = 0.f;               // ACT_ELU / ACT_LEAKY_RELU (>= 0)
+  uint32_t drop_thr = 0;           // fwd only (0: no dropout)
+  float drop_scale = 1.f;
+  uint32_t seed = 0, stream_id = 0;
+  const StepState* st = nullptr;   // fwd: the dropout counter's step (null: 0)
+  float y_scale = 1.f;             // bwd only
+};

@@ -63,6 +63,8 @@ int clip_blocks(const ClipArgs& a);
 void launch_weight_reg(const RegArgs& a, hipStream_t s);
 int reg_blocks(const RegArgs& a);
 void reg_set_ranges(RegArgs& a, const int* lo, const int* hi, const float* l1, const float* l2, int count);
+void launch_act_fwd(const ActArgs& a, hipStream_t s);
+void launch_act_bwd(const ActArgs& a, hipStream_t s);
 int xgmi_grid(const XgmiArgs& a);
 void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s);
 uintptr_t xgmi_alloc_uncached(size_t bytes, bool finegrained);
@@ -506,6 +508,23 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("REG_TICKET") = REG_TICKET;
   m.def("reg_blocks", &reg_blocks);
   m.def("weight_reg", [](const RegArgs& a, uintptr_t s) { launch_weight_reg(a, S(s)); check_last("weight_reg"); });
+  // element-wise hidden activations (act.hip): one launch per direction behind a stage's linear kernels
+  py::class_<ActArgs>(m, "ActArgs")
+      .def(py::init<>())
+      PTR(ActArgs, x) PTR(ActArgs, y) RW(ActArgs, rows) RW(ActArgs, C) RW(ActArgs, Cs) RW(ActArgs, act)
+      RW(ActArgs, alpha) RW(ActArgs, drop_thr) RW(ActArgs, drop_scale) RW(ActArgs, seed) RW(ActArgs, stream_id)
+      PTR(ActArgs, st) RW(ActArgs, y_scale);
+  {
+    py::dict codes, alphas;
+    for (const ActRow& r : ACT_KINDS) {
+      codes[r.name] = r.id;
+      alphas[r.name] = (bool)r.has_alpha;
+    }
+    m.attr("ACT_CODES") = codes;
+    m.attr("ACT_HAS_ALPHA") = alphas;
+  }
+  m.def("act_fwd", [](const ActArgs& a, uintptr_t s) { launch_act_fwd(a, S(s)); check_last("act_fwd"); });
+  m.def("act_bwd", [](const ActArgs& a, uintptr_t s) { launch_act_bwd(a, S(s)); check_last("act_bwd"); });
   m.def("pack", [](uintptr_t master, uintptr_t arena, const PackTable& t, uintptr_t s) {
     launch_pack(reinterpret_cast<const float*>(master), reinterpret_cast<bf16*>(arena), t, S(s)); check_last("pack"); });
 

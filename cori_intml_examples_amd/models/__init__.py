@@ -1,8 +1,9 @@
 """Keras-shaped model API: layers, Sequential/Model, fused stage plan, executors."""
-from .layers import Conv2D, Dense, Dropout, Flatten, Input, InputLayer, KTensor, Layer, MaxPooling2D, reset_names
+from .layers import (ELU, Activation, Conv2D, Dense, Dropout, Flatten, Input, InputLayer, KTensor, Layer, LeakyReLU,
+                     MaxPooling2D, reset_names)
 from .model import Model, Sequential
 
-__all__ = ["Layer", "InputLayer", "Input", "Conv2D", "MaxPooling2D", "Dropout", "Flatten", "Dense",
+__all__ = ["Layer", "InputLayer", "Input", "Conv2D", "MaxPooling2D", "Dropout", "Flatten", "Dense", "Activation", "LeakyReLU", "ELU",
            "KTensor", "Model", "Sequential", "reset_names", "load_model"]
 
 

@@ -9,7 +9,8 @@ boundaries"), captured once per batch size into a HIP graph and replayed:
   (a clipping optimizer: slab_reduce -> grad_sqnorm -> clipped optim on one GPU; data parallel
   slab_reduce -> grad_sqnorm -> grad_clip_apply -> RCCL all-reduce -> optim; a model with weight
   regularizers: slab_reduce -> weight_reg -> [grad_sqnorm ..] as above, and head -> weight_reg in
-  an evaluation step)
+  an evaluation step; a stage with a hidden activation other than relu / linear: its linear
+  forward kernels -> act_fwd, and the launch that stores its gradient -> act_bwd)
 
 Activations are bf16 NHWC with channel strides padded to 8 (input: 4); weights live in
 ONE fp32 master buffer (Keras layout) and are mirrored into bf16 fragment-major packs by
@@ -91,6 +92,8 @@ class ConvGeo:
     NTd: int = 0
     pack_fwd: int = 0
     pack_dgrad: int = -1
+    act: Optional[str] = None      # hidden activation other than relu / linear (plan.ConvStage.act)
+    act_alpha: float = 0.0
 
 
 @dataclass
@@ -109,6 +112,8 @@ class DenseGeo:
     NTb: int = 0
     pack_fwd: int = 0
     pack_bwd: int = -1
+    act: Optional[str] = None      # hidden activation other than relu / linear (plan.DenseStage.act)
+    act_alpha: float = 0.0
 
 
 class HipExecutor(Executor):
@@ -199,6 +204,7 @@ class HipExecutor(Executor):
             kh, kw = cs.conv.kernel_size
             g = ConvGeo(i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
                         cs.pool is not None, cs.relu, cs.rate, cs.stream)
+            g.act, g.act_alpha = cs.act, cs.act_alpha
             g.KS = cdiv(kh * kw * Cs_in, 32)
             g.NT = cdiv(Cout, 16)
             if i > 0:
@@ -212,6 +218,7 @@ class HipExecutor(Executor):
             g = DenseGeo(j, src, ds.K, ds.N, r8(ds.N), ds.relu, ds.rate, ds.stream)
             if g.K != src.H * src.W * src.C:
                 raise ValueError("dense %d input width mismatch" % j)
+            g.act, g.act_alpha = ds.act, ds.act_alpha
             g.KS = cdiv(src.width, 32)
             g.NT = cdiv(ds.N, 16)
             if j > 0 or self.convs:
@@ -672,6 +679,42 @@ class BatchPlan(GeometryMixin):
     def _add(self, name, fn, tag="main", **args):
         self.launches.append(Launch(name, fn, tag, args))
 
+    def _act_args(self, kind, g, bwd):
+        """ActArgs of stage g ('conv' | 'dense') with a hidden activation: the forward launch (in
+        place on the stage output, with the stage's dropout in a training step) or the backward
+        launch (in place on the stage's gradient buffer, reading the saved output)."""
+        ex, K = self.ex, self.ex.K
+        a = K.ActArgs()
+        if kind == "conv":
+            out, grad = self.conv_out[g.i], self.conv_dy[g.i]
+            a.rows, a.C, a.Cs = self.bs * g.Hp * g.Wp, g.Cout, g.Cs_out
+        else:
+            out, grad = self.dense_out[g.j], self.dense_dh[g.j]
+            a.rows, a.C, a.Cs = self.bs, g.N, g.Ns
+        a.act, a.alpha = K.ACT_CODES[g.act], g.act_alpha
+        if bwd:
+            a.x, a.y = grad.data_ptr(), out.data_ptr()
+            if g.rate > 0:       # the saved output carries the dropout scale: undo it (fp32(1 - rate))
+                a.y_scale = float(np.float32(1.0 - g.rate))
+        else:
+            a.x = out.data_ptr()
+            if self.training and g.rate > 0:
+                a.drop_thr, a.drop_scale = dropout_pair(g.rate)
+            a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
+        return a
+
+    def _add_act_bwd(self, src: Src):
+        """Behind the launch that stored the gradient wrt ``src``'s output through its BwdThrough
+        (dropout mask applied, prev_relu = 0): the multiplication by A' of a stage with a hidden
+        activation, before anything reads that gradient buffer."""
+        if src.kind == "input":
+            return
+        g = self.ex.convs[src.idx] if src.kind == "conv" else self.ex.denses[src.idx]
+        if g.act is None:
+            return
+        a = self._act_args(src.kind, g, True)
+        self._add("act_bwd_%s%d" % (src.kind[0], src.idx), lambda s, a=a: self.ex.K.act_bwd(a, s), act=a)
+
     def _build_args(self):
         """The step program, stage by stage; each stage appends its launches."""
         ex = self.ex
@@ -714,7 +757,10 @@ class BatchPlan(GeometryMixin):
         # one prologue launch: gather + the previous update's weight re-pack (training: always,
         # except with per-bucket optimizers that pack themselves; eval/predict: only if an
         # optimizer ran since the last pack) + the step bookkeeping
-        stack = self._conv_stack_args(training) if tune("conv_stack") else None
+        # (a conv stage with a hidden activation other than relu / linear: the per-layer structure
+        # of conv_stack=0, each such layer's linear kernel followed by its act_fwd launch)
+        conv_act = any(g.act is not None for g in ex.convs)
+        stack = self._conv_stack_args(training) if tune("conv_stack") and not conv_act else None
         # Prologue-free step (conv stack + a hidden dense layer + optimizer-written packs): the
         # stack reads its images straight from the dataset through the cursor and permutation
         # (recording each image's dataset row for the first layer's wgrad and the head's
@@ -768,10 +814,14 @@ class BatchPlan(GeometryMixin):
             a.Cs_out, a.Hp, a.Wp = g.Cs_out, g.Hp, g.Wp
             if g.pool:
                 a.code = self.conv_code[g.i].data_ptr()
-            if self.training and g.rate > 0:
+            if self.training and g.rate > 0 and g.act is None:
                 a.drop_thr, a.drop_scale = dropout_pair(g.rate)
             a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
             self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool), ca=a)
+            if g.act is not None:
+                # the linear conv (+ pool) above, then A and the stage's dropout in place
+                fa = self._act_args("conv", g, False)
+                self._add("act_fwd_c%d" % g.i, lambda s, a=fa: K.act_fwd(a, s), act=fa)
             x_buf = self.conv_out[g.i]
 
     def _build_dense_fwd(self, sb):
@@ -797,17 +847,22 @@ class BatchPlan(GeometryMixin):
             e.bias = ex.store.view(ds.dense, "bias").data_ptr() if ds.dense.use_bias else 0
             e.relu = int(g.relu)
             e.out = self.dense_out[g.j].data_ptr()
-            if self.training and g.rate > 0:
+            if self.training and g.rate > 0 and g.act is None:
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head")):
+                    and tune("fuse_head") and g.act is None):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
                 self.head_blocks = cdiv(bs, K.head_rows_per_block(True))
             else:
                 self._add("dense_epi%d" % g.j, lambda s, e=e: K.dense_epi(e, s), epi=e)
+            if g.act is not None:
+                # the linear epilogue above (never the head's: fuse_head=0 structure), then A and
+                # the layer's dropout in place
+                fa = self._act_args("dense", g, False)
+                self._add("act_fwd_d%d" % g.j, lambda s, a=fa: K.act_fwd(a, s), act=fa)
         return head_epi
 
     def _build_head(self, head_epi):
@@ -869,6 +924,7 @@ class BatchPlan(GeometryMixin):
             descs.append(RedDesc(self.head_bslab.data_ptr(), hd.N, self.head_blocks, hd.N, hb.offset, hb.numel,
                                  RED_BIAS))
         self._add_group(hw, descs, hb)
+        self._add_act_bwd(ex.head_src)     # (the head stored the last hidden stage's gradient)
         # opt-in: the dense layer's optimizer update inside its (one-split) wgrad kernel.  Measured
         # slower on RPV at batch 128: the 128 wgrad workgroups move the layer's 14 MB of optimizer
         # state at per-CU bandwidth (wgrad 6.1 -> 9.7 us) while the end-of-step reduction, which
@@ -972,6 +1028,7 @@ class BatchPlan(GeometryMixin):
             # in one launch with it (dense_bwd_pair: dX workgroups would read a pack the
             # wgrad workgroups are rewriting)
             self._add(dname, dl, da=da)
+            self._add_act_bwd(g.src)
         if dual:
             # one launch for the dense wgrad and dX (independent GEMMs over dH); the layer's
             # slabs are final after it
@@ -998,6 +1055,8 @@ class BatchPlan(GeometryMixin):
             self._add(dname, dl, da=da)
         if da is not None:
             self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
+            if not dx_first:
+                self._add_act_bwd(g.src)
 
     def _dgrad_args(self, g):
         """ConvMMArgs of conv layer g's dgrad (a stride-1 conv over the input-dilated dY with
@@ -1062,6 +1121,8 @@ class BatchPlan(GeometryMixin):
             if not dual:
                 self._add(dname, self._conv_launch(ca, g.NTd, False), ca=ca)
             self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
+            prev = ex.convs[g.i - 1]
+            self._add_act_bwd(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
 
     # ---------------------------------------------------------------- step program: reductions
     def _build_reduce(self):

@@ -7,7 +7,9 @@ graph) in exactly the stage order the HIP executor uses.
 ``INTML_TUNE=ref_bf16=1`` makes it a bf16-FAITHFUL oracle: values are rounded to bf16 at
 exactly the points where the HIP step stores them in bf16 (weight packs of the convs and
 hidden denses, every stage output after its dropout, the hidden denses' dH and every pooled
-dP after their masks), everything else in fp32 -- so the whole-step gradient test can use
+dP after their masks; for a stage with a hidden activation also its pre-activation, which the
+GPU stores between its linear kernels and the activation launch, and its gradient on both sides of
+the multiplication by A'), everything else in fp32 -- so the whole-step gradient test can use
 the per-kernel tests' tight tolerances instead of the loose fp32-vs-bf16 bound.
 """
 from __future__ import annotations
@@ -59,6 +61,13 @@ class RefExecutor(Executor):
         """bf16 rounding at a HIP storage point (identity unless emulating bf16)."""
         return t.to(torch.bfloat16).to(torch.float32) if self.emulate_bf16 else t
 
+    def _act_slope(self, stage, out, dropped: bool):
+        """A' of a stage with a hidden activation from its STORED output: the dropout scale is
+        undone first (y = out * fp32(1 - rate), as act_bwd_kernel does; dropped elements carry a
+        zero gradient already)."""
+        y = out * torch.tensor(1.0 - stage.rate, dtype=torch.float32) if dropped else out
+        return R.act_grad_from_output(stage.act, stage.act_alpha, y)
+
     def _forward(self, x, training: bool, step: int):
         st = self.store
         saved = []
@@ -68,16 +77,25 @@ class RefExecutor(Executor):
             b = st.view(cs.conv, "bias") if cs.conv.use_bias else None
             z = R.conv2d(a, w, b, cs.stride, cs.conv.padding)
             r = torch.relu(z) if cs.relu else z
+            if cs.act is not None:
+                # Keras' order: activate, then pool (the GPU pools the linear conv, then activates:
+                # the same for a non-decreasing function)
+                r = R.act(cs.act, cs.act_alpha, self._q(z))
             code = None
             p = r
             if cs.pool is not None:
                 p, code = R.maxpool2x2(r)
+                if cs.act is not None and self.emulate_bf16:
+                    # the bf16 rounding of the pre-activation ties neighbours that the GPU's linear
+                    # kernel, which takes the argmax on its fp32 accumulators, never sees tied: the
+                    # codes from z (the values are the same: A and the rounding are non-decreasing)
+                    code = R.maxpool2x2(z)[1]
             mask = None
             if training and cs.rate > 0:
                 mask = self._mask(p.numel(), cs.rate, cs.stream, step).view(p.shape)
                 p = p * mask
-            saved.append((a, r, code, mask))
-            a = self._q(p)
+            a_in, a = a, self._q(p)
+            saved.append((a_in, r, code, mask, a))
         a = a.reshape(a.shape[0], -1)
         for ds in self.plan.denses:
             w = self._q(st.view(ds.dense, "kernel"))
@@ -85,12 +103,14 @@ class RefExecutor(Executor):
             if ds.dense.use_bias:
                 z = z + st.view(ds.dense, "bias")
             r = torch.relu(z) if ds.relu else z
+            if ds.act is not None:
+                r = R.act(ds.act, ds.act_alpha, self._q(z))
             mask = None
             if training and ds.rate > 0:
                 mask = self._mask(r.numel(), ds.rate, ds.stream, step).view(r.shape)
                 r = r * mask
-            saved.append((a, z, None, mask))
-            a = self._q(r)
+            a_in, a = a, self._q(r)
+            saved.append((a_in, z, None, mask, a))
         hd = self.plan.head
         z = a @ st.view(hd.dense, "kernel")
         if hd.dense.use_bias:
@@ -122,11 +142,13 @@ class RefExecutor(Executor):
         nconv = len(self.plan.convs)
         for i in reversed(range(len(self.plan.denses))):
             ds = self.plan.denses[i]
-            a_in, z, _, mask = saved[nconv + i]
+            a_in, z, _, mask, out = saved[nconv + i]
             if mask is not None:
                 da = da * mask
             if ds.relu:
                 da = da * (z > 0).to(da.dtype)
+            if ds.act is not None:                             # (the masked gradient is stored first)
+                da = self._q(da) * self._act_slope(ds, out, mask is not None)
             da = self._q(da)                                   # the stored bf16 dH
             st.view(ds.dense, "kernel", grad=True).copy_(a_in.t() @ da)
             if ds.dense.use_bias:
@@ -137,7 +159,7 @@ class RefExecutor(Executor):
             da = da.reshape((da.shape[0],) + tuple(cs_last.out_shape))
         for i in reversed(range(nconv)):
             cs = self.plan.convs[i]
-            a_in, r, code, mask = saved[i]
+            a_in, r, code, mask, out = saved[i]
             if mask is not None:
                 da = da * mask
             if self.emulate_bf16:
@@ -147,6 +169,8 @@ class RefExecutor(Executor):
                     pooled = R.maxpool2x2(r)[0] if cs.pool is not None else r
                     da = da * (pooled > 0).to(da.dtype)
                 da = self._q(da)
+            if cs.act is not None:
+                da = self._q(da * self._act_slope(cs, out, mask is not None))
             if cs.pool is not None:
                 da = R.maxpool2x2_backward(da, code, r.shape[1:3])
             if cs.relu:

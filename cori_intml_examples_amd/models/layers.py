@@ -58,7 +58,8 @@ class KTensor:
 
 
 class Layer:
-    activation_names = (None, "linear", "relu", "softmax", "sigmoid")
+    activation_names = (None, "linear", "relu", "softmax", "sigmoid", "tanh", "hard_sigmoid", "elu", "selu",
+                        "softplus", "softsign")
 
     def __init__(self, name: Optional[str] = None, input_shape=None, trainable: bool = True, **kw):
         self.name = name or unique_name(_snake(type(self).__name__))
@@ -375,4 +376,63 @@ class Dense(_Regularized, Layer):
         return super().from_config(cfg)
 
 
-LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense)}
+class Activation(Layer):
+    """``keras.layers.Activation``: folded by the plan into the Conv2D / Dense directly before it."""
+
+    def __init__(self, activation, **kw):
+        super().__init__(**kw)
+        self.activation = _check_act(activation)
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg["activation"] = self.activation or "linear"
+        return cfg
+
+
+def _alpha32(layer, alpha) -> float:
+    """Keras stores alpha through ``K.cast_to_floatx``: an fp32 value (0.3 -> 0.30000001192092896)."""
+    import numpy as np
+    a = float(np.float32(alpha))
+    if not a >= 0.0 or a == float("inf"):
+        raise ValueError("layer %s: alpha = %r; a negative (or non-finite) alpha makes the function non-monotone, "
+                         "which the pooled stages rely on" % (layer.name, alpha))
+    return a
+
+
+class LeakyReLU(Layer):
+    """``keras.layers.LeakyReLU``: x > 0 ? x : alpha * x, alpha >= 0."""
+
+    def __init__(self, alpha=0.3, **kw):
+        super().__init__(**kw)
+        self.alpha = _alpha32(self, alpha)
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg["alpha"] = self.alpha
+        return cfg
+
+
+class ELU(Layer):
+    """``keras.layers.ELU``: x > 0 ? x : alpha * (exp(x) - 1), alpha >= 0."""
+
+    def __init__(self, alpha=1.0, **kw):
+        super().__init__(**kw)
+        self.alpha = _alpha32(self, alpha)
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg["alpha"] = self.alpha
+        return cfg
+
+
+def activation_of(layer):
+    """(name, alpha) an activation-type layer applies: ('relu' | None | a table name, alpha)."""
+    if isinstance(layer, LeakyReLU):
+        return "leaky_relu", layer.alpha
+    if isinstance(layer, ELU):
+        return "elu", layer.alpha
+    return layer.activation, 1.0 if layer.activation == "elu" else 0.0
+
+
+LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
+                                         LeakyReLU, ELU)}

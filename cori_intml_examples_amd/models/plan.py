@@ -8,6 +8,12 @@ family on gfx950:
   DenseStage  Dense(+ReLU) [+Dropout]                   -> dense split-K + epilogue
   HeadStage   final Dense + softmax/sigmoid + loss      -> head_fused (fwd+loss+bwd)
 
+A hidden activation other than relu / linear (``act``: a name of ops/reference.py ACTIVATIONS,
+from the layer's ``activation=`` or from an Activation / LeakyReLU / ELU layer directly behind a
+linear Conv2D / Dense) makes the stage ``dropout(A(maxpool(conv)))``: its kernels run in their
+linear form and one element-wise launch per direction follows them (act.hip).  A is
+non-decreasing, so this equals Keras' ``maxpool(A(conv))``.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -16,7 +22,8 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .layers import Conv2D, Dense, Dropout, Flatten, InputLayer, Layer, MaxPooling2D
+from .layers import (ELU, Activation, Conv2D, Dense, Dropout, Flatten, InputLayer, Layer, LeakyReLU, MaxPooling2D,
+                     activation_of)
 from ..ops.reference import conv_pads
 
 
@@ -30,6 +37,8 @@ class ConvStage:
     pool: Optional[MaxPooling2D] = None
     dropout: Optional[Dropout] = None
     stream: int = 0                         # RNG stream id of the dropout
+    act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
+    act_alpha: float = 0.0
 
     @property
     def rate(self) -> float:
@@ -55,6 +64,8 @@ class DenseStage:
     dropout: Optional[Dropout] = None
     stream: int = 0
     flat_from: Optional[Tuple[int, int, int]] = None   # (H,W,C) if the input comes from a Flatten
+    act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
+    act_alpha: float = 0.0
 
     @property
     def rate(self) -> float:
@@ -94,6 +105,20 @@ def canonical_loss(loss) -> str:
     return aliases[name]
 
 
+ACT_LAYERS = (Activation, LeakyReLU, ELU)
+
+
+def _stage_act(layer, name, alpha, what):
+    """(relu, act, act_alpha) of a hidden stage whose activation is ``name``."""
+    if name is None:
+        return False, None, 0.0
+    if name == "relu":
+        return True, None, 0.0
+    if name == "softmax":
+        raise NotImplementedError("%s activation softmax (layer %s): softmax is an output activation" % (what, layer.name))
+    return False, name, float(alpha)
+
+
 def build_plan(layers: List[Layer], loss) -> Plan:
     """``layers`` is the linear chain starting with an InputLayer."""
     if not layers or not isinstance(layers[0], InputLayer):
@@ -105,19 +130,44 @@ def build_plan(layers: List[Layer], loss) -> Plan:
     flat_from = None
     body = layers[1:]
     stream = 0
+    open_stage = None          # (stage, its Conv2D / Dense): an activation layer may still fold into it
+    prev = layers[0]
+    skip = False
     for i, layer in enumerate(body):
         last = i == len(body) - 1
-        if isinstance(layer, Conv2D):
+        before, prev = prev, layer
+        if skip:                # the output Activation layer, taken by the head Dense before it
+            skip = False
+            continue
+        if not isinstance(layer, ACT_LAYERS + (Conv2D, Dense)):
+            open_stage = None
+        if isinstance(layer, ACT_LAYERS):
+            name, alpha = activation_of(layer)
+            if open_stage is None:
+                owner = before if isinstance(before, (Conv2D, Dense)) else None
+                if owner is not None and owner.activation is not None:
+                    raise NotImplementedError("layer %s follows %s, which already has the activation %s: two "
+                                              "activations on one stage" % (layer.name, owner.name, owner.activation))
+                raise NotImplementedError("layer %s follows %s: an activation layer must directly follow a Conv2D "
+                                          "or Dense (before any pooling, dropout or flatten)"
+                                          % (layer.name, before.name))
+            stage, owner = open_stage
+            if stage.relu or stage.act is not None:
+                raise NotImplementedError("layer %s follows %s and %s: two activations on one stage"
+                                          % (layer.name, owner.name, before.name))
+            stage.relu, stage.act, stage.act_alpha = _stage_act(layer, name, alpha, "hidden")
+            if name is not None:
+                open_stage = None
+        elif isinstance(layer, Conv2D):
             if plan.denses or flat_from is not None:
                 raise NotImplementedError("Conv2D after Flatten/Dense")
-            relu = layer.activation == "relu"
-            if layer.activation not in (None, "relu"):
-                raise NotImplementedError("conv activation %s" % layer.activation)
+            relu, act, alpha = _stage_act(layer, layer.activation, 1.0 if layer.activation == "elu" else 0.0, "conv")
             cur_conv = ConvStage(conv=layer, in_shape=tuple(layer.input_shape),
                                  conv_shape=tuple(layer.output_shape_),
-                                 out_shape=tuple(layer.output_shape_), relu=relu)
+                                 out_shape=tuple(layer.output_shape_), relu=relu, act=act, act_alpha=alpha)
             plan.convs.append(cur_conv)
             cur_dense = None
+            open_stage = (cur_conv, layer) if layer.activation is None else None
         elif isinstance(layer, MaxPooling2D):
             if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None:
                 raise NotImplementedError("MaxPooling2D must directly follow a Conv2D")
@@ -140,18 +190,27 @@ def build_plan(layers: List[Layer], loss) -> Plan:
             if len(layer.input_shape) != 1:
                 raise ValueError("Dense on non-flat input")
             ff = flat_from if not plan.denses else None
-            if last:
+            open_stage = None
+            out_act = body[i + 1] if i == len(body) - 2 and isinstance(body[i + 1], ACT_LAYERS) else None
+            if last or out_act is not None:
                 act = layer.activation
+                if out_act is not None:
+                    # Dense(n) + Activation("softmax" | "sigmoid") as the last two layers: the head
+                    if act is not None:
+                        raise NotImplementedError("layer %s follows %s, which already has the activation %s: two "
+                                                  "activations on one stage" % (out_act.name, layer.name, act))
+                    act, skip = activation_of(out_act)[0], True
                 if act not in (None, "softmax", "sigmoid"):
                     raise NotImplementedError("output activation %s" % act)
                 plan.head = HeadStage(dense=layer, K=layer.input_shape[0], N=layer.units,
                                       activation=act, loss=loss, flat_from=ff)
             else:
-                if layer.activation not in (None, "relu"):
-                    raise NotImplementedError("hidden Dense activation %s" % layer.activation)
+                relu, act, alpha = _stage_act(layer, layer.activation, 1.0 if layer.activation == "elu" else 0.0,
+                                              "hidden Dense")
                 cur_dense = DenseStage(dense=layer, K=layer.input_shape[0], N=layer.units,
-                                       relu=layer.activation == "relu", flat_from=ff)
+                                       relu=relu, flat_from=ff, act=act, act_alpha=alpha)
                 plan.denses.append(cur_dense)
+                open_stage = (cur_dense, layer) if layer.activation is None else None
             cur_conv = None
         else:
             raise NotImplementedError("layer type %s" % type(layer).__name__)

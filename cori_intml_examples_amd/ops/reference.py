@@ -94,6 +94,61 @@ def maxpool2x2_backward(dy: torch.Tensor, code: torch.Tensor, in_hw: Tuple[int, 
     return out
 
 
+# --------------------------------------------------------------------------- activations
+# The hidden activations beyond relu / linear (Keras 2.2.4 keras/activations.py and the
+# LeakyReLU / ELU layers): name -> whether it takes an alpha.  Every function is non-decreasing
+# and every derivative is a function of the OUTPUT, clamped to >= 0.
+ACTIVATIONS = {"tanh": False, "sigmoid": False, "hard_sigmoid": False, "elu": True, "selu": False,
+               "softplus": False, "softsign": False, "leaky_relu": True}
+SELU_SCALE, SELU_ALPHA = 1.0507009873554805, 1.6732632423543772
+
+
+def act(name: str, alpha: float, x: torch.Tensor) -> torch.Tensor:
+    """A(x) of the activation table, in x's dtype (fp32 twin of act_fwd_kernel)."""
+    if name == "tanh":
+        return torch.tanh(x)
+    if name == "sigmoid":
+        return 1.0 / (1.0 + torch.exp(-x))
+    if name == "hard_sigmoid":
+        v = 0.2 * x + 0.5
+        return torch.where(v < 0, torch.zeros_like(v), torch.where(v > 1, torch.ones_like(v), v))
+    if name == "elu":
+        return torch.where(x > 0, x, alpha * torch.expm1(x))
+    if name == "selu":
+        return SELU_SCALE * torch.where(x > 0, x, SELU_ALPHA * torch.expm1(x))
+    if name == "softplus":
+        return torch.where(x > 0, x, torch.where(x < 0, torch.zeros_like(x), x)) + torch.log1p(torch.exp(-x.abs()))
+    if name == "softsign":
+        return torch.where(torch.isinf(x), torch.sign(x), x / (1.0 + x.abs()))
+    if name == "leaky_relu":
+        neg = torch.zeros_like(x) if alpha == 0 else alpha * x      # (alpha = 0 is relu, also at -inf)
+        return torch.where(x > 0, x, torch.where(x < 0, neg, alpha * x))
+    raise NotImplementedError("activation %r" % (name,))
+
+
+def act_grad_from_output(name: str, alpha: float, y: torch.Tensor) -> torch.Tensor:
+    """dA/dx as a function of the output y = A(x), clamped to >= 0 (fp32 twin of act_bwd_kernel)."""
+    zero = torch.zeros_like(y)
+    if name == "tanh":
+        return torch.maximum(zero, 1.0 - y * y)
+    if name == "sigmoid":
+        return torch.maximum(zero, y * (1.0 - y))
+    if name == "hard_sigmoid":
+        return torch.where((y > 0) & (y < 1), torch.full_like(y, 0.2), zero)
+    if name == "elu":
+        return torch.where(y > 0, torch.ones_like(y), torch.maximum(zero, y + alpha))
+    if name == "selu":
+        return torch.where(y > 0, torch.full_like(y, SELU_SCALE), torch.maximum(zero, y + SELU_SCALE * SELU_ALPHA))
+    if name == "softplus":
+        return torch.maximum(zero, -torch.expm1(-y))
+    if name == "softsign":
+        d = 1.0 - torch.minimum(y.abs(), torch.ones_like(y))
+        return d * d
+    if name == "leaky_relu":
+        return torch.where(y > 0, torch.ones_like(y), torch.full_like(y, alpha))
+    raise NotImplementedError("activation %r" % (name,))
+
+
 # --------------------------------------------------------------------------- losses
 def softmax_cce(logits: torch.Tensor, y: torch.Tensor):
     """Keras categorical_crossentropy on a softmax output (TF backend semantics).
