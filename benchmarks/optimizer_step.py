@@ -1,7 +1,7 @@
 """Step time of the RPV CNN ([16,32,64]/[128], 64x64x3, B=128) per optimizer on one GPU.
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
-                                        [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]]
+                                        [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -23,7 +23,11 @@ the two is the cost of the weight regularizers.
 takes, without the activation launches) and one ``<name>/<activation>`` model per name (that
 structure plus one ``act_fwd`` and one ``act_bwd`` launch per hidden stage).  The difference between
 those is the cost of the activation launches; the difference between ``<name>`` and
-``<name>/perlayer`` is the cost of leaving the fused conv stack."""
+``<name>/perlayer`` is the cost of leaving the fused conv stack.
+
+``--batch-norm`` adds ``<name>/perlayer`` likewise and ``<name>/bn`` (a BatchNormalization between
+every hidden Conv2D / Dense and its relu: that structure plus ``bn_stats``, ``bn_apply_fwd``,
+``bn_bwd_reduce`` and ``bn_bwd_apply`` per hidden stage, whose conv kernels run un-pooled)."""
 import argparse
 import json
 import os
@@ -51,9 +55,9 @@ def make_opt(name, **kw):
     return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
 
 
-def variants(names, clipnorm, l2=None, activations=()):
+def variants(names, clipnorm, l2=None, activations=(), batch_norm=False):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
-    hidden activation)]"""
+    hidden activation -- or "relu+bn": relu behind a BatchNormalization)]"""
     out = []
     for nm in names:
         out.append((nm, nm, {}, None, 0.0, "relu"))
@@ -63,8 +67,10 @@ def variants(names, clipnorm, l2=None, activations=()):
             out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None, 0.0, "relu"))
         if l2:
             out.append((nm + "/l2", nm, {}, None, l2, "relu"))
-        if activations:
+        if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
+        if batch_norm:
+            out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
             out.append((nm + "/" + act, nm, {}, None, 0.0, act))
     return out
@@ -98,8 +104,9 @@ def main():
     ap.add_argument("--clipnorm", type=float, default=None)
     ap.add_argument("--l2", type=float, default=None)
     ap.add_argument("--activation", default="", help="comma-separated hidden activations to time")
+    ap.add_argument("--batch-norm", action="store_true", help="time the model with BatchNormalization layers")
     a = ap.parse_args()
-    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n])
+    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n], a.batch_norm)
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -112,7 +119,8 @@ def main():
         with tuned(tv):
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
                             optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
-                            **({"activation": act} if act != "relu" else {}))
+                            **({"batch_norm": True} if act == "relu+bn" else {}),
+                            **({"activation": act} if act not in ("relu", "relu+bn") else {}))
         ex = m._executor
         d = ex.upload(x, y)
         perm = torch.arange(d.n, device=ex.device)

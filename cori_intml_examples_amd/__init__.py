@@ -8,5 +8,5 @@ random / genetic / grid hyper-parameter search with live monitoring widgets.
 __version__ = "0.1.0"
 
 from . import activations, models, optim, regularizers, train, utils  # noqa: F401
-from .models import (ELU, Activation, Conv2D, Dense, Dropout, Flatten, Input, LeakyReLU, MaxPooling2D,  # noqa: F401
-                     Model, Sequential, load_model)
+from .models import (ELU, Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, Input,  # noqa: F401
+                     LeakyReLU, MaxPooling2D, Model, Sequential, load_model)

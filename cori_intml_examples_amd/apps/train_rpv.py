@@ -44,6 +44,8 @@ def build_parser():
     p.add_argument("--activation", default="relu",
                    help="hidden activation of every Conv2D / Dense: relu, tanh, sigmoid, hard_sigmoid, elu, selu, "
                         "softplus, softsign")
+    p.add_argument("--batch-norm", action="store_true",
+                   help="a BatchNormalization between every hidden Conv2D / Dense and its activation")
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--n-epochs", type=int, default=4)
     p.add_argument("--fom", choices=["best", "last"])
@@ -91,7 +93,8 @@ def main(argv=None):
     model = build_model(train_input.shape[1:], conv_sizes=[args.h1, args.h2, args.h3], fc_sizes=[args.h4],
                         dropout=args.dropout,
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
-                        use_horovod=True, l2=args.l2, activation=args.activation)
+                        use_horovod=True, l2=args.l2, activation=args.activation,
+                        batch_norm=args.batch_norm)
     if hvd.rank() == 0:
         model.summary()
 

@@ -8,7 +8,8 @@
 """
 from __future__ import annotations
 
-from ..models import Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model, Sequential
+from ..models import (Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model,
+                      Sequential)
 from .. import optim as optimizers
 from .. import regularizers
 
@@ -17,6 +18,20 @@ def _kernel_l2(l2):
     """Layer keywords of the builders' ``l2=``: an l2 kernel regularizer on every Conv2D / Dense
     (not on biases); nothing at all for 0 -- exactly the unregularized model."""
     return {"kernel_regularizer": regularizers.l2(l2)} if l2 else {}
+
+
+def _hidden(layer_cls, *args, activation="relu", batch_norm=False, **kw):
+    """The layers of one hidden Conv2D / Dense: the layer itself, or with ``batch_norm`` its linear
+    form, a BatchNormalization and the activation as a layer (ahead of the stage's pool / dropout)."""
+    if not batch_norm:
+        return [layer_cls(*args, activation=activation, **kw)]
+    return [layer_cls(*args, **kw), BatchNormalization(), Activation(activation)]
+
+
+def _chain(h, layers):
+    for layer in layers:
+        h = layer(h)
+    return h
 
 
 def clipped_optimizer(optimizer: str, lr=None, clipnorm=None, clipvalue=None):
@@ -42,16 +57,21 @@ def _opt(optimizer, lr, use_horovod):
 
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
-              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu", l2=0.0):
-    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
+              n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu",
+              batch_norm=False, l2=0.0):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
+    Activation(activation)."""
     reg = _kernel_l2(l2)
+    hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     m = Sequential(device=device)
-    m.add(Conv2D(h1, (3, 3), activation=activation, input_shape=input_shape, **reg))
-    m.add(Conv2D(h2, (3, 3), activation=activation, **reg))
+    for layer in (_hidden(Conv2D, h1, (3, 3), input_shape=input_shape, **hid) + _hidden(Conv2D, h2, (3, 3), **hid)):
+        m.add(layer)
     m.add(MaxPooling2D(pool_size=(2, 2)))
     m.add(Dropout(dropout))
     m.add(Flatten())
-    m.add(Dense(h3, activation=activation, **reg))
+    for layer in _hidden(Dense, h3, **hid):
+        m.add(layer)
     m.add(Dropout(dropout if dropout2 is None else dropout2))
     m.add(Dense(n_classes, activation="softmax", **reg))
     m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy",
@@ -60,18 +80,21 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
-            use_horovod=False, device=None, activation="relu", l2=0.0):
-    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
+            use_horovod=False, device=None, activation="relu", batch_norm=False, l2=0.0):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
+    Activation(activation)."""
     reg = _kernel_l2(l2)
+    hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     inputs = Input(shape=input_shape)
     h = inputs
     for c in conv_sizes:
-        h = Conv2D(c, kernel_size=(3, 3), activation=activation, padding="same", **reg)(h)
+        h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), padding="same", **hid))
         h = MaxPooling2D(pool_size=(2, 2))(h)
     h = Dropout(dropout)(h)
     h = Flatten()(h)
     for f in fc_sizes:
-        h = Dense(f, activation=activation, **reg)(h)
+        h = _chain(h, _hidden(Dense, f, **hid))
         h = Dropout(dropout)(h)
     outputs = Dense(1, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
@@ -80,15 +103,16 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
 
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
-                   use_horovod=False, device=None, activation="relu"):
-    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model)."""
-    inputs = Input(shape=input_shape)
-    h = Conv2D(h1, kernel_size=(3, 3), activation=activation, strides=1, padding="same")(inputs)
-    h = Conv2D(h2, kernel_size=(3, 3), activation=activation, strides=2, padding="same")(h)
-    h = Conv2D(h3, kernel_size=(3, 3), activation=activation, strides=1, padding="same")(h)
-    h = Conv2D(h4, kernel_size=(3, 3), activation=activation, strides=2, padding="same")(h)
+                   use_horovod=False, device=None, activation="relu", batch_norm=False):
+    """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
+    Activation(activation)."""
+    hid = dict(activation=activation, batch_norm=batch_norm)
+    h = inputs = Input(shape=input_shape)
+    for c, st in ((h1, 1), (h2, 2), (h3, 1), (h4, 2)):
+        h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), strides=st, padding="same", **hid))
     h = Flatten()(h)
-    h = Dense(h5, activation=activation)(h)
+    h = _chain(h, _hidden(Dense, h5, **hid))
     outputs = Dense(1, activation="sigmoid")(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
     model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])

@@ -57,7 +57,8 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
                    backend=lambda: "tensorflow", get_value=_opt.get_value, set_value=_opt.set_value)
     layers = _mod("keras.layers", **{k: getattr(_layers, k) for k in
                                      ("Input", "InputLayer", "Conv2D", "MaxPooling2D", "MaxPool2D", "Dropout",
-                                      "Flatten", "Dense", "Activation", "LeakyReLU", "ELU", "Layer")
+                                      "Flatten", "Dense", "Activation", "LeakyReLU", "ELU", "BatchNormalization",
+                                      "Layer")
                                      if hasattr(_layers, k)})
     if not hasattr(layers, "MaxPool2D"):
         layers.MaxPool2D = _layers.MaxPooling2D

@@ -576,3 +576,41 @@ struct ActArgs {
   const StepState* st = nullptr;   // fwd: the dropout counter's step (null: 0)
   float y_scale = 1.f;             // bwd only
 };
+
+// Keras BatchNormalization of a stage (bn.hip): bn_stats -> bn_apply_fwd in the forward,
+// bn_bwd_reduce -> bn_bwd_apply in the backward, all over the stage's un-pooled pre-activation
+// z [rows][Cs] bf16 (rows = B * Ho * Wo of a conv stage, B of a dense stage; C <= Cs real channels).
+// chunk / nchunks / gp_log2 are bn_plan(rows, Cs)'s: rows per statistics chunk (at most
+// BN_MAX_CHUNKS chunks of at least BN_MIN_CHUNK rows), and log2 of the 8-channel groups a
+// workgroup holds side by side.
+#define BN_THREADS 256
+#define BN_MIN_CHUNK 1024
+#define BN_MAX_CHUNKS 256
+struct BnArgs {
+  const bf16* z = nullptr;
+  long long rows = 0;
+  int C = 0, Cs = 0;
+  int chunk = 0, nchunks = 0, gp_log2 = 0;
+  // conv geometry of a pooled stage (pool = 0: Hp x Wp unused, the output has z's resolution)
+  int B = 0, Ho = 1, Wo = 1, Hp = 1, Wp = 1, pool = 0;
+  float* part = nullptr;           // [2][nchunks][Cs]: chunk means, chunk sums of squares about them
+  float* saved = nullptr;          // [2][Cs]: the step's mean, 1 / sqrt(var + eps)
+  const float* gamma = nullptr;    // [C] (null: ones)
+  const float* beta = nullptr;     // [C] (null: zeros)
+  float* moving_mean = nullptr;    // [C]: updated by a training bn_apply_fwd, read by an evaluation one
+  float* moving_var = nullptr;
+  float eps = 1e-3f, momentum = 0.99f;
+  float unbias = 1.f;              // m / (m - (1 + eps)): Keras 2.2.4's sample-variance factor
+  int training = 0;                // bn_apply_fwd: batch statistics + moving update, else moving statistics
+  int relu = 0;
+  bf16* out = nullptr;             // [rows or B * Hp * Wp][Cs]
+  uint8_t* code = nullptr;         // pooled: argmax codes (dy * 2 + dx, first maximum), conv_code's format
+  uint32_t drop_thr = 0;           // 0: no dropout
+  float drop_scale = 1.f;
+  uint32_t seed = 0, stream_id = 0;
+  const StepState* st = nullptr;   // the dropout counter's step (null: 0)
+  // backward
+  const bf16* dp = nullptr;        // gradient wrt the stage output, at its (pooled) resolution
+  float* slab = nullptr;           // [nchunks][2][C]: partial dgamma, partial dbeta (gamma / beta's store order)
+  bf16* dz = nullptr;              // [rows][Cs]
+};

@@ -65,6 +65,11 @@ int reg_blocks(const RegArgs& a);
 void reg_set_ranges(RegArgs& a, const int* lo, const int* hi, const float* l1, const float* l2, int count);
 void launch_act_fwd(const ActArgs& a, hipStream_t s);
 void launch_act_bwd(const ActArgs& a, hipStream_t s);
+void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
+void launch_bn_stats(const BnArgs& a, hipStream_t s);
+void launch_bn_apply_fwd(const BnArgs& a, hipStream_t s);
+void launch_bn_bwd_reduce(const BnArgs& a, hipStream_t s);
+void launch_bn_bwd_apply(const BnArgs& a, hipStream_t s);
 int xgmi_grid(const XgmiArgs& a);
 void launch_xgmi_allreduce(const XgmiArgs& a, hipStream_t s);
 uintptr_t xgmi_alloc_uncached(size_t bytes, bool finegrained);
@@ -351,6 +356,7 @@ PYBIND11_MODULE(_kernels, m) {
   static_assert(sizeof(PackRoute) == 56 && offsetof(PackRoute, fwd) == 40, "PackRoute layout (models/plan routes)");
   m.attr("PACK_ROUTE_BYTES") = (int)sizeof(PackRoute);
   m.attr("MAX_ROUTES") = MAX_ROUTES;
+  m.attr("MAX_RED") = MAX_RED;
   m.attr("STEP_STATE_METRICS_OFFSET") = (int)offsetof(StepState, metric_slots);
   m.attr("STEP_STATE_METRIC_SLOTS") = 16;
   m.attr("STEP_STATE_MSCHED_OFFSET") = (int)offsetof(StepState, m_schedule);
@@ -525,6 +531,30 @@ PYBIND11_MODULE(_kernels, m) {
   }
   m.def("act_fwd", [](const ActArgs& a, uintptr_t s) { launch_act_fwd(a, S(s)); check_last("act_fwd"); });
   m.def("act_bwd", [](const ActArgs& a, uintptr_t s) { launch_act_bwd(a, S(s)); check_last("act_bwd"); });
+  // Keras BatchNormalization (bn.hip): two launches per direction around a stage's linear kernels
+  py::class_<BnArgs>(m, "BnArgs")
+      .def(py::init<>())
+      PTR(BnArgs, z) RW(BnArgs, rows) RW(BnArgs, C) RW(BnArgs, Cs) RW(BnArgs, chunk) RW(BnArgs, nchunks)
+      RW(BnArgs, gp_log2) RW(BnArgs, B) RW(BnArgs, Ho) RW(BnArgs, Wo) RW(BnArgs, Hp) RW(BnArgs, Wp) RW(BnArgs, pool)
+      PTR(BnArgs, part) PTR(BnArgs, saved) PTR(BnArgs, gamma) PTR(BnArgs, beta) PTR(BnArgs, moving_mean)
+      PTR(BnArgs, moving_var) RW(BnArgs, eps) RW(BnArgs, momentum) RW(BnArgs, unbias) RW(BnArgs, training)
+      RW(BnArgs, relu) PTR(BnArgs, out) PTR(BnArgs, code) RW(BnArgs, drop_thr) RW(BnArgs, drop_scale)
+      RW(BnArgs, seed) RW(BnArgs, stream_id) PTR(BnArgs, st) PTR(BnArgs, dp) PTR(BnArgs, slab) PTR(BnArgs, dz);
+  m.attr("BN_MIN_CHUNK") = BN_MIN_CHUNK;
+  m.attr("BN_MAX_CHUNKS") = BN_MAX_CHUNKS;
+  m.attr("BN_THREADS") = BN_THREADS;
+  m.def("bn_plan", [](long long rows, int Cs) {
+    int chunk, nchunks, lg;
+    bn_plan(rows, Cs, &chunk, &nchunks, &lg);
+    return py::make_tuple(chunk, nchunks, lg);
+  });
+  m.def("bn_stats", [](const BnArgs& a, uintptr_t s) { launch_bn_stats(a, S(s)); check_last("bn_stats"); });
+  m.def("bn_apply_fwd",
+        [](const BnArgs& a, uintptr_t s) { launch_bn_apply_fwd(a, S(s)); check_last("bn_apply_fwd"); });
+  m.def("bn_bwd_reduce",
+        [](const BnArgs& a, uintptr_t s) { launch_bn_bwd_reduce(a, S(s)); check_last("bn_bwd_reduce"); });
+  m.def("bn_bwd_apply",
+        [](const BnArgs& a, uintptr_t s) { launch_bn_bwd_apply(a, S(s)); check_last("bn_bwd_apply"); });
   m.def("pack", [](uintptr_t master, uintptr_t arena, const PackTable& t, uintptr_t s) {
     launch_pack(reinterpret_cast<const float*>(master), reinterpret_cast<bf16*>(arena), t, S(s)); check_last("pack"); });
 

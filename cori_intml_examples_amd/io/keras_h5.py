@@ -94,7 +94,8 @@ def _opt_layout(opt, n_params):
 
 
 def _param_specs(model):
-    return list(model.store.specs) if model.store is not None else []
+    """The specs an optimizer has slots for: trainable tensors only, as Keras writes them."""
+    return [s for s in model.store.specs if s.trainable] if model.store is not None else []
 
 
 # ----------------------------------------------------------------------------- save

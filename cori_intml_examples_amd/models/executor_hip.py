@@ -10,7 +10,10 @@ boundaries"), captured once per batch size into a HIP graph and replayed:
   slab_reduce -> grad_sqnorm -> grad_clip_apply -> RCCL all-reduce -> optim; a model with weight
   regularizers: slab_reduce -> weight_reg -> [grad_sqnorm ..] as above, and head -> weight_reg in
   an evaluation step; a stage with a hidden activation other than relu / linear: its linear
-  forward kernels -> act_fwd, and the launch that stores its gradient -> act_bwd)
+  forward kernels -> act_fwd, and the launch that stores its gradient -> act_bwd; a stage with a
+  BatchNormalization: its linear forward kernels (un-pooled) -> bn_stats -> bn_apply_fwd [-> act_fwd],
+  and the launch that stores its gradient [-> act_bwd] -> bn_bwd_reduce -> bn_bwd_apply -> its wgrad /
+  dgrad in their un-pooled linear form)
 
 Activations are bf16 NHWC with channel strides padded to 8 (input: 4); weights live in
 ONE fp32 master buffer (Keras layout) and are mirrored into bf16 fragment-major packs by
@@ -21,7 +24,8 @@ from __future__ import annotations
 
 import gc
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
+from types import SimpleNamespace
 from operator import attrgetter
 from typing import Dict, List, Optional, Tuple
 
@@ -94,6 +98,7 @@ class ConvGeo:
     pack_dgrad: int = -1
     act: Optional[str] = None      # hidden activation other than relu / linear (plan.ConvStage.act)
     act_alpha: float = 0.0
+    bn: Optional[object] = None    # the stage's BatchNormalization layer (plan.ConvStage.bn)
 
 
 @dataclass
@@ -114,6 +119,7 @@ class DenseGeo:
     pack_bwd: int = -1
     act: Optional[str] = None      # hidden activation other than relu / linear (plan.DenseStage.act)
     act_alpha: float = 0.0
+    bn: Optional[object] = None    # the stage's BatchNormalization layer (plan.DenseStage.bn)
 
 
 class HipExecutor(Executor):
@@ -204,7 +210,7 @@ class HipExecutor(Executor):
             kh, kw = cs.conv.kernel_size
             g = ConvGeo(i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
                         cs.pool is not None, cs.relu, cs.rate, cs.stream)
-            g.act, g.act_alpha = cs.act, cs.act_alpha
+            g.act, g.act_alpha, g.bn = cs.act, cs.act_alpha, cs.bn
             g.KS = cdiv(kh * kw * Cs_in, 32)
             g.NT = cdiv(Cout, 16)
             if i > 0:
@@ -218,7 +224,7 @@ class HipExecutor(Executor):
             g = DenseGeo(j, src, ds.K, ds.N, r8(ds.N), ds.relu, ds.rate, ds.stream)
             if g.K != src.H * src.W * src.C:
                 raise ValueError("dense %d input width mismatch" % j)
-            g.act, g.act_alpha = ds.act, ds.act_alpha
+            g.act, g.act_alpha, g.bn = ds.act, ds.act_alpha, ds.bn
             g.KS = cdiv(src.width, 32)
             g.NT = cdiv(ds.N, 16)
             if j > 0 or self.convs:
@@ -573,6 +579,7 @@ class BatchPlan(GeometryMixin):
         self.wgrad_slabs = []
         self.dense_fused_opt = []          # (WgradArgs, params) updated inside dense_wgrad
         self.bucket_tables, self.bucket_ready = [], []
+        self.bucket_overflow = {}          # bucket -> further RedTables (more than MAX_RED descriptors)
         self._no_packs = K.PackTable()     # a comm-stream optimizer re-packs nothing
         self._ncu = self._zero16 = None    # hip_geometry: CU count, the DMA kernels' zero bytes
         # Native RCCL data plane: the bucket all-reduces are part of the launch sequence (on
@@ -594,9 +601,20 @@ class BatchPlan(GeometryMixin):
         self.yb = z(bs, ex.plan.head.N, dt=torch.float32)
         self.wb = z(max(bs, 1), dt=torch.float32) if self.weighted else None   # gathered sample weights
         self.conv_out, self.conv_code, self.conv_dy = [], [], []
+        # BatchNormalization stages: ('conv' | 'dense', index) -> z (the un-pooled pre-activation the
+        # linear kernels store), dp (the gradient wrt the stage output, which the next stage's
+        # BwdThrough stores), the statistics partials, the saved mean / invstd, the dbeta / dgamma
+        # slabs and the BnArgs.  Such a stage's conv_dy / dense_dh is dz: un-pooled, what its wgrad
+        # and dgrad read as the dY of a linear stage
+        self.bn: Dict[Tuple[str, int], SimpleNamespace] = {}
         for g in ex.convs:
             self.conv_out.append(z(bs, g.Hp, g.Wp, g.Cs_out))
             self.conv_code.append(z(bs, g.Hp, g.Wp, g.Cs_out, dt=torch.uint8) if g.pool else None)
+            if g.bn is not None:
+                self.bn["conv", g.i] = self._bn_buffers(z, bs * g.Ho * g.Wo, (bs, g.Ho, g.Wo, g.Cs_out),
+                                                        (bs, g.Hp, g.Wp, g.Cs_out))
+                self.conv_dy.append(z(bs, g.Ho, g.Wo, g.Cs_out) if self.training else None)
+                continue
             # gradient wrt the stage OUTPUT resolution (pooled dP for pooled convs; the
             # full-resolution dY is rebuilt on load from dP + codes, never stored)
             self.conv_dy.append(z(bs, g.Hp, g.Wp, g.Cs_out) if self.training else None)
@@ -617,6 +635,8 @@ class BatchPlan(GeometryMixin):
             self.dense_splits.append((splits, kps))
             self.dense_part.append(z(splits, bs, g.NT * 16, dt=torch.float32))
             self.dense_dh.append(z(bs, g.Ns) if self.training else None)
+            if g.bn is not None:
+                self.bn["dense", g.j] = self._bn_buffers(z, bs, (bs, g.Ns), (bs, g.Ns))
         hd = ex.plan.head
         self.head_blocks = cdiv(bs, K.head_rows_per_block(False))   # re-set below if the head fuses the epilogue
         head_slab_blocks = cdiv(bs, K.head_rows_per_block(True))
@@ -627,6 +647,87 @@ class BatchPlan(GeometryMixin):
         self._build_args()
 
     # ---------------------------------------------------------------- helpers
+    def _bn_buffers(self, z, rows, z_shape, out_shape):
+        """The buffers of one BatchNormalization stage over ``rows`` rows (bn_plan's chunking)."""
+        Cs = z_shape[-1]
+        chunk, nchunks, gp_log2 = self.ex.K.bn_plan(max(rows, 1), Cs)
+        f32 = torch.float32
+        return SimpleNamespace(z=z(*z_shape), dp=z(*out_shape) if self.training else None,
+                               part=z(2, nchunks, Cs, dt=f32), saved=z(2, Cs, dt=f32),
+                               slab=None,
+                               plan=(chunk, nchunks, gp_log2), args=None)
+
+    def _bn_args(self, kind, g):
+        """The BnArgs of stage g ('conv' | 'dense'): one struct for the stage's four launches."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        b = self.bn[kind, g.i if kind == "conv" else g.j]
+        if b.args is not None:
+            return b.args
+        a = K.BnArgs()
+        bn = g.bn
+        a.z = b.z.data_ptr()
+        if kind == "conv":
+            a.rows, a.C, a.Cs = self.bs * g.Ho * g.Wo, g.Cout, g.Cs_out
+            a.B, a.Ho, a.Wo, a.Hp, a.Wp, a.pool = self.bs, g.Ho, g.Wo, g.Hp, g.Wp, int(g.pool)
+            out, code = self.conv_out[g.i], self.conv_code[g.i]
+            dz = self.conv_dy[g.i]
+        else:
+            a.rows, a.C, a.Cs = self.bs, g.N, g.Ns
+            a.B = self.bs
+            out, code, dz = self.dense_out[g.j], None, self.dense_dh[g.j]
+        a.chunk, a.nchunks, a.gp_log2 = b.plan
+        a.part, a.saved = b.part.data_ptr(), b.saved.data_ptr()
+        if bn.scale:
+            a.gamma = store.view(bn, "gamma").data_ptr()
+        if bn.center:
+            a.beta = store.view(bn, "beta").data_ptr()
+        a.moving_mean = store.view(bn, "moving_mean").data_ptr()
+        a.moving_var = store.view(bn, "moving_variance").data_ptr()
+        m = a.rows
+        a.eps, a.momentum = bn.epsilon, bn.momentum
+        a.unbias = m / (m - (1.0 + bn.epsilon))     # Keras 2.2.4's sample-variance factor
+        a.training, a.relu = int(self.training), int(g.relu)
+        a.out = out.data_ptr()
+        if code is not None:
+            a.code = code.data_ptr()
+        # (a table activation's launch behind this one carries the dropout, as it does today)
+        if self.training and g.rate > 0 and g.act is None:
+            a.drop_thr, a.drop_scale = dropout_pair(g.rate)
+        a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
+        if self.training:
+            # the chunk slabs: [nchunks][dgamma[C], dbeta[C]]
+            b.slab = torch.zeros(b.plan[1], 2, a.C, dtype=torch.float32, device=ex.device)
+            a.dp, a.slab, a.dz = b.dp.data_ptr(), b.slab.data_ptr(), dz.data_ptr()
+        b.args = a
+        return a
+
+    def _add_bn_fwd(self, kind, g):
+        """Behind the stage's linear kernels: bn_stats (training) and bn_apply_fwd."""
+        K = self.ex.K
+        a = self._bn_args(kind, g)
+        tag = "%s%d" % (kind[0], g.i if kind == "conv" else g.j)
+        if self.training:
+            self._add("bn_stats_" + tag, lambda s, a=a: K.bn_stats(a, s), bn=a)
+        self._add("bn_apply_fwd_" + tag, lambda s, a=a: K.bn_apply_fwd(a, s), bn=a)
+
+    def _bn_descs(self, kind, g):
+        """(RedDescs, specs) of stage g's gamma / beta: the bn_bwd_reduce slabs [chunk][dgamma, dbeta]
+        as ONE bias-like reduction over gamma and beta, which are adjacent in the store (or over the
+        one of them the layer has)."""
+        if g.bn is None:
+            return [], []
+        store = self.ex.store
+        b = self.bn[kind, g.i if kind == "conv" else g.j]
+        _, nchunks, _ = b.plan
+        C = b.slab.shape[-1]
+        specs = [store.spec(g.bn, short) for short in ("gamma", "beta") if store.has(g.bn, short)]
+        if not specs:
+            return [], []
+        if len(specs) == 2 and specs[0].offset + C != specs[1].offset:
+            raise AssertionError("gamma and beta of %s are not adjacent in the parameter store" % g.bn.name)
+        first = b.slab[0, 0 if specs[0].short == "gamma" else 1]
+        return [RedDesc(first.data_ptr(), 2 * C, nchunks, 2 * C, specs[0].offset, C * len(specs), RED_BIAS)], specs
+
     def step_inputs(self):
         """(x [bs, R] bf16, y [bs, C] fp32) of this plan's last step: the gathered batch
         buffers, or -- prologue-free step -- the dataset rows the conv stack recorded."""
@@ -658,7 +759,7 @@ class BatchPlan(GeometryMixin):
             bt.pH, bt.pW, bt.pC, bt.pCs = g.Hp, g.Wp, g.Cout, g.Cs_out
             bt.cH, bt.cW = g.Ho, g.Wo
             rate, stream = g.rate, g.stream
-            bt.dy = self.conv_dy[g.i].data_ptr()
+            dyb = self.bn["conv", g.i].dp if g.bn is not None else self.conv_dy[g.i]
         else:
             g = ex.denses[src.idx]
             bt.prev_out = self.dense_out[g.j].data_ptr()
@@ -666,12 +767,12 @@ class BatchPlan(GeometryMixin):
             bt.pH, bt.pW, bt.pC, bt.pCs = 1, 1, g.N, g.Ns
             bt.cH, bt.cW = 1, 1
             rate, stream = g.rate, g.stream
-            bt.dy = self.dense_dh[g.j].data_ptr()
+            dyb = self.bn["dense", g.j].dp if g.bn is not None else self.dense_dh[g.j]
+        bt.dy = dyb.data_ptr()
         if rate > 0:
             bt.drop_thr, bt.drop_scale = dropout_pair(rate)
         bt.seed, bt.stream_id = ex.seed, stream
         # write-through gradient stores (16-byte sc1; byte offsets < 2 GB)
-        dyb = self.conv_dy[g.i] if src.kind == "conv" else self.dense_dh[g.j]
         bt.wt = int(bool(int(tune("wt")) & 2) and dyb.numel() * 2 < (1 << 31))
         return bt
 
@@ -687,9 +788,13 @@ class BatchPlan(GeometryMixin):
         a = K.ActArgs()
         if kind == "conv":
             out, grad = self.conv_out[g.i], self.conv_dy[g.i]
+            if g.bn is not None:
+                grad = self.bn["conv", g.i].dp
             a.rows, a.C, a.Cs = self.bs * g.Hp * g.Wp, g.Cout, g.Cs_out
         else:
             out, grad = self.dense_out[g.j], self.dense_dh[g.j]
+            if g.bn is not None:
+                grad = self.bn["dense", g.j].dp
             a.rows, a.C, a.Cs = self.bs, g.N, g.Ns
         a.act, a.alpha = K.ACT_CODES[g.act], g.act_alpha
         if bwd:
@@ -706,14 +811,22 @@ class BatchPlan(GeometryMixin):
     def _add_act_bwd(self, src: Src):
         """Behind the launch that stored the gradient wrt ``src``'s output through its BwdThrough
         (dropout mask applied, prev_relu = 0): the multiplication by A' of a stage with a hidden
-        activation, before anything reads that gradient buffer."""
+        activation, before anything reads that gradient buffer; and for a stage with a
+        BatchNormalization the two bn.hip backward launches, which turn that buffer into the stage's dz."""
         if src.kind == "input":
             return
         g = self.ex.convs[src.idx] if src.kind == "conv" else self.ex.denses[src.idx]
-        if g.act is None:
-            return
-        a = self._act_args(src.kind, g, True)
-        self._add("act_bwd_%s%d" % (src.kind[0], src.idx), lambda s, a=a: self.ex.K.act_bwd(a, s), act=a)
+        K = self.ex.K
+        if g.act is not None:
+            a = self._act_args(src.kind, g, True)
+            self._add("act_bwd_%s%d" % (src.kind[0], src.idx), lambda s, a=a: K.act_bwd(a, s), act=a)
+        if g.bn is not None:
+            # ... then the BatchNormalization backward: the dbeta / dgamma slabs, and the dense dz
+            # the stage's wgrad / dgrad read
+            b = self._bn_args(src.kind, g)
+            tag = "%s%d" % (src.kind[0], src.idx)
+            self._add("bn_bwd_reduce_" + tag, lambda s, a=b: K.bn_bwd_reduce(a, s), bn=b)
+            self._add("bn_bwd_apply_" + tag, lambda s, a=b: K.bn_bwd_apply(a, s), bn=b)
 
     def _build_args(self):
         """The step program, stage by stage; each stage appends its launches."""
@@ -759,7 +872,9 @@ class BatchPlan(GeometryMixin):
         # optimizer ran since the last pack) + the step bookkeeping
         # (a conv stage with a hidden activation other than relu / linear: the per-layer structure
         # of conv_stack=0, each such layer's linear kernel followed by its act_fwd launch)
-        conv_act = any(g.act is not None for g in ex.convs)
+        # (a conv stage with a BatchNormalization likewise: its linear kernel stores the un-pooled
+        # pre-activation for the bn.hip launches)
+        conv_act = any(g.act is not None or g.bn is not None for g in ex.convs)
         stack = self._conv_stack_args(training) if tune("conv_stack") and not conv_act else None
         # Prologue-free step (conv stack + a hidden dense layer + optimizer-written packs): the
         # stack reads its images straight from the dataset through the cursor and permutation
@@ -812,12 +927,19 @@ class BatchPlan(GeometryMixin):
             a.relu, a.pool = int(g.relu), int(g.pool)
             a.out = self.conv_out[g.i].data_ptr()
             a.Cs_out, a.Hp, a.Wp = g.Cs_out, g.Hp, g.Wp
-            if g.pool:
+            if g.bn is not None:
+                # the linear, un-pooled, dropout-free form: z for the bn.hip launches
+                a.relu, a.pool = 0, 0
+                a.out = self.bn["conv", g.i].z.data_ptr()
+                a.Hp, a.Wp = g.Ho, g.Wo
+            elif g.pool:
                 a.code = self.conv_code[g.i].data_ptr()
-            if self.training and g.rate > 0 and g.act is None:
+            if self.training and g.rate > 0 and g.act is None and g.bn is None:
                 a.drop_thr, a.drop_scale = dropout_pair(g.rate)
             a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
-            self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool), ca=a)
+            self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool and g.bn is None), ca=a)
+            if g.bn is not None:
+                self._add_bn_fwd("conv", g)
             if g.act is not None:
                 # the linear conv (+ pool) above, then A and the stage's dropout in place
                 fa = self._act_args("conv", g, False)
@@ -847,17 +969,22 @@ class BatchPlan(GeometryMixin):
             e.bias = ex.store.view(ds.dense, "bias").data_ptr() if ds.dense.use_bias else 0
             e.relu = int(g.relu)
             e.out = self.dense_out[g.j].data_ptr()
-            if self.training and g.rate > 0 and g.act is None:
+            if g.bn is not None:
+                e.relu, e.out = 0, self.bn["dense", g.j].z.data_ptr()
+            if self.training and g.rate > 0 and g.act is None and g.bn is None:
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head") and g.act is None):
+                    and tune("fuse_head") and g.act is None and g.bn is None):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
                 self.head_blocks = cdiv(bs, K.head_rows_per_block(True))
             else:
                 self._add("dense_epi%d" % g.j, lambda s, e=e: K.dense_epi(e, s), epi=e)
+            if g.bn is not None:
+                # (never the head's epilogue: fuse_head=0 structure)
+                self._add_bn_fwd("dense", g)
             if g.act is not None:
                 # the linear epilogue above (never the head's: fuse_head=0 structure), then A and
                 # the layer's dropout in place
@@ -903,12 +1030,12 @@ class BatchPlan(GeometryMixin):
         self._add("head", lambda s, a=h: K.head(a, s), head=h)
 
     # ---------------------------------------------------------------- step program: backward
-    def _add_group(self, spec, descs, bias_spec=None):
-        """A layer's reduction group over its kernel (and bias) span, its partial slabs final
-        after the launches appended so far."""
+    def _add_group(self, spec, descs, bias_spec=None, more=()):
+        """A layer's reduction group over its kernel (and bias, and its BatchNormalization's gamma /
+        beta: ``more``) span, its partial slabs final after the launches appended so far."""
         lo, hi = spec.offset, spec.offset + spec.numel
-        if bias_spec is not None:
-            hi = max(hi, bias_spec.offset + bias_spec.numel)
+        for sp in ([bias_spec] if bias_spec is not None else []) + list(more):
+            hi = max(hi, sp.offset + sp.numel)
         self.red_groups.append(RedGroup(lo, hi, descs, len(self.launches)))
         return lo, hi
 
@@ -958,7 +1085,8 @@ class BatchPlan(GeometryMixin):
         # one split + identity layout: the kernel's fixed-order sum IS the Keras
         # gradient -- write it in place and apply the optimizer there (single GPU,
         # fused-optimizer step), so the layer skips the end-of-step reduction
-        fused_opt = (self.dense_opt_ok and (self.dense_opt_all or direct)
+        # (a BatchNormalization stage's group also holds gamma / beta, which the kernel does not update)
+        fused_opt = (self.dense_opt_ok and (self.dense_opt_all or direct) and g.bn is None
                      and w.splits == 1 and g.src.C == g.src.Cs and g.N % 16 == 0 and sp.offset % 4 == 0)
         # with optimizer-written packs the kernel must write this layer's packs itself
         pk_ok = (kg == 2 and g.src.width % 32 == 0 and g.N % 32 == 0
@@ -1048,7 +1176,8 @@ class BatchPlan(GeometryMixin):
                                                           g.src.Cs)]
         if bsp is not None and not fused_opt:
             descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
-        lo, hi = self._add_group(sp, descs, bsp)
+        bn_descs, bn_specs = self._bn_descs("dense", g)
+        lo, hi = self._add_group(sp, descs + bn_descs, bsp, bn_specs)
         if fused_opt:
             self.dense_fused_opt.append((wa, hi - lo))
         if da is not None and not (dx_first or dual):
@@ -1087,6 +1216,11 @@ class BatchPlan(GeometryMixin):
         one dual launch where both take the halo kernels -- and the layer's reduction group."""
         ex, K, store = self.ex, self.ex.K, self.ex.store
         xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
+        g_stage = g
+        if g.bn is not None:
+            # conv_dy holds the dense un-pooled dz (bn_bwd_apply): the wgrad / dgrad of a linear,
+            # un-pooled stage
+            g = replace(g, pool=False, relu=False, rate=0.0, Hp=g.Ho, Wp=g.Wo)
         wide = self._wide(g.Cs_in, g.KS, g.NT)
         if wide:
             w = self._wgrad_tile_args(xin, g, cs.conv.use_bias)
@@ -1116,7 +1250,8 @@ class BatchPlan(GeometryMixin):
                          g.KH, g.KW, g.Cin, g.Cout, g.Cs_in)]
         if bsp is not None:
             descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
-        self._add_group(sp, descs, bsp)
+        bn_descs, bn_specs = self._bn_descs("conv", g_stage)
+        self._add_group(sp, descs + bn_descs, bsp, bn_specs)
         if ca is not None:
             if not dual:
                 self._add(dname, self._conv_launch(ca, g.NTd, False), ca=ca)
@@ -1140,9 +1275,17 @@ class BatchPlan(GeometryMixin):
             tab = ex.K.RedTable()
             # longest reductions (most slabs) first: their workgroups dispatch first and their
             # memory round trips overlap the many short ones instead of trailing the launch
-            for d in sorted((d for i in bg if i not in dp_early for d in self.red_groups[i].descs),
-                            key=lambda d: -d.S):
-                tab.add(*d)
+            descs = sorted((d for i in bg if i not in dp_early for d in self.red_groups[i].descs),
+                           key=lambda d: -d.S)
+            # (a bucket with more descriptors than a table holds -- many BatchNormalization stages:
+            # further tables, launched as plain slab reductions behind the first)
+            more = []
+            for j, d in enumerate(descs):
+                if j and j % ex.K.MAX_RED == 0:
+                    more.append(ex.K.RedTable())
+                (more[-1] if more else tab).add(*d)
+            if more:
+                self.bucket_overflow[k] = more
             lo = min(self.red_groups[i].lo for i in bg)
             hi = max(self.red_groups[i].hi for i in bg)
             self.bucket_tables.append((lo, hi, tab))
@@ -1472,6 +1615,10 @@ class BatchPlan(GeometryMixin):
             ex.K.reduce_optim(ex.store.grad.data_ptr(), tab, ex._optim_args(False, defer_pack=True), s)
         else:
             ex.K.slab_reduce(ex.store.grad.data_ptr(), lo, hi, tab, s)
+        for t in self.bucket_overflow.get(k, ()):
+            if xp is not None or self.optim_fused:
+                raise AssertionError("a bucket of several reduction tables is reduced by plain slab reductions only")
+            ex.K.slab_reduce(ex.store.grad.data_ptr(), lo, hi, t, s)
 
     def _launch_optim(self):
         ex = self.ex

@@ -9,7 +9,8 @@ exactly the points where the HIP step stores them in bf16 (weight packs of the c
 hidden denses, every stage output after its dropout, the hidden denses' dH and every pooled
 dP after their masks; for a stage with a hidden activation also its pre-activation, which the
 GPU stores between its linear kernels and the activation launch, and its gradient on both sides of
-the multiplication by A'), everything else in fp32 -- so the whole-step gradient test can use
+the multiplication by A'; for a BatchNormalization stage its pre-activation z before the
+statistics, the pooled gradient buffer and dz), everything else in fp32 -- so the whole-step gradient test can use
 the per-kernel tests' tight tolerances instead of the loose fp32-vs-bf16 bound.
 """
 from __future__ import annotations
@@ -68,14 +69,61 @@ class RefExecutor(Executor):
         y = out * torch.tensor(1.0 - stage.rate, dtype=torch.float32) if dropped else out
         return R.act_grad_from_output(stage.act, stage.act_alpha, y)
 
+    def _bn_forward(self, bn, z, training: bool):
+        """BatchNormalization of the (stored, so rounded) pre-activation z over all axes but the last
+        (Keras 2.2.4): batch statistics and the moving update in a training step, the moving statistics
+        otherwise.  Returns (u, (xhat, gamma * invstd) or None)."""
+        st = self.store
+        C = z.shape[-1]
+        gamma = st.view(bn, "gamma") if bn.scale else torch.ones(C)
+        beta = st.view(bn, "beta") if bn.center else torch.zeros(C)
+        eps = torch.tensor(bn.epsilon, dtype=torch.float32)
+        if not training:
+            inv = 1.0 / torch.sqrt(st.view(bn, "moving_variance") + eps)
+            return gamma * ((z - st.view(bn, "moving_mean")) * inv) + beta, None
+        z2 = z.reshape(-1, C)
+        m = z2.shape[0]
+        mean = z2.sum(0) / m
+        var = ((z2 - mean) ** 2).sum(0) / m           # biased, about the mean
+        inv = 1.0 / torch.sqrt(var + eps)
+        xhat = (z - mean) * inv
+        # Keras 2.2.4's sample-variance factor m / (m - (1 + eps)); m = 1 gives var = 0 exactly
+        mom = torch.tensor(bn.momentum, dtype=torch.float32)
+        unb = var * torch.tensor(m / (m - (1.0 + bn.epsilon)), dtype=torch.float32)
+        mm, mv = st.view(bn, "moving_mean"), st.view(bn, "moving_variance")
+        mm.copy_(mm * mom + mean * (1.0 - mom))
+        mv.copy_(mv * mom + unb * (1.0 - mom))
+        return gamma * xhat + beta, (xhat, gamma * inv)
+
+    def _bn_backward(self, bn, du, ctx):
+        """dz of a BatchNormalization stage from du (un-pooled, dense); writes dgamma / dbeta."""
+        st = self.store
+        xhat, ginv = ctx
+        C = du.shape[-1]
+        m = du.numel() // C
+        dbeta = du.reshape(-1, C).sum(0)
+        dgamma = (du * xhat).reshape(-1, C).sum(0)
+        if bn.scale:
+            st.view(bn, "gamma", grad=True).copy_(dgamma)
+        if bn.center:
+            st.view(bn, "beta", grad=True).copy_(dbeta)
+        return self._q(ginv * (du - dbeta / m - xhat * (dgamma / m)))
+
     def _forward(self, x, training: bool, step: int):
         st = self.store
         saved = []
+        self._bn_ctx = {}
         a = x
         for cs in self.plan.convs:
             w = self._q(st.view(cs.conv, "kernel"))
             b = st.view(cs.conv, "bias") if cs.conv.use_bias else None
             z = R.conv2d(a, w, b, cs.stride, cs.conv.padding)
+            z_code = z
+            if cs.bn is not None:
+                # z is stored (bf16) before the statistics; everything behind it acts on u = BN(z),
+                # and the argmax is taken on the fp32 u
+                z, self._bn_ctx[id(cs)] = self._bn_forward(cs.bn, self._q(z), training)
+                z_code = z
             r = torch.relu(z) if cs.relu else z
             if cs.act is not None:
                 # Keras' order: activate, then pool (the GPU pools the linear conv, then activates:
@@ -85,7 +133,9 @@ class RefExecutor(Executor):
             p = r
             if cs.pool is not None:
                 p, code = R.maxpool2x2(r)
-                if cs.act is not None and self.emulate_bf16:
+                if cs.bn is not None:
+                    code = R.maxpool2x2(z_code)[1]
+                elif cs.act is not None and self.emulate_bf16:
                     # the bf16 rounding of the pre-activation ties neighbours that the GPU's linear
                     # kernel, which takes the argmax on its fp32 accumulators, never sees tied: the
                     # codes from z (the values are the same: A and the rounding are non-decreasing)
@@ -102,6 +152,8 @@ class RefExecutor(Executor):
             z = a @ w
             if ds.dense.use_bias:
                 z = z + st.view(ds.dense, "bias")
+            if ds.bn is not None:
+                z, self._bn_ctx[id(ds)] = self._bn_forward(ds.bn, self._q(z), training)
             r = torch.relu(z) if ds.relu else z
             if ds.act is not None:
                 r = R.act(ds.act, ds.act_alpha, self._q(z))
@@ -150,6 +202,8 @@ class RefExecutor(Executor):
             if ds.act is not None:                             # (the masked gradient is stored first)
                 da = self._q(da) * self._act_slope(ds, out, mask is not None)
             da = self._q(da)                                   # the stored bf16 dH
+            if ds.bn is not None:
+                da = self._bn_backward(ds.bn, da, self._bn_ctx[id(ds)])
             st.view(ds.dense, "kernel", grad=True).copy_(a_in.t() @ da)
             if ds.dense.use_bias:
                 st.view(ds.dense, "bias", grad=True).copy_(da.sum(0))
@@ -175,6 +229,8 @@ class RefExecutor(Executor):
                 da = R.maxpool2x2_backward(da, code, r.shape[1:3])
             if cs.relu:
                 da = da * (r > 0).to(da.dtype)
+            if cs.bn is not None:
+                da = self._bn_backward(cs.bn, da, self._bn_ctx[id(cs)])
             dx, dw, db = R.conv2d_backward(a_in, self._q(st.view(cs.conv, "kernel")), da, cs.stride,
                                            cs.conv.padding, need_dx=i > 0)
             st.view(cs.conv, "kernel", grad=True).copy_(dw)

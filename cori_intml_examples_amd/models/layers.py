@@ -90,9 +90,15 @@ class Layer:
         """[(short_name, shape, initializer)] in Keras order."""
         return []
 
-    def count_params(self) -> int:
+    non_trainable_weights_ = ()      # short names of the weights no optimizer updates
+
+    def count_params(self, trainable=None) -> int:
+        """Elements of the layer's weights; ``trainable`` True / False counts only those the
+        optimizer updates / only the others (a layer with ``trainable=False`` has none of the first)."""
         n = 0
-        for _, shape, _ in self.weight_specs():
+        for short, shape, _ in self.weight_specs():
+            if trainable is not None and trainable != (self.trainable and short not in self.non_trainable_weights_):
+                continue
             c = 1
             for s in shape:
                 c *= s
@@ -425,6 +431,72 @@ class ELU(Layer):
         return cfg
 
 
+class BatchNormalization(Layer):
+    """``keras.layers.BatchNormalization`` over the last axis (Keras 2.2.4).  The plan folds it into
+    the linear Conv2D / Dense directly before it (plan.py); ``moving_mean`` / ``moving_variance`` are
+    non-trainable weights the training step itself updates."""
+
+    non_trainable_weights_ = ("moving_mean", "moving_variance")
+    _DEFAULT_INITS = (("beta_initializer", "zeros", "Zeros"), ("gamma_initializer", "ones", "Ones"),
+                      ("moving_mean_initializer", "zeros", "Zeros"),
+                      ("moving_variance_initializer", "ones", "Ones"))
+
+    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True, beta_initializer="zeros",
+                 gamma_initializer="ones", moving_mean_initializer="zeros", moving_variance_initializer="ones",
+                 beta_regularizer=None, gamma_regularizer=None, beta_constraint=None, gamma_constraint=None, **kw):
+        super().__init__(**kw)
+        if axis != -1:
+            raise NotImplementedError("layer %s (BatchNormalization): axis = %r; only axis=-1 (the channel axis, "
+                                      "given as -1) is implemented" % (self.name, axis))
+        given = {"beta_initializer": beta_initializer, "gamma_initializer": gamma_initializer,
+                 "moving_mean_initializer": moving_mean_initializer,
+                 "moving_variance_initializer": moving_variance_initializer}
+        for key, name, cls in self._DEFAULT_INITS:
+            v = given[key]
+            if isinstance(v, dict):
+                v = v.get("class_name") if not v.get("config") else v
+            if v not in (name, cls):
+                raise NotImplementedError("layer %s (BatchNormalization): %s = %r; only the default %r is "
+                                          "implemented" % (self.name, key, given[key], name))
+        for key, v in (("beta_regularizer", beta_regularizer), ("gamma_regularizer", gamma_regularizer),
+                       ("beta_constraint", beta_constraint), ("gamma_constraint", gamma_constraint)):
+            if v is not None:
+                raise NotImplementedError("layer %s (BatchNormalization): %s is not implemented"
+                                          % (self.name, key))
+        if not self.trainable:
+            raise NotImplementedError("layer %s (BatchNormalization): trainable=False (frozen statistics) is not "
+                                      "implemented" % self.name)
+        self.axis = -1
+        self.momentum = float(momentum)
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError("layer %s (BatchNormalization): momentum = %r is outside [0, 1)" % (self.name, momentum))
+        self.epsilon = float(epsilon)
+        if not self.epsilon > 0.0:
+            raise ValueError("layer %s (BatchNormalization): epsilon = %r must be > 0" % (self.name, epsilon))
+        self.center, self.scale = bool(center), bool(scale)
+
+    def weight_specs(self):
+        c = self.input_shape[-1]
+        specs = []
+        if self.scale:
+            specs.append(("gamma", (c,), "ones"))
+        if self.center:
+            specs.append(("beta", (c,), "zeros"))
+        return specs + [("moving_mean", (c,), "zeros"), ("moving_variance", (c,), "ones")]
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.update({"axis": -1, "momentum": self.momentum, "epsilon": self.epsilon, "center": self.center,
+                    "scale": self.scale,
+                    "beta_initializer": {"class_name": "Zeros", "config": {}},
+                    "gamma_initializer": {"class_name": "Ones", "config": {}},
+                    "moving_mean_initializer": {"class_name": "Zeros", "config": {}},
+                    "moving_variance_initializer": {"class_name": "Ones", "config": {}},
+                    "beta_regularizer": None, "gamma_regularizer": None, "beta_constraint": None,
+                    "gamma_constraint": None})
+        return cfg
+
+
 def activation_of(layer):
     """(name, alpha) an activation-type layer applies: ('relu' | None | a table name, alpha)."""
     if isinstance(layer, LeakyReLU):
@@ -435,4 +507,4 @@ def activation_of(layer):
 
 
 LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
-                                         LeakyReLU, ELU)}
+                                         LeakyReLU, ELU, BatchNormalization)}

@@ -168,7 +168,7 @@ class Model:
         if getattr(self.optimizer, "distributed", False):
             from ..parallel import dist
             dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda",
-                                       tuple(self.store.regularized_layers()))
+                                       tuple(self.store.regularized_layers()), dist.bn_layer_names(self._plan))
         if self._device.type == "cuda":
             from .executor_hip import HipExecutor
             self._executor = HipExecutor(self._plan, self.store, base, self._seed)
@@ -304,7 +304,7 @@ class Model:
                  layer.count_params()])
             print_fn("=" * line_length if i == len(shown) - 1 else "_" * line_length)
         total = self.count_params()
-        trainable = sum(l.count_params() for l in self._chain if l.trainable)
+        trainable = sum(l.count_params(trainable=True) for l in self._chain)
         print_fn("Total params: {:,}".format(total))
         print_fn("Trainable params: {:,}".format(trainable))
         print_fn("Non-trainable params: {:,}".format(total - trainable))

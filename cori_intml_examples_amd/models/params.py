@@ -27,6 +27,7 @@ class ParamSpec:
     init: str
     offset: int
     numel: int
+    trainable: bool = True     # False: no gradient, no optimizer slot (BatchNormalization's moving statistics)
 
     @property
     def name(self) -> str:
@@ -36,17 +37,32 @@ class ParamSpec:
 class ParamStore:
     def __init__(self, layers: List[Layer], device: torch.device):
         self.device = torch.device(device)
-        self.specs: List[ParamSpec] = []
+        self.specs: List[ParamSpec] = []       # Keras order, trainable or not
         off = 0
         for layer in layers:
+            frozen = getattr(layer, "non_trainable_weights_", ())
             for short, shape, init in layer.weight_specs():
                 n = int(np.prod(shape))
+                if short in frozen:
+                    self.specs.append(ParamSpec(layer, short, tuple(shape), init, -1, n, False))
+                    continue
                 self.specs.append(ParamSpec(layer, short, tuple(shape), init, off, n))
                 off += n
+        # numel / capacity: the TRAINABLE flat range [0, numel) -- what the optimizer, the clip /
+        # regularizer / reduction launches, the all-reduce buckets, the optimizer slots and the
+        # weight digest see
         self.numel = off
         # keep the buffer size a multiple of 64 floats so vectorised kernels need no tails
         self.capacity = max(64, (off + 63) // 64 * 64)
-        self.master = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        # non-trainable tensors live behind the trainable capacity in the same master buffer (one
+        # broadcast of master moves them too); they have no element in grad
+        off = self.capacity
+        for s in self.specs:
+            if not s.trainable:
+                s.offset = off
+                off += s.numel
+        self.total = self.capacity if off == self.capacity else (off + 63) // 64 * 64
+        self.master = torch.zeros(self.total, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
         self._bind_views()
 
@@ -62,6 +78,8 @@ class ParamStore:
 
     def view(self, layer: Layer, short: str, grad: bool = False) -> torch.Tensor:
         s = self.spec(layer, short)
+        if grad and not s.trainable:
+            raise KeyError("%s is not trainable: it has no gradient" % s.name)
         buf = self.grad if grad else self.master
         return buf[s.offset:s.offset + s.numel].view(s.shape)
 
@@ -157,8 +175,11 @@ class ParamStore:
         return names
 
     def layer_ranges(self) -> Dict[str, Tuple[int, int]]:
+        """Per layer, the flat range of its trainable tensors."""
         out: Dict[str, Tuple[int, int]] = {}
         for s in self.specs:
+            if not s.trainable:
+                continue
             lo, hi = out.get(s.layer.name, (s.offset, s.offset))
             out[s.layer.name] = (min(lo, s.offset), max(hi, s.offset + s.numel))
         return out

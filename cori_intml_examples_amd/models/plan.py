@@ -14,6 +14,11 @@ linear Conv2D / Dense) makes the stage ``dropout(A(maxpool(conv)))``: its kernel
 linear form and one element-wise launch per direction follows them (act.hip).  A is
 non-decreasing, so this equals Keras' ``maxpool(A(conv))``.
 
+A BatchNormalization directly behind a linear Conv2D / hidden Dense (``bn``) makes the stage
+``dropout(maxpool(A(BN(conv))))``: the linear kernels store the un-pooled pre-activation, and the
+bn.hip launches normalise, activate (relu), pool and drop.  gamma may be negative, so the pool is
+never taken before BN.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -22,8 +27,8 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .layers import (ELU, Activation, Conv2D, Dense, Dropout, Flatten, InputLayer, Layer, LeakyReLU, MaxPooling2D,
-                     activation_of)
+from .layers import (ELU, Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, InputLayer, Layer, LeakyReLU,
+                     MaxPooling2D, activation_of)
 from ..ops.reference import conv_pads
 
 
@@ -39,6 +44,7 @@ class ConvStage:
     stream: int = 0                         # RNG stream id of the dropout
     act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
     act_alpha: float = 0.0
+    bn: Optional[BatchNormalization] = None  # dropout(maxpool(A(BN(conv)))): the pool is NOT taken before BN
 
     @property
     def rate(self) -> float:
@@ -66,6 +72,7 @@ class DenseStage:
     flat_from: Optional[Tuple[int, int, int]] = None   # (H,W,C) if the input comes from a Flatten
     act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
     act_alpha: float = 0.0
+    bn: Optional[BatchNormalization] = None  # dropout(A(BN(dense)))
 
     @property
     def rate(self) -> float:
@@ -139,9 +146,27 @@ def build_plan(layers: List[Layer], loss) -> Plan:
         if skip:                # the output Activation layer, taken by the head Dense before it
             skip = False
             continue
-        if not isinstance(layer, ACT_LAYERS + (Conv2D, Dense)):
+        if not isinstance(layer, ACT_LAYERS + (Conv2D, Dense, BatchNormalization)):
             open_stage = None
-        if isinstance(layer, ACT_LAYERS):
+        if isinstance(layer, BatchNormalization):
+            if isinstance(before, BatchNormalization):
+                raise NotImplementedError("layer %s follows %s: two BatchNormalization layers on one stage"
+                                          % (layer.name, before.name))
+            if plan.head is not None or (last and isinstance(before, Dense)):
+                raise NotImplementedError("layer %s follows %s, the output Dense: BatchNormalization behind the "
+                                          "output layer is not implemented"
+                                          % (layer.name, (plan.head.dense if plan.head is not None else before).name))
+            if isinstance(before, (Conv2D, Dense)) and before.activation is not None:
+                raise NotImplementedError("layer %s follows %s, which already has the activation %s: "
+                                          "BatchNormalization must follow a linear Conv2D or Dense (put the "
+                                          "activation behind it as a layer)"
+                                          % (layer.name, before.name, before.activation))
+            if open_stage is None or before is not open_stage[1]:
+                raise NotImplementedError("layer %s follows %s: BatchNormalization must directly follow a linear "
+                                          "Conv2D or hidden Dense (before any activation, pooling, dropout or "
+                                          "flatten)" % (layer.name, before.name))
+            open_stage[0].bn = layer
+        elif isinstance(layer, ACT_LAYERS):
             name, alpha = activation_of(layer)
             if open_stage is None:
                 owner = before if isinstance(before, (Conv2D, Dense)) else None

@@ -533,17 +533,23 @@ def auto_plane(grad_bytes: Optional[int] = None) -> str:
 RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-switch instance)
 
 
-def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=()) -> str:
+def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=(), bn_layers=()) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
     for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``), and for a
     model with weight regularizers (``needs_local_gradient``: the names of its regularized
     layers) -- when it was merely chosen (auto / a recorded verdict), and is a ValueError when it
-    was forced (INTML_XGMI, or a job without an RCCL communicator)."""
+    was forced (INTML_XGMI, or a job without an RCCL communicator).  A model with
+    BatchNormalization layers (``bn_layers``: their names) is gated the same way: its step is
+    exercised on the RCCL plane only."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
     clips = bool(getattr(base, "clips", False))
     if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips
-                                               or needs_local_gradient):
+                                               or needs_local_gradient or bn_layers):
         return plane
+    if forced and bn_layers:
+        raise ValueError("BatchNormalization layers (%s) have no kernels for the %r data plane (their gamma / beta "
+                         "gradients are all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
+                         % (", ".join(bn_layers), plane))
     if forced and needs_local_gradient:
         # weight regularizers: their term joins the local gradient in memory ahead of the
         # all-reduce, which only the RCCL plane's step does
@@ -582,8 +588,9 @@ class NativeGradReducer:
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
                  rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None,
-                 needs_local_gradient=()):
+                 needs_local_gradient=(), bn_layers=()):
         self.store, self.comm = store, comm
+        self.bn_layers = bn_layers      # (a model with BatchNormalization layers: RCCL plane only)
         self.optimizer = optimizer      # (plane_for_optimizer: kinds that stay off the xGMI planes)
         self.needs_local_gradient = needs_local_gradient   # (a regularized model's layer names: the same)
         self.compression = compression
@@ -613,7 +620,7 @@ class NativeGradReducer:
         local = getattr(self, "needs_local_gradient", ())
         self.plane = plane_for_optimizer(self.plane, getattr(self, "optimizer", None),
                                          forced=self.comm is None or forced_plane() is not None,
-                                         needs_local_gradient=local)
+                                         needs_local_gradient=local, bn_layers=getattr(self, "bn_layers", ()))
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
@@ -773,7 +780,7 @@ class NativeGradReducer:
             grad[: self.store.numel].div_(self.size)
 
 
-def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=()) -> None:
+def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_layers=()) -> None:
     """ValueError when the job pins a data plane ``optimizer`` -- or a model with weight
     regularizers (``needs_local_gradient``: its regularized layers' names) -- has no kernels for
     (INTML_XGMI = xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds
@@ -782,9 +789,16 @@ def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=()) -> N
         init()
     st = _st()
     if on_gpu and st.comm is not None:
-        plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient)
+        plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
+                            bn_layers=bn_layers)
     elif on_gpu and st.xgmi_only and st.size > 1:
-        plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient)
+        plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
+                            bn_layers=bn_layers)
+
+
+def bn_layer_names(plan) -> tuple:
+    """Names of a plan's BatchNormalization layers, in stage order."""
+    return tuple(s.bn.name for s in list(plan.convs) + list(plan.denses) if getattr(s, "bn", None) is not None)
 
 
 def make_reducer(executor, optimizer):
@@ -797,10 +811,13 @@ def make_reducer(executor, optimizer):
     # a model with weight regularizers needs each rank's whole local gradient ahead of the
     # all-reduce, as a clipping optimizer does: ONE bucket, RCCL plane (the layers' names, for errors)
     local = tuple(executor.store.regularized_layers()) if getattr(executor, "regs", None) else ()
-    check_optimizer_plane(optimizer, on_gpu, local)
+    bn = bn_layer_names(executor.plan)
+    check_optimizer_plane(optimizer, on_gpu, local, bn)
     if on_gpu and st.comm is not None:
-        return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local)
+        return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local,
+                                 bn_layers=bn)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
-                                 device=executor.store.device, optimizer=optimizer, needs_local_gradient=local)
+                                 device=executor.store.device, optimizer=optimizer, needs_local_gradient=local,
+                                 bn_layers=bn)
     return GradReducer(executor.store, comp, bb, optimizer=optimizer, needs_local_gradient=local)
