@@ -24,10 +24,9 @@ from __future__ import annotations
 
 import gc
 import os
-from dataclasses import dataclass, field, replace
 from types import SimpleNamespace
 from operator import attrgetter
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -37,89 +36,28 @@ from ..optim.optimizers import KIND_IDS, STANDALONE_KINDS, clip_pair, fill_clip_
 from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
-from .hip_geometry import GeometryMixin, cdiv, r8  # noqa: F401  (cdiv: re-exported for tests)
+from .hip_geometry import GeometryMixin
 from .plan import Plan
-from .step_program import (Exchange, Launch, RedDesc, RedGroup, check_bucket_cover,  # noqa: F401  (re-exported)
-                           defer_after_readers, dropout_pair, splice_bucket_launches, stream_program)
+from .step_program import (ConvGeo, DenseGeo, Exchange, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
+                           cdiv, check_bucket_cover, defer_after_readers, dropout_pair, splice_bucket_launches,
+                           stage_geometry, stream_program)
 
 BF16 = torch.bfloat16
-# views of the optimizer-kind table (optim/optimizers.py KINDS).  STANDALONE_KINDS: kinds with
-# instances of optim_kernel / reduce_optim_kernel only -- the kernels that choose the optimizer
-# at run time (the dual launch's early reduction, the dense wgrad's fused update, the xGMI
-# exchange and all-reduce kernels) stay five-way, so a step of these kinds carries no early
-# reduction and no fused dense update, and its data plane updates after the all-reduce
+# views of the optimizer-kind table (optim/optimizers.py KINDS); STANDALONE_KINDS: see
+# HipExecutor.inline_update_ok
 OPT_KIND = KIND_IDS
 PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_DENSE_FWD, PACK_DENSE_BWD = 0, 1, 2, 3
 RED_CONVW, RED_BIAS, RED_FLATW = 0, 1, 2
 
 
-@dataclass
-class Src:
-    """An activation buffer feeding the next stage (for flatten mapping / bwd-through)."""
-    kind: str            # 'input' | 'conv' | 'dense'
-    idx: int
-    C: int               # logical channels (flatten mapping)
-    Cs: int              # padded channel stride
-    H: int = 1
-    W: int = 1
-
-    @property
-    def width(self):
-        return self.H * self.W * self.Cs
-
-
-@dataclass
-class ConvGeo:
-    i: int
-    H: int
-    W: int
-    Cin: int
-    Cs_in: int
-    Ho: int
-    Wo: int
-    Cout: int
-    Cs_out: int
-    Hp: int
-    Wp: int
-    KH: int
-    KW: int
-    stride: int
-    pad_t: int
-    pad_l: int
-    pool: bool
-    relu: bool
-    rate: float
-    stream: int
-    KS: int = 0
-    NT: int = 0
-    KSd: int = 0
-    NTd: int = 0
-    pack_fwd: int = 0
-    pack_dgrad: int = -1
-    act: Optional[str] = None      # hidden activation other than relu / linear (plan.ConvStage.act)
-    act_alpha: float = 0.0
-    bn: Optional[object] = None    # the stage's BatchNormalization layer (plan.ConvStage.bn)
-
-
-@dataclass
-class DenseGeo:
-    j: int
-    src: Src
-    K: int
-    N: int
-    Ns: int
-    relu: bool
-    rate: float
-    stream: int
-    KS: int = 0
-    NT: int = 0
-    KSb: int = 0
-    NTb: int = 0
-    pack_fwd: int = 0
-    pack_bwd: int = -1
-    act: Optional[str] = None      # hidden activation other than relu / linear (plan.DenseStage.act)
-    act_alpha: float = 0.0
-    bn: Optional[object] = None    # the stage's BatchNormalization layer (plan.DenseStage.bn)
+class StageBufs(NamedTuple):
+    """The buffers of one hidden stage in one BatchPlan (BatchPlan.stage_bufs)."""
+    lin_out: torch.Tensor          # where the linear kernel / epilogue writes: ``out``, or a BatchNormalization's z
+    out: torch.Tensor              # the stage output
+    code: Optional[torch.Tensor]   # the pooling argmax codes
+    dout: Optional[torch.Tensor]   # the gradient wrt the stage output: what the next stage's BwdThrough
+    #                                stores and act_bwd scales (training)
+    dz: Optional[torch.Tensor]     # what the stage's own wgrad and dgrad read: ``dout``, or bn_bwd_apply's dz
 
 
 class HipExecutor(Executor):
@@ -146,9 +84,8 @@ class HipExecutor(Executor):
         # other hyper-parameters except lr: the values go into kernel arguments of the captured
         # step, so a later change of optimizer.clipnorm / clipvalue takes a new compile().  A clipping
         # optimizer's step has the fuse_optim=0 structure whatever its kind -- every slab
-        # reduction, the norm launch, then the clipped optimizer launch -- gated like
-        # STANDALONE_KINDS: no early reduction, no fused dense update, RCCL plane only.  The clip
-        # scalars (norm, factor, the norm kernel's ticket) live in a buffer of their own.
+        # reduction, the norm launch, then the clipped optimizer launch (whole_grad_first below).
+        # The clip scalars (norm, factor, the norm kernel's ticket) live in a buffer of their own.
         self.clipnorm, self.clipvalue = clip_pair(base)
         self.clips = bool(self.clipnorm or self.clipvalue)
         self.clip_state = self.clip_partials = None
@@ -159,12 +96,22 @@ class HipExecutor(Executor):
             self.clip_partials = torch.zeros(cdiv(store.numel + 3, K.CLIP_CHUNK) + 1, dtype=torch.float32,
                                              device=self.device)
         # Keras weight regularizers [(lo, hi, l1, l2)] over the flat store, read HERE like the clip
-        # values (they go into kernel arguments of the captured step).  A regularized model's step
-        # is gated exactly like a clipping one's: the term joins the whole reduced gradient in ONE
-        # weight_reg launch (reg.hip) behind the last slab reduction and ahead of the norm launch
-        # and the update, so no early reduction, no fused dense update, optim_fused = False, RCCL
-        # plane only.  reg_state[REG_PENALTY] is the last step's penalty P.
+        # values (they go into kernel arguments of the captured step).  The term joins the whole
+        # reduced gradient in ONE weight_reg launch (reg.hip) behind the last slab reduction and
+        # ahead of the norm launch and the update.  reg_state[REG_PENALTY] is the last step's penalty P.
         self.regs = store.regularized_ranges()
+        # The update gate, read by everything that could update before the step's end.
+        # whole_grad_first: something must see the WHOLE reduced gradient before any update -- the
+        # global norm of a clipping optimizer, the regularizers' term -- so the step is every slab
+        # reduction, BatchPlan._whole_grad_launches, then the update: optim_fused = False, ONE
+        # data-parallel bucket, RCCL plane only.
+        # inline_update_ok: an update may run inside the backward -- the dual launch's early
+        # reduction, the dense wgrad's fused update.  Not with whole_grad_first, and not for
+        # STANDALONE_KINDS: kinds with instances of optim_kernel / reduce_optim_kernel only, while
+        # the kernels that choose the optimizer at run time (those two, the xGMI exchange and
+        # all-reduce kernels) stay five-way, so their data plane updates after the all-reduce.
+        self.whole_grad_first = self.clips or bool(self.regs)
+        self.inline_update_ok = not self.whole_grad_first and base.kind not in STANDALONE_KINDS
         self.reg_state = self.reg_partials = None
         if self.regs:
             K = self.K
@@ -193,52 +140,12 @@ class HipExecutor(Executor):
 
     # ------------------------------------------------------------------ geometry
     def _build_geometry(self):
-        p = self.plan
-        H0, W0, C0 = (p.input_shape + (1, 1))[:3] if len(p.input_shape) == 3 else (1, 1, p.input_shape[0])
-        if len(p.input_shape) == 1:
-            H0, W0, C0 = 1, 1, p.input_shape[0]
-        self.in_C = C0
-        self.in_Cs = 4 if C0 <= 4 else r8(C0)
-        self.in_H, self.in_W = H0, W0
-        self.convs: List[ConvGeo] = []
-        src = Src("input", 0, C0, self.in_Cs, H0, W0)
-        H, W, Cin, Cs_in = H0, W0, C0, self.in_Cs
-        for i, cs in enumerate(p.convs):
-            Ho, Wo, Cout = cs.conv_shape
-            Hp, Wp, _ = cs.out_shape
-            pt, _, pl, _ = cs.pads
-            kh, kw = cs.conv.kernel_size
-            g = ConvGeo(i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
-                        cs.pool is not None, cs.relu, cs.rate, cs.stream)
-            g.act, g.act_alpha, g.bn = cs.act, cs.act_alpha, cs.bn
-            g.KS = cdiv(kh * kw * Cs_in, 32)
-            g.NT = cdiv(Cout, 16)
-            if i > 0:
-                g.KSd = cdiv(kh * kw * g.Cs_out, 32)
-                g.NTd = cdiv(Cin, 16)
-            self.convs.append(g)
-            H, W, Cin, Cs_in = Hp, Wp, Cout, g.Cs_out
-            src = Src("conv", i, Cout, g.Cs_out, Hp, Wp)
-        self.denses: List[DenseGeo] = []
-        for j, ds in enumerate(p.denses):
-            g = DenseGeo(j, src, ds.K, ds.N, r8(ds.N), ds.relu, ds.rate, ds.stream)
-            if g.K != src.H * src.W * src.C:
-                raise ValueError("dense %d input width mismatch" % j)
-            g.act, g.act_alpha, g.bn = ds.act, ds.act_alpha, ds.bn
-            g.KS = cdiv(src.width, 32)
-            g.NT = cdiv(ds.N, 16)
-            if j > 0 or self.convs:
-                g.KSb = cdiv(g.Ns, 32)
-                g.NTb = cdiv(src.width, 16)
-            self.denses.append(g)
-            src = Src("dense", j, ds.N, g.Ns)
-        self.head_src = src
-        hd = p.head
-        if hd.K != src.H * src.W * src.C:
-            raise ValueError("head input width mismatch")
-        if hd.N > 16:
-            raise NotImplementedError("output layers wider than 16 units")
-        self.head_act = {None: 0, "sigmoid": 1, "softmax": 2}[hd.activation]
+        inp, self.convs, self.denses, self.head_src, self.head_act = stage_geometry(self.plan)
+        self.in_C, self.in_Cs, self.in_H, self.in_W = inp.C, inp.Cs, inp.H, inp.W
+
+    def stage_of(self, src: Src):
+        """The hidden stage whose output ``src`` describes (None: the model input)."""
+        return {"input": [None], "conv": self.convs, "dense": self.denses}[src.kind][src.idx]
 
     def _build_packs(self):
         K = self.K
@@ -605,19 +512,17 @@ class BatchPlan(GeometryMixin):
         # linear kernels store), dp (the gradient wrt the stage output, which the next stage's
         # BwdThrough stores), the statistics partials, the saved mean / invstd, the dbeta / dgamma
         # slabs and the BnArgs.  Such a stage's conv_dy / dense_dh is dz: un-pooled, what its wgrad
-        # and dgrad read as the dY of a linear stage
+        # and dgrad read as the dY of a linear stage.  Read through stage_bufs
         self.bn: Dict[Tuple[str, int], SimpleNamespace] = {}
         for g in ex.convs:
             self.conv_out.append(z(bs, g.Hp, g.Wp, g.Cs_out))
             self.conv_code.append(z(bs, g.Hp, g.Wp, g.Cs_out, dt=torch.uint8) if g.pool else None)
+            # gradient wrt the stage OUTPUT resolution (pooled dP for pooled convs; the
+            # full-resolution dY is rebuilt on load from dP + codes, never stored)
+            self.conv_dy.append(z(bs, g.linear.Hp, g.linear.Wp, g.Cs_out) if self.training else None)
             if g.bn is not None:
                 self.bn["conv", g.i] = self._bn_buffers(z, bs * g.Ho * g.Wo, (bs, g.Ho, g.Wo, g.Cs_out),
                                                         (bs, g.Hp, g.Wp, g.Cs_out))
-                self.conv_dy.append(z(bs, g.Ho, g.Wo, g.Cs_out) if self.training else None)
-                continue
-            # gradient wrt the stage OUTPUT resolution (pooled dP for pooled convs; the
-            # full-resolution dY is rebuilt on load from dP + codes, never stored)
-            self.conv_dy.append(z(bs, g.Hp, g.Wp, g.Cs_out) if self.training else None)
         self.dense_out, self.dense_part, self.dense_dh = [], [], []
         self.dense_splits = []
         for g in ex.denses:
@@ -637,6 +542,9 @@ class BatchPlan(GeometryMixin):
             self.dense_dh.append(z(bs, g.Ns) if self.training else None)
             if g.bn is not None:
                 self.bn["dense", g.j] = self._bn_buffers(z, bs, (bs, g.Ns), (bs, g.Ns))
+        # Stage.kind -> its (output, pooling code, gradient) lists, for stage_bufs
+        self._stage_lists = {"conv": (self.conv_out, self.conv_code, self.conv_dy),
+                             "dense": (self.dense_out, [None] * len(ex.denses), self.dense_dh)}
         hd = ex.plan.head
         self.head_blocks = cdiv(bs, K.head_rows_per_block(False))   # re-set below if the head fuses the epilogue
         head_slab_blocks = cdiv(bs, K.head_rows_per_block(True))
@@ -657,24 +565,23 @@ class BatchPlan(GeometryMixin):
                                slab=None,
                                plan=(chunk, nchunks, gp_log2), args=None)
 
-    def _bn_args(self, kind, g):
-        """The BnArgs of stage g ('conv' | 'dense'): one struct for the stage's four launches."""
+    def stage_bufs(self, g) -> StageBufs:
+        """Which buffer holds what for hidden stage ``g`` (a ConvGeo / DenseGeo)."""
+        out, code, dz = (lst[g.idx] for lst in self._stage_lists[g.kind])
+        b = self.bn.get((g.kind, g.idx))
+        return StageBufs(out, out, code, dz, dz) if b is None else StageBufs(b.z, out, code, b.dp, dz)
+
+    def _bn_args(self, g):
+        """The BnArgs of stage g: one struct for the stage's four launches."""
         ex, K, store = self.ex, self.ex.K, self.ex.store
-        b = self.bn[kind, g.i if kind == "conv" else g.j]
+        b, bufs = self.bn[g.kind, g.idx], self.stage_bufs(g)
         if b.args is not None:
             return b.args
         a = K.BnArgs()
         bn = g.bn
-        a.z = b.z.data_ptr()
-        if kind == "conv":
-            a.rows, a.C, a.Cs = self.bs * g.Ho * g.Wo, g.Cout, g.Cs_out
-            a.B, a.Ho, a.Wo, a.Hp, a.Wp, a.pool = self.bs, g.Ho, g.Wo, g.Hp, g.Wp, int(g.pool)
-            out, code = self.conv_out[g.i], self.conv_code[g.i]
-            dz = self.conv_dy[g.i]
-        else:
-            a.rows, a.C, a.Cs = self.bs, g.N, g.Ns
-            a.B = self.bs
-            out, code, dz = self.dense_out[g.j], None, self.dense_dh[g.j]
+        a.z = bufs.lin_out.data_ptr()
+        (a.Ho, a.Wo), (a.Hp, a.Wp) = g.lin_grid, g.out_grid
+        a.B, a.rows, a.C, a.Cs, a.pool = self.bs, self.bs * a.Ho * a.Wo, g.C, g.Cs, int(g.pool)
         a.chunk, a.nchunks, a.gp_log2 = b.plan
         a.part, a.saved = b.part.data_ptr(), b.saved.data_ptr()
         if bn.scale:
@@ -687,37 +594,27 @@ class BatchPlan(GeometryMixin):
         a.eps, a.momentum = bn.epsilon, bn.momentum
         a.unbias = m / (m - (1.0 + bn.epsilon))     # Keras 2.2.4's sample-variance factor
         a.training, a.relu = int(self.training), int(g.relu)
-        a.out = out.data_ptr()
-        if code is not None:
-            a.code = code.data_ptr()
-        # (a table activation's launch behind this one carries the dropout, as it does today)
-        if self.training and g.rate > 0 and g.act is None:
+        a.out = bufs.out.data_ptr()
+        if bufs.code is not None:
+            a.code = bufs.code.data_ptr()
+        if self.training and g.dropout_in == "bn":
             a.drop_thr, a.drop_scale = dropout_pair(g.rate)
         a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
         if self.training:
             # the chunk slabs: [nchunks][dgamma[C], dbeta[C]]
             b.slab = torch.zeros(b.plan[1], 2, a.C, dtype=torch.float32, device=ex.device)
-            a.dp, a.slab, a.dz = b.dp.data_ptr(), b.slab.data_ptr(), dz.data_ptr()
+            a.dp, a.slab, a.dz = bufs.dout.data_ptr(), b.slab.data_ptr(), bufs.dz.data_ptr()
         b.args = a
         return a
 
-    def _add_bn_fwd(self, kind, g):
-        """Behind the stage's linear kernels: bn_stats (training) and bn_apply_fwd."""
-        K = self.ex.K
-        a = self._bn_args(kind, g)
-        tag = "%s%d" % (kind[0], g.i if kind == "conv" else g.j)
-        if self.training:
-            self._add("bn_stats_" + tag, lambda s, a=a: K.bn_stats(a, s), bn=a)
-        self._add("bn_apply_fwd_" + tag, lambda s, a=a: K.bn_apply_fwd(a, s), bn=a)
-
-    def _bn_descs(self, kind, g):
+    def _bn_descs(self, g):
         """(RedDescs, specs) of stage g's gamma / beta: the bn_bwd_reduce slabs [chunk][dgamma, dbeta]
         as ONE bias-like reduction over gamma and beta, which are adjacent in the store (or over the
         one of them the layer has)."""
         if g.bn is None:
             return [], []
         store = self.ex.store
-        b = self.bn[kind, g.i if kind == "conv" else g.j]
+        b = self.bn[g.kind, g.idx]
         _, nchunks, _ = b.plan
         C = b.slab.shape[-1]
         specs = [store.spec(g.bn, short) for short in ("gamma", "beta") if store.has(g.bn, short)]
@@ -738,95 +635,85 @@ class BatchPlan(GeometryMixin):
         return d.x[idx], d.y[idx]
 
     def _src_buf(self, src: Src):
-        if src.kind == "input":
-            return self.xb
-        if src.kind == "conv":
-            return self.conv_out[src.idx]
-        return self.dense_out[src.idx]
+        g = self.ex.stage_of(src)
+        return self.xb if g is None else self.stage_bufs(g).out
 
     def _bt_for(self, src: Src):
         """BwdThrough args routing a gradient wrt ``src``'s output back into its layer."""
         K, ex = self.ex.K, self.ex
-        bt = K.BwdThrough()
-        if src.kind == "input":
+        g = ex.stage_of(src)
+        if g is None:
             return None
-        if src.kind == "conv":
-            g = ex.convs[src.idx]
-            bt.prev_out = self.conv_out[g.i].data_ptr()
-            if g.pool:
-                bt.prev_code = self.conv_code[g.i].data_ptr()
-            bt.prev_relu, bt.prev_pool = int(g.relu), int(g.pool)
-            bt.pH, bt.pW, bt.pC, bt.pCs = g.Hp, g.Wp, g.Cout, g.Cs_out
-            bt.cH, bt.cW = g.Ho, g.Wo
-            rate, stream = g.rate, g.stream
-            dyb = self.bn["conv", g.i].dp if g.bn is not None else self.conv_dy[g.i]
-        else:
-            g = ex.denses[src.idx]
-            bt.prev_out = self.dense_out[g.j].data_ptr()
-            bt.prev_relu, bt.prev_pool = int(g.relu), 0
-            bt.pH, bt.pW, bt.pC, bt.pCs = 1, 1, g.N, g.Ns
-            bt.cH, bt.cW = 1, 1
-            rate, stream = g.rate, g.stream
-            dyb = self.bn["dense", g.j].dp if g.bn is not None else self.dense_dh[g.j]
-        bt.dy = dyb.data_ptr()
-        if rate > 0:
-            bt.drop_thr, bt.drop_scale = dropout_pair(rate)
-        bt.seed, bt.stream_id = ex.seed, stream
+        bufs = self.stage_bufs(g)
+        bt = K.BwdThrough()
+        bt.prev_out = bufs.out.data_ptr()
+        if bufs.code is not None:
+            bt.prev_code = bufs.code.data_ptr()
+        bt.prev_relu, bt.prev_pool = int(g.relu), int(g.pool)
+        (bt.pH, bt.pW), bt.pC, bt.pCs = g.out_grid, g.C, g.Cs
+        bt.cH, bt.cW = g.lin_grid
+        bt.dy = bufs.dout.data_ptr()
+        if g.rate > 0:
+            bt.drop_thr, bt.drop_scale = dropout_pair(g.rate)
+        bt.seed, bt.stream_id = ex.seed, g.stream
         # write-through gradient stores (16-byte sc1; byte offsets < 2 GB)
-        bt.wt = int(bool(int(tune("wt")) & 2) and dyb.numel() * 2 < (1 << 31))
+        bt.wt = int(bool(int(tune("wt")) & 2) and bufs.dout.numel() * 2 < (1 << 31))
         return bt
 
     # ---------------------------------------------------------------- step program: forward
     def _add(self, name, fn, tag="main", **args):
         self.launches.append(Launch(name, fn, tag, args))
 
-    def _act_args(self, kind, g, bwd):
-        """ActArgs of stage g ('conv' | 'dense') with a hidden activation: the forward launch (in
-        place on the stage output, with the stage's dropout in a training step) or the backward
-        launch (in place on the stage's gradient buffer, reading the saved output)."""
-        ex, K = self.ex, self.ex.K
+    def _act_args(self, g, bwd):
+        """ActArgs of stage g with a hidden activation: the forward launch (in place on the stage
+        output, with the stage's dropout in a training step) or the backward launch (in place on
+        the stage's gradient buffer, reading the saved output)."""
+        ex, K, bufs = self.ex, self.ex.K, self.stage_bufs(g)
         a = K.ActArgs()
-        if kind == "conv":
-            out, grad = self.conv_out[g.i], self.conv_dy[g.i]
-            if g.bn is not None:
-                grad = self.bn["conv", g.i].dp
-            a.rows, a.C, a.Cs = self.bs * g.Hp * g.Wp, g.Cout, g.Cs_out
-        else:
-            out, grad = self.dense_out[g.j], self.dense_dh[g.j]
-            if g.bn is not None:
-                grad = self.bn["dense", g.j].dp
-            a.rows, a.C, a.Cs = self.bs, g.N, g.Ns
+        Hp, Wp = g.out_grid
+        a.rows, a.C, a.Cs = self.bs * Hp * Wp, g.C, g.Cs
         a.act, a.alpha = K.ACT_CODES[g.act], g.act_alpha
         if bwd:
-            a.x, a.y = grad.data_ptr(), out.data_ptr()
+            a.x, a.y = bufs.dout.data_ptr(), bufs.out.data_ptr()
             if g.rate > 0:       # the saved output carries the dropout scale: undo it (fp32(1 - rate))
                 a.y_scale = float(np.float32(1.0 - g.rate))
         else:
-            a.x = out.data_ptr()
-            if self.training and g.rate > 0:
+            a.x = bufs.out.data_ptr()
+            if self.training and g.dropout_in == "act":
                 a.drop_thr, a.drop_scale = dropout_pair(g.rate)
             a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
         return a
 
-    def _add_act_bwd(self, src: Src):
-        """Behind the launch that stored the gradient wrt ``src``'s output through its BwdThrough
-        (dropout mask applied, prev_relu = 0): the multiplication by A' of a stage with a hidden
-        activation, before anything reads that gradient buffer; and for a stage with a
-        BatchNormalization the two bn.hip backward launches, which turn that buffer into the stage's dz."""
-        if src.kind == "input":
+    def _add_stage_tail_fwd(self, g):
+        """Behind stage g's linear kernels, as the stage has them: bn_stats (training) ->
+        bn_apply_fwd -> act_fwd (A and, unless an earlier launch carried it, the stage's dropout,
+        in place)."""
+        K = self.ex.K
+        if g.bn is not None:
+            a = self._bn_args(g)
+            if self.training:
+                self._add("bn_stats_" + g.tag, lambda s, a=a: K.bn_stats(a, s), bn=a)
+            self._add("bn_apply_fwd_" + g.tag, lambda s, a=a: K.bn_apply_fwd(a, s), bn=a)
+        if g.act is not None:
+            fa = self._act_args(g, False)
+            self._add("act_fwd_" + g.tag, lambda s, a=fa: K.act_fwd(a, s), act=fa)
+
+    def _add_stage_tail_bwd(self, g):
+        """Behind the launch that stored the gradient wrt stage g's output (None: the model input)
+        through its BwdThrough (dropout mask applied, prev_relu = 0): act_bwd, the multiplication by
+        A' of a stage with a hidden activation, before anything reads that gradient buffer; and for
+        a stage with a BatchNormalization bn_bwd_reduce -> bn_bwd_apply (the dbeta / dgamma slabs,
+        and the dense dz the stage's wgrad / dgrad read)."""
+        if g is None:
             return
-        g = self.ex.convs[src.idx] if src.kind == "conv" else self.ex.denses[src.idx]
         K = self.ex.K
         if g.act is not None:
-            a = self._act_args(src.kind, g, True)
-            self._add("act_bwd_%s%d" % (src.kind[0], src.idx), lambda s, a=a: K.act_bwd(a, s), act=a)
+            a = self._act_args(g, True)
+            self._add("act_bwd_" + g.tag, lambda s, a=a: K.act_bwd(a, s), act=a)
         if g.bn is not None:
-            # ... then the BatchNormalization backward: the dbeta / dgamma slabs, and the dense dz
-            # the stage's wgrad / dgrad read
-            b = self._bn_args(src.kind, g)
-            tag = "%s%d" % (src.kind[0], src.idx)
-            self._add("bn_bwd_reduce_" + tag, lambda s, a=b: K.bn_bwd_reduce(a, s), bn=b)
-            self._add("bn_bwd_apply_" + tag, lambda s, a=b: K.bn_bwd_apply(a, s), bn=b)
+            b = self._bn_args(g)
+            self._add("bn_bwd_reduce_" + g.tag, lambda s, a=b: K.bn_bwd_reduce(a, s), bn=b)
+            self._add("bn_bwd_apply_" + g.tag, lambda s, a=b: K.bn_bwd_apply(a, s), bn=b)
 
     def _build_args(self):
         """The step program, stage by stage; each stage appends its launches."""
@@ -874,8 +761,7 @@ class BatchPlan(GeometryMixin):
         # of conv_stack=0, each such layer's linear kernel followed by its act_fwd launch)
         # (a conv stage with a BatchNormalization likewise: its linear kernel stores the un-pooled
         # pre-activation for the bn.hip launches)
-        conv_act = any(g.act is not None or g.bn is not None for g in ex.convs)
-        stack = self._conv_stack_args(training) if tune("conv_stack") and not conv_act else None
+        stack = self._conv_stack_args(training) if tune("conv_stack") and all(g.plain for g in ex.convs) else None
         # Prologue-free step (conv stack + a hidden dense layer + optimizer-written packs): the
         # stack reads its images straight from the dataset through the cursor and permutation
         # (recording each image's dataset row for the first layer's wgrad and the head's
@@ -924,27 +810,19 @@ class BatchPlan(GeometryMixin):
             a.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
             a.N = g.Cout
             a.mode = 0
-            a.relu, a.pool = int(g.relu), int(g.pool)
-            a.out = self.conv_out[g.i].data_ptr()
-            a.Cs_out, a.Hp, a.Wp = g.Cs_out, g.Hp, g.Wp
-            if g.bn is not None:
-                # the linear, un-pooled, dropout-free form: z for the bn.hip launches
-                a.relu, a.pool = 0, 0
-                a.out = self.bn["conv", g.i].z.data_ptr()
-                a.Hp, a.Wp = g.Ho, g.Wo
-            elif g.pool:
-                a.code = self.conv_code[g.i].data_ptr()
-            if self.training and g.rate > 0 and g.act is None and g.bn is None:
+            # (a BatchNormalization stage in its linear, un-pooled form: z for the bn.hip launches)
+            lin, bufs = g.linear, self.stage_bufs(g)
+            a.relu, a.pool = int(lin.relu), int(lin.pool)
+            a.out = bufs.lin_out.data_ptr()
+            a.Cs_out, a.Hp, a.Wp = g.Cs_out, lin.Hp, lin.Wp
+            if lin.pool:
+                a.code = bufs.code.data_ptr()
+            if self.training and g.dropout_in == "linear":
                 a.drop_thr, a.drop_scale = dropout_pair(g.rate)
             a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
-            self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, g.pool and g.bn is None), ca=a)
-            if g.bn is not None:
-                self._add_bn_fwd("conv", g)
-            if g.act is not None:
-                # the linear conv (+ pool) above, then A and the stage's dropout in place
-                fa = self._act_args("conv", g, False)
-                self._add("act_fwd_c%d" % g.i, lambda s, a=fa: K.act_fwd(a, s), act=fa)
-            x_buf = self.conv_out[g.i]
+            self._add("conv_fwd%d" % g.i, self._conv_launch(a, g.NT, lin.pool), ca=a)
+            self._add_stage_tail_fwd(g)
+            x_buf = bufs.out
 
     def _build_dense_fwd(self, sb):
         """The hidden dense layers: split-K GEMM + epilogue each.  Returns the last layer's
@@ -967,29 +845,20 @@ class BatchPlan(GeometryMixin):
             e.part = a.part
             e.splits, e.M, e.N, e.Ns, e.ldp = splits, bs, g.N, g.Ns, g.NT * 16
             e.bias = ex.store.view(ds.dense, "bias").data_ptr() if ds.dense.use_bias else 0
-            e.relu = int(g.relu)
-            e.out = self.dense_out[g.j].data_ptr()
-            if g.bn is not None:
-                e.relu, e.out = 0, self.bn["dense", g.j].z.data_ptr()
-            if self.training and g.rate > 0 and g.act is None and g.bn is None:
+            e.relu = int(g.relu and g.bn is None)      # (a BatchNormalization stage: the linear z)
+            e.out = self.stage_bufs(g).lin_out.data_ptr()
+            if self.training and g.dropout_in == "linear":
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head") and g.act is None and g.bn is None):
+                    and tune("fuse_head") and g.plain):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
                 self.head_blocks = cdiv(bs, K.head_rows_per_block(True))
             else:
                 self._add("dense_epi%d" % g.j, lambda s, e=e: K.dense_epi(e, s), epi=e)
-            if g.bn is not None:
-                # (never the head's epilogue: fuse_head=0 structure)
-                self._add_bn_fwd("dense", g)
-            if g.act is not None:
-                # the linear epilogue above (never the head's: fuse_head=0 structure), then A and
-                # the layer's dropout in place
-                fa = self._act_args("dense", g, False)
-                self._add("act_fwd_d%d" % g.j, lambda s, a=fa: K.act_fwd(a, s), act=fa)
+            self._add_stage_tail_fwd(g)      # (behind the epilogue, never the head's: fuse_head=0 structure)
         return head_epi
 
     def _build_head(self, head_epi):
@@ -1051,7 +920,8 @@ class BatchPlan(GeometryMixin):
             descs.append(RedDesc(self.head_bslab.data_ptr(), hd.N, self.head_blocks, hd.N, hb.offset, hb.numel,
                                  RED_BIAS))
         self._add_group(hw, descs, hb)
-        self._add_act_bwd(ex.head_src)     # (the head stored the last hidden stage's gradient)
+        # (the head stored the last hidden stage's gradient)
+        self._add_stage_tail_bwd(ex.stage_of(ex.head_src))
         # opt-in: the dense layer's optimizer update inside its (one-split) wgrad kernel.  Measured
         # slower on RPV at batch 128: the 128 wgrad workgroups move the layer's 14 MB of optimizer
         # state at per-CU bandwidth (wgrad 6.1 -> 9.7 us) while the end-of-step reduction, which
@@ -1062,9 +932,7 @@ class BatchPlan(GeometryMixin):
         # profiles/r4c_ab_legacy.txt); "1" = every one-split layer; "0" = off
         dense_opt = str(tune("dense_opt")).lower()
         self.dense_opt_ok = (ex.reducer is None and tune("fuse_optim")
-                             and dense_opt not in ("0", "false", "off", "no")
-                             and ex.opt.kind not in STANDALONE_KINDS and not ex.clips
-                             and not ex.regs)
+                             and dense_opt not in ("0", "false", "off", "no") and ex.inline_update_ok)
         self.dense_opt_all = dense_opt in ("1", "true", "on", "yes")
 
     def _dense_wgrad(self, g, ds, direct):
@@ -1156,7 +1024,7 @@ class BatchPlan(GeometryMixin):
             # in one launch with it (dense_bwd_pair: dX workgroups would read a pack the
             # wgrad workgroups are rewriting)
             self._add(dname, dl, da=da)
-            self._add_act_bwd(g.src)
+            self._add_stage_tail_bwd(self.ex.stage_of(g.src))
         if dual:
             # one launch for the dense wgrad and dX (independent GEMMs over dH); the layer's
             # slabs are final after it
@@ -1176,7 +1044,7 @@ class BatchPlan(GeometryMixin):
                                                           g.src.Cs)]
         if bsp is not None and not fused_opt:
             descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
-        bn_descs, bn_specs = self._bn_descs("dense", g)
+        bn_descs, bn_specs = self._bn_descs(g)
         lo, hi = self._add_group(sp, descs + bn_descs, bsp, bn_specs)
         if fused_opt:
             self.dense_fused_opt.append((wa, hi - lo))
@@ -1185,7 +1053,7 @@ class BatchPlan(GeometryMixin):
         if da is not None:
             self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
             if not dx_first:
-                self._add_act_bwd(g.src)
+                self._add_stage_tail_bwd(self.ex.stage_of(g.src))
 
     def _dgrad_args(self, g):
         """ConvMMArgs of conv layer g's dgrad (a stride-1 conv over the input-dilated dY with
@@ -1206,7 +1074,7 @@ class BatchPlan(GeometryMixin):
         a.NT = g.NTd
         a.mode, a.flat_out = 1, 0
         a.st = ex.state.data_ptr()
-        a.bt = self._bt_for(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
+        a.bt = self._bt_for(prev.out_src)
         a.tm = tune("dgrad_tm", layer=g.i)      # co-scheduled dgrad m-tiles per wave per pass
         a.dbg = tune("dgrad_dbg")            # A/B switches (ConvMMArgs::dbg; exact ones only)
         return a
@@ -1216,11 +1084,8 @@ class BatchPlan(GeometryMixin):
         one dual launch where both take the halo kernels -- and the layer's reduction group."""
         ex, K, store = self.ex, self.ex.K, self.ex.store
         xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
-        g_stage = g
-        if g.bn is not None:
-            # conv_dy holds the dense un-pooled dz (bn_bwd_apply): the wgrad / dgrad of a linear,
-            # un-pooled stage
-            g = replace(g, pool=False, relu=False, rate=0.0, Hp=g.Ho, Wp=g.Wo)
+        # (a BatchNormalization stage: conv_dy holds the dense un-pooled dz of bn_bwd_apply)
+        g_stage, g = g, g.linear
         wide = self._wide(g.Cs_in, g.KS, g.NT)
         if wide:
             w = self._wgrad_tile_args(xin, g, cs.conv.use_bias)
@@ -1250,14 +1115,13 @@ class BatchPlan(GeometryMixin):
                          g.KH, g.KW, g.Cin, g.Cout, g.Cs_in)]
         if bsp is not None:
             descs.append(RedDesc(w.bslab.data_ptr(), ld, w.splits, ld, bsp.offset, bsp.numel, RED_BIAS))
-        bn_descs, bn_specs = self._bn_descs("conv", g_stage)
+        bn_descs, bn_specs = self._bn_descs(g_stage)
         self._add_group(sp, descs + bn_descs, bsp, bn_specs)
         if ca is not None:
             if not dual:
                 self._add(dname, self._conv_launch(ca, g.NTd, False), ca=ca)
             self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
-            prev = ex.convs[g.i - 1]
-            self._add_act_bwd(Src("conv", prev.i, prev.Cout, prev.Cs_out, prev.Hp, prev.Wp))
+            self._add_stage_tail_bwd(ex.convs[g.i - 1])
 
     # ---------------------------------------------------------------- step program: reductions
     def _build_reduce(self):
@@ -1290,41 +1154,23 @@ class BatchPlan(GeometryMixin):
             hi = max(self.red_groups[i].hi for i in bg)
             self.bucket_tables.append((lo, hi, tab))
             inserts.append((max(self.red_groups[i].ready for i in bg), k))
-        extra = []
-        if reducer is not None and ex.regs:
-            # data parallel: every rank adds the regularizers' term to its OWN reduced gradient
-            # (weights are identical on all ranks: the average is avg(g) + reg'(w)), ahead of its
-            # clip and of the all-reduce; every rank's loss takes the penalty
-            ra = ex._reg_args(self.bs, True)
-            extra.append(("weight_reg_b%d", lambda k: (lambda s: ex.K.weight_reg(ra, s)), "main"))
-        if reducer is not None and ex.clips:
-            # data parallel: each rank clips its OWN reduced gradient by its own norm, in memory,
-            # ahead of the all-reduce (Horovod's order: clip, then average); the update behind
-            # the all-reduce is the ordinary unclipped one with grad_scale = 1 / size
-            ca = ex._clip_args()
-            if ex.clipnorm:
-                extra.append(("grad_sqnorm_b%d", lambda k: (lambda s: ex.K.grad_sqnorm(ca, s)), "main"))
-            extra.append(("grad_clip_apply_b%d", lambda k: (lambda s: ex.K.grad_clip_apply(ca, s)), "main"))
+        whole = self._whole_grad_launches(dp=reducer is not None)
+        # data parallel: behind the (one) bucket's slab reduction, ahead of its all-reduce
+        extra = [(name + "_b%d", lambda k, fn=fn: fn, "main") for name, fn, _ in whole] if reducer is not None else []
         if self.comm_in_graph:
             xk = getattr(reducer, "xgmi_bucket", None)
-            if (ex.clips or ex.regs) and xk is not None:
+            if ex.whole_grad_first and xk is not None:
                 raise AssertionError("gradient clipping / weight regularizers run on the RCCL plane only")
             self._plan_bucket_exchange(reducer, xk, bucket_groups, dp_early)
             extra += self._comm_launches(reducer, xk, len(bucket_groups))
         self.launches, self.bucket_ready = splice_bucket_launches(
             self.launches, inserts,
             [("reduce_b%d", lambda k: (lambda s: self._launch_bucket_reduce(k, s)), "side")] + extra)
-        if reducer is None and ex.regs:
-            # single GPU: the regularizers' term joins the whole reduced gradient (in place:
-            # store.grad holds the regularized gradient) after the last slab reduction, ahead of
-            # the norm launch and the update -- inside the captured step
-            ra = ex._reg_args(self.bs, True)
-            self._add("weight_reg", lambda s, a=ra: ex.K.weight_reg(a, s), reg=ra)
-        if reducer is None and ex.clipnorm:
-            # single GPU: the norm of the whole reduced gradient, after the last slab reduction
-            # and ahead of the clipped optimizer launch (_launch_optim) -- inside the captured step
-            ca = ex._clip_args()
-            self._add("grad_sqnorm", lambda s, a=ca: ex.K.grad_sqnorm(a, s), clip=ca)
+        if reducer is None:
+            # single GPU: after the last slab reduction, ahead of the (clipped) optimizer launch
+            # (_launch_optim) -- inside the captured step
+            for name, fn, args in whole:
+                self._add(name, fn, **args)
         spans = [(lo, hi) for lo, hi, _ in self.bucket_tables]
         if self.comm_in_graph and self.optim_on_comm:
             # a comm-stream optimizer writes its layers' packs: never while a later
@@ -1334,6 +1180,28 @@ class BatchPlan(GeometryMixin):
         if reducer is None:
             spans = spans + [e[1] for e in self.early_red.values()]
         check_bucket_cover(spans, ex.store.numel)
+
+    def _whole_grad_launches(self, dp: bool):
+        """The launches over the WHOLE reduced gradient, in their order, behind the last slab
+        reduction and ahead of any update (HipExecutor.whole_grad_first):
+        [(name, fn(stream), Launch.args)].
+        weight_reg: the regularizers' term joins the gradient in place (data parallel: every rank
+        adds it to its OWN reduced gradient -- weights are identical on all ranks, the average is
+        avg(g) + reg'(w) -- and every rank's loss takes the penalty).
+        grad_sqnorm: the global norm for clipnorm, which the clipped optimizer launch reads.
+        grad_clip_apply, data parallel only: each rank clips its OWN reduced gradient by its own
+        norm, in memory, ahead of the all-reduce (Horovod's order: clip, then average); the update
+        behind the all-reduce is the ordinary unclipped one with grad_scale = 1 / size."""
+        ex, out = self.ex, []
+        if ex.regs:
+            ra = ex._reg_args(self.bs, True)
+            out.append(("weight_reg", lambda s, a=ra: ex.K.weight_reg(a, s), {"reg": ra}))
+        ca = ex._clip_args() if ex.clips else None
+        if ex.clipnorm:
+            out.append(("grad_sqnorm", lambda s, a=ca: ex.K.grad_sqnorm(a, s), {"clip": ca}))
+        if dp and ex.clips:
+            out.append(("grad_clip_apply", lambda s, a=ca: ex.K.grad_clip_apply(a, s), {"clip": ca}))
+        return out
 
     def _assign_buckets(self):
         """Single GPU: the groups of each bucket (lists of red_groups indices), less the groups
@@ -1346,10 +1214,8 @@ class BatchPlan(GeometryMixin):
         # ... with the optimizer fused into it when its table covers every parameter
         covered = sum(d.numel for grp in self.red_groups for d in grp.descs)
         covered += sum(n for _, n in self.dense_fused_opt)
-        # (a clipping optimizer: the global norm needs every reduced gradient before any update)
-        # (weight regularizers: their term joins the whole reduced gradient before any update)
-        self.optim_fused = (one and covered == self.ex.store.numel and tune("fuse_optim") and not self.ex.clips
-                            and not self.ex.regs)
+        self.optim_fused = (one and covered == self.ex.store.numel and tune("fuse_optim")
+                            and not self.ex.whole_grad_first)
         if not self.optim_fused:
             # the step ends with a full optimizer launch after all: the dense layers keep
             # writing their gradient in place, but leave the update -- and the bf16 pack
@@ -1376,10 +1242,10 @@ class BatchPlan(GeometryMixin):
     def _assign_buckets_dp(self, reducer):
         """Data parallel: the reducer's buckets, and the groups reduced early inside the
         backward (with their xGMI push / exchange planned).  Returns (bucket groups, early groups)."""
-        # (a clipping optimizer or a regularized model: the reducers' configure gives ONE bucket,
-        # from optimizer.clips / the needs_local_gradient flag make_reducer passes)
+        # (whole_grad_first: the reducers' configure gives ONE bucket, from optimizer.clips / the
+        # needs_local_gradient flag make_reducer passes)
         bucket_groups = reducer.configure([(grp.lo, grp.hi) for grp in self.red_groups])
-        if (self.ex.clips or self.ex.regs) and len(bucket_groups) != 1:
+        if self.ex.whole_grad_first and len(bucket_groups) != 1:
             raise AssertionError("gradient clipping / weight regularizers: the data-parallel step needs ONE bucket")
         # one bucket at the end of the backward (the adaptive plan for gradients <= 16 MB):
         # the groups final before the first dual launch (head, dense -- the single-GPU
@@ -1519,11 +1385,9 @@ class BatchPlan(GeometryMixin):
         assigned.  grad_only (data-parallel step): reduction only -- no update, no pack
         writes, so later pack readers do not matter."""
         self.early_red = {}
-        # (the extras choose the optimizer at run time among five kinds: the others' head and
-        # dense groups stay in the end-of-step / per-bucket reduce_optim_kernel<KIND> launch)
-        # (nor with gradient clipping: no update before the global norm of every gradient; nor with
-        # weight regularizers: no update before their term has joined the reduced gradient)
-        if not tune("early_reduce") or self.ex.opt.kind in STANDALONE_KINDS or self.ex.clips or self.ex.regs:
+        # (not inline_update_ok: the head and dense groups stay in the end-of-step / per-bucket
+        # reduce_optim_kernel<KIND> launch)
+        if not tune("early_reduce") or not self.ex.inline_update_ok:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous

@@ -11,15 +11,7 @@ import torch
 
 from ..utils.tune import tune
 from . import lds_layout
-from .step_program import dropout_pair
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def r8(x):
-    return cdiv(x, 8) * 8
+from .step_program import cdiv, dropout_pair
 
 
 def _pow2_le(x, cap):

@@ -1,12 +1,180 @@
-"""The step program of the HIP backend, GPU-free: what a launch, a slab-reduction descriptor
-and a reduction group are, and the pure list transformations that place the per-bucket
+"""The step program of the HIP backend, GPU-free: the geometry of a model's hidden stages (one
+record per stage, the same view for a conv and a dense one), what a launch, a slab-reduction
+descriptor and a reduction group are, and the pure list transformations that place the per-bucket
 launches into a step (executor_hip.BatchPlan builds the entries; hip_geometry sizes them)."""
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
+from operator import attrgetter
 from typing import Callable, List, NamedTuple, Optional, Tuple
 
 from ..ops.rng import keep_threshold
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def r8(x):
+    return cdiv(x, 8) * 8
+
+
+@dataclass
+class Src:
+    """An activation buffer feeding the next stage (for flatten mapping / bwd-through)."""
+    kind: str            # 'input' | 'conv' | 'dense'
+    idx: int
+    C: int               # logical channels (flatten mapping)
+    Cs: int              # padded channel stride
+    H: int = 1
+    W: int = 1
+
+    @property
+    def width(self):
+        return self.H * self.W * self.Cs
+
+
+@dataclass(kw_only=True)
+class Stage:
+    """What a hidden stage is around its linear kernel (plan.ConvStage / DenseStage), and the view
+    its tail launches are written against: ``kind`` 'conv' | 'dense', ``idx`` (ConvGeo.i /
+    DenseGeo.j), ``C`` / ``Cs`` the logical and padded output channels, ``lin_grid`` the grid of the
+    linear kernel's output and ``out_grid`` the stage output's (pooled; (1, 1) for a dense stage)."""
+    relu: bool
+    rate: float
+    stream: int                    # RNG stream id of the dropout
+    act: Optional[str] = None      # hidden activation other than relu / linear
+    act_alpha: float = 0.0
+    bn: Optional[object] = None    # the stage's BatchNormalization layer
+    lin_grid = out_grid = (1, 1)
+
+    @classmethod
+    def of(cls, st, *geo):
+        """The record of plan stage ``st`` with the positional geometry ``geo``."""
+        return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn)
+
+    @property
+    def tag(self):
+        """'c0', 'd1': the suffix of the stage's tail launch names."""
+        return "%s%d" % (self.kind[0], self.idx)
+
+    @property
+    def out_src(self):
+        return Src(self.kind, self.idx, self.C, self.Cs, *self.out_grid)
+
+    @property
+    def plain(self):
+        """Neither a table activation nor a BatchNormalization: the linear kernels are the whole
+        stage (the condition for the conv stack and for the head launch running the epilogue)."""
+        return self.act is None and self.bn is None
+
+    @property
+    def dropout_in(self):
+        """The launch that carries the stage's dropout in a training step (plan.py): the 'linear'
+        kernel iff the stage is plain, bn_apply_fwd ('bn') iff it has a BatchNormalization and no
+        table activation, else act_fwd ('act'); None at rate 0."""
+        if not self.rate > 0:
+            return None
+        return "linear" if self.plain else "bn" if self.act is None else "act"
+
+
+def _alias(name):
+    return property(attrgetter(name))
+
+
+@dataclass
+class ConvGeo(Stage):
+    i: int
+    H: int
+    W: int
+    Cin: int
+    Cs_in: int
+    Ho: int
+    Wo: int
+    Cout: int
+    Cs_out: int
+    Hp: int
+    Wp: int
+    KH: int
+    KW: int
+    stride: int
+    pad_t: int
+    pad_l: int
+    pool: bool
+    KS: int = 0
+    NT: int = 0
+    KSd: int = 0
+    NTd: int = 0
+    pack_fwd: int = 0
+    pack_dgrad: int = -1
+    kind = "conv"
+    idx, C, Cs = _alias("i"), _alias("Cout"), _alias("Cs_out")
+    lin_grid = property(lambda g: (g.Ho, g.Wo))
+    out_grid = property(lambda g: (g.Hp, g.Wp))
+
+    @property
+    def linear(self):
+        """The form the stage's conv kernels run in: a BatchNormalization stage's forward, wgrad and
+        dgrad are those of a linear, un-pooled, dropout-free stage (the bn.hip launches do the rest)."""
+        return self if self.bn is None else replace(self, pool=False, relu=False, rate=0.0, Hp=self.Ho, Wp=self.Wo)
+
+
+@dataclass
+class DenseGeo(Stage):
+    j: int
+    src: Src
+    K: int
+    N: int
+    Ns: int
+    KS: int = 0
+    NT: int = 0
+    KSb: int = 0
+    NTb: int = 0
+    pack_fwd: int = 0
+    pack_bwd: int = -1
+    kind, pool = "dense", False
+    idx, C, Cs = _alias("j"), _alias("N"), _alias("Ns")
+
+
+def stage_geometry(plan):
+    """(input Src, [ConvGeo], [DenseGeo], head Src, head activation code) of a models.plan.Plan."""
+    shape = plan.input_shape
+    H, W, Cin = shape if len(shape) == 3 else (1, 1, shape[0])
+    Cs_in = 4 if Cin <= 4 else r8(Cin)
+    src = inp = Src("input", 0, Cin, Cs_in, H, W)
+    convs, denses = [], []
+    for i, cs in enumerate(plan.convs):
+        Ho, Wo, Cout = cs.conv_shape
+        Hp, Wp, _ = cs.out_shape
+        pt, _, pl, _ = cs.pads
+        kh, kw = cs.conv.kernel_size
+        g = ConvGeo.of(cs, i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
+                       cs.pool is not None)
+        g.KS = cdiv(kh * kw * Cs_in, 32)
+        g.NT = cdiv(Cout, 16)
+        if i > 0:
+            g.KSd = cdiv(kh * kw * g.Cs_out, 32)
+            g.NTd = cdiv(Cin, 16)
+        convs.append(g)
+        H, W, Cin, Cs_in = Hp, Wp, Cout, g.Cs_out
+        src = g.out_src
+    for j, ds in enumerate(plan.denses):
+        g = DenseGeo.of(ds, j, src, ds.K, ds.N, r8(ds.N))
+        if g.K != src.H * src.W * src.C:
+            raise ValueError("dense %d input width mismatch" % j)
+        g.KS = cdiv(src.width, 32)
+        g.NT = cdiv(ds.N, 16)
+        if j > 0 or convs:
+            g.KSb = cdiv(g.Ns, 32)
+            g.NTb = cdiv(src.width, 16)
+        denses.append(g)
+        src = g.out_src
+    hd = plan.head
+    if hd.K != src.H * src.W * src.C:
+        raise ValueError("head input width mismatch")
+    if hd.N > 16:
+        raise NotImplementedError("output layers wider than 16 units")
+    return inp, convs, denses, src, {None: 0, "sigmoid": 1, "softmax": 2}[hd.activation]
 
 
 class Launch(NamedTuple):
