@@ -176,7 +176,21 @@ struct ConvMMArgs {
   int xpix = 0;
   int kpipe = 0;                 // software-pipelined k loop with scalar tap offsets (Cs % 32 == 0)
   int tm = 0;                    // co-scheduled dgrad: m-tiles per wave per pass (0: launch_dual_halo picks)
+  // co-scheduled dgrad: run the dual instance whose dgrad geometry is fixed at compile time too
+  // (dual_halo_fix_body.h) when its signature matches (dual_halo_dgrad_fixed); 0 = the dual
+  // launch as without it (A/B and the bit-identity tests).  Host-only; it sits in the 4 bytes of
+  // padding that ended the struct, so the kernel-argument layout of every ConvMMArgs kernel is
+  // what it was without it.
+  int spec = 1;
 };
+
+// The ConvMMArgs / BwdThrough fields that are geometry of the halo conv body: the ONE list behind
+// the body's geometry traits (conv_halo_body.h, bwd_through.h), the dgrad signatures and the
+// host's field-by-field match (wgrad_sig.h / wgrad_sig.hip)
+#define CV_GEO_INTS(F)                                                                                       \
+  F(H) F(W) F(Cs_in) F(Ho) F(Wo) F(KH) F(KW) F(stride) F(pad_t) F(pad_l) F(in_dil) F(KS) F(NT) F(pool) F(Hp) \
+  F(Wp) F(Cs_out) F(R) F(in_pH) F(in_pW) F(xpix) F(kpipe)
+#define CV_BT_INTS(F) F(pCs) F(pC) F(prev_relu) F(wt)
 
 // Layer-fused forward of a conv stack (conv_stack.hip): one workgroup per image, all
 // stages' activations in LDS.  Stride-1 convs with optional 2x2 max-pool.

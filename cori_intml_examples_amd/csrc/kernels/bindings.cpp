@@ -24,6 +24,7 @@ size_t wgrad_halo_lds_bytes(const WgradArgs& a, int MT, int NTT);
 int wgrad_halo_resident(const WgradArgs& a, int MT, int NTT, bool bias);
 int wgrad_halo_variant(const WgradArgs& a, int MT, int NTT);
 int dual_halo_variant(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp, bool extras);
+bool dual_halo_dgrad_fixed(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp, bool extras);
 int head_rows_per_block(bool fused);
 int head_epi_max();
 void launch_wgrad(const WgradArgs& a, int ktw, int ntt, int splits, hipStream_t s);
@@ -143,7 +144,8 @@ PYBIND11_MODULE(_kernels, m) {
       RW(ConvMMArgs, Cs_out) RW(ConvMMArgs, Hp) RW(ConvMMArgs, Wp) PTR(ConvMMArgs, code)
       RW(ConvMMArgs, drop_thr) RW(ConvMMArgs, drop_scale) RW(ConvMMArgs, seed) RW(ConvMMArgs, stream_id)
       PTR(ConvMMArgs, st) RW(ConvMMArgs, bt) RW(ConvMMArgs, R) PTR(ConvMMArgs, in_code) PTR(ConvMMArgs, zero)
-      RW(ConvMMArgs, in_pH) RW(ConvMMArgs, in_pW) RW(ConvMMArgs, dbg) PTR(ConvMMArgs, ts) RW(ConvMMArgs, xpix) RW(ConvMMArgs, kpipe) RW(ConvMMArgs, tm);
+      RW(ConvMMArgs, in_pH) RW(ConvMMArgs, in_pW) RW(ConvMMArgs, dbg) PTR(ConvMMArgs, ts) RW(ConvMMArgs, xpix) RW(ConvMMArgs, kpipe) RW(ConvMMArgs, tm)
+      RW(ConvMMArgs, spec);
 
   py::class_<WgradArgs>(m, "WgradArgs")
       .def(py::init<>())
@@ -373,6 +375,8 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("wgrad_halo_resident", &wgrad_halo_resident);
   m.def("wgrad_halo_variant", &wgrad_halo_variant);
   m.def("dual_halo_variant", &dual_halo_variant, py::arg("ca"), py::arg("ntc"), py::arg("wa"), py::arg("MT"),
+        py::arg("NTT"), py::arg("xp") = false, py::arg("extras") = false);
+  m.def("dual_halo_dgrad_fixed", &dual_halo_dgrad_fixed, py::arg("ca"), py::arg("ntc"), py::arg("wa"), py::arg("MT"),
         py::arg("NTT"), py::arg("xp") = false, py::arg("extras") = false);
   m.def("head_rows_per_block", &head_rows_per_block, py::arg("fused") = false);
   m.def("conv_tile_lds_bytes", &conv_tile_lds_bytes);

@@ -27,30 +27,41 @@ __device__ __forceinline__ void bwd_through_store(const BwdThrough& t, int b, in
   t.dy[qi * t.pCs + c] = f2bf(g);
 }
 
+// Where bwd_through_store8 reads the geometry of the previous stage (CV_BT_INTS, args.h):
+// BtGeoRt the BwdThrough fields; the fixed form is part of CvGeoFix (conv_halo_body.h).  The
+// pointers and the dropout threshold / scale / seed / stream id always come from BwdThrough.
+struct BtGeoRt {
+#define F(n) \
+  __device__ __forceinline__ static int n(const BwdThrough& t) { return t.n; }
+  CV_BT_INTS(F)
+#undef F
+};
+
 // Vectorised form: 8 consecutive channels [c0, c0+8) of output pixel qi (flat index over
 // the previous stage's output grid); one 16-byte load of the saved output, one 16-byte store.
+template <class G = BtGeoRt>
 __device__ __forceinline__ void bwd_through_store8(const BwdThrough& t, size_t qi, int c0, const float* g,
                                                    uint32_t step) {
-  if (c0 >= t.pCs) return;
-  const size_t o = qi * t.pCs + c0;
+  if (c0 >= G::pCs(t)) return;
+  const size_t o = qi * G::pCs(t) + c0;
   bf16x8 prev = zero_bf16x8();
-  if (t.prev_relu) prev = load_bf16x8(t.prev_out + o);
+  if (G::prev_relu(t)) prev = load_bf16x8(t.prev_out + o);
   bf16x8 outv;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int c = c0 + k;
     float v = g[k];
-    if (c >= t.pC) {
+    if (c >= G::pC(t)) {
       v = 0.f;
     } else {
       if (t.drop_thr)
-        v = dropout_keep((uint32_t)(qi * (size_t)t.pC + c), t.seed, t.stream_id, step, t.drop_thr) ? v * t.drop_scale
-                                                                                                  : 0.f;
-      if (t.prev_relu && !(bf2f(prev[k]) > 0.f)) v = 0.f;
+        v = dropout_keep((uint32_t)(qi * (size_t)G::pC(t) + c), t.seed, t.stream_id, step, t.drop_thr) ? v * t.drop_scale
+                                                                                                      : 0.f;
+      if (G::prev_relu(t) && !(bf2f(prev[k]) > 0.f)) v = 0.f;
     }
     outv[k] = f2bf(v);
   }
-  if (t.wt) st_wt16(t.dy, (unsigned)(o * 2), __builtin_bit_cast(u32x4, outv));
+  if (G::wt(t)) st_wt16(t.dy, (unsigned)(o * 2), __builtin_bit_cast(u32x4, outv));
   else *reinterpret_cast<bf16x8*>(t.dy + o) = outv;
 }
 

@@ -6,6 +6,58 @@
 
 #include "bwd_through.h"
 
+// Where the body reads its geometry (template parameter G).  The pointers, the batch size B,
+// the StepState pointer and the backward-through dropout threshold / scale / seed / stream id
+// always come from ConvMMArgs.
+//   CvGeoRt: every value is the ConvMMArgs / BwdThrough field -- every kernel but the fixed duals.
+//   CvGeoFix<S>: constants of a dgrad signature S (wgrad_sig.h).  The staging index math and the
+//     divisors fold, and the path choices are made when the body is compiled: the one-batch
+//     prologue at one WU, the pooled expansion, the kfast k loop (fully unrolled, every halo
+//     offset an immediate; neither the table loop nor the table fill is compiled), the mode-1
+//     epilogue with whole n-tiles, and the tile / pass counts of whole blocks.
+// (CV_GEO_INTS / CV_BT_INTS, args.h: the one list of the geometry fields)
+struct CvGeoRt : BtGeoRt {
+  static constexpr bool fixed = false;
+  using Div = FastDiv;
+#define F(n) \
+  __device__ __forceinline__ static int n(const ConvMMArgs& a) { return a.n; }
+  CV_GEO_INTS(F)
+#undef F
+  __device__ __forceinline__ static bool in_coded(const ConvMMArgs& a) { return a.in_code != nullptr; }
+  __device__ __forceinline__ static constexpr bool onebatch() { return false; }
+};
+// x / d for x >= 0 by a divisor the compiler sees as a constant (FastDiv's interface)
+struct CvConstDiv {
+  int d;
+  __device__ __forceinline__ explicit CvConstDiv(int dd) : d(dd) {}
+  __device__ __forceinline__ int div(int x) const { return (int)((unsigned)x / (unsigned)d); }
+};
+template <class S>
+struct CvGeoFix {
+  static constexpr bool fixed = true;
+  using Sig = S;
+  using Div = CvConstDiv;
+#define F(n) \
+  __device__ __forceinline__ static constexpr int n(const ConvMMArgs&) { return S::n; }
+  CV_GEO_INTS(F)
+#undef F
+#define F(n) \
+  __device__ __forceinline__ static constexpr int n(const BwdThrough&) { return S::n; }
+  CV_BT_INTS(F)
+#undef F
+  __device__ __forceinline__ static constexpr bool in_coded(const ConvMMArgs&) { return S::pooled; }
+  // the one-batch prologue serves EVERY block of the layer: each block's halo meets the pooled
+  // area (pin), and no block has more pooled chunks than one batch (nq <= 256 * UQ, UQ = 4)
+  __device__ __forceinline__ static constexpr bool onebatch() {
+    constexpr int R_in = (S::R - 1) * S::stride + S::KH, W_in = (S::Wo - 1) * S::stride + S::KW;
+    constexpr int nrb = (S::Ho + S::R - 1) / S::R;
+    constexpr int yb_last = (nrb - 1) * S::R * S::stride - S::pad_t;
+    constexpr bool pin = S::pooled && S::in_dil == 1 && R_in > S::pad_t && yb_last < 2 * S::in_pH &&
+                         W_in > S::pad_l && -S::pad_l < 2 * S::in_pW;
+    return pin && (R_in / 2 + 1) * (W_in / 2 + 1) * (S::Cs_in / 8) <= 256 * 4;
+  }
+};
+
 // NTC n-tiles of the weight slice, TM m-tiles per wave per pass (each A fragment feeds NTC
 // MFMAs and each weight fragment TM), KCH k-steps per batch of independent reads.
 #define HALO_STAMP(i)                                                                \
@@ -15,23 +67,25 @@
 // INSTR: the ablation switches (dbg) and diagnostics stamps (a.ts) are compiled in.  The
 // co-scheduled dual launch instantiates <.., 1, false>: none of that code (nor the forward
 // epilogue) is in its instruction stream or its register allocation.
-template <int NTC, int TM, int KCH, bool CS4, int MODE = -1, bool INSTR = true>
+// G: where the body reads its geometry (CV_GEO_INTS / CV_BT_INTS, args.h); CvGeoRt by default
+template <int NTC, int TM, int KCH, bool CS4, int MODE = -1, bool INSTR = true, class G = CvGeoRt>
 __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx, const int by, char* smem) {
+  using Div = typename G::Div;
   const int dbg = INSTR ? a.dbg : 0;
   const int mode = MODE >= 0 ? MODE : a.mode;
-  const int KS = a.KS, R = a.R, s = a.stride, dil = a.in_dil, Cs = a.Cs_in;
+  const int KS = G::KS(a), R = G::R(a), s = G::stride(a), dil = G::in_dil(a), Cs = G::Cs_in(a);
   // halo pixel stride (elements): padded by the host's bank-conflict model (lds_layout.py)
-  const int XP = (CS4 || !a.xpix) ? Cs : a.xpix;
+  const int XP = (CS4 || !G::xpix(a)) ? Cs : G::xpix(a);
   const int ntab = CS4 ? KS * 8 : KS * 4;
   int* tab = reinterpret_cast<int*>(smem);
   const int tab_bytes = (ntab * 4 + 15) & ~15;
   bf16* zl = reinterpret_cast<bf16*>(smem + tab_bytes);      // 32 B of zeros
   bf16* wl = zl + 16;
   bf16* xl = wl + (size_t)KS * NTC * 64 * 8;
-  const int W_in = (a.Wo - 1) * s + a.KW;
-  const int R_in = (R - 1) * s + a.KH;
+  const int W_in = (G::Wo(a) - 1) * s + G::KW(a);
+  const int R_in = (R - 1) * s + G::KH(a);
   const int tid = threadIdx.x;
-  const int nrb = (a.Ho + R - 1) / R;
+  const int nrb = (G::Ho(a) + R - 1) / R;
   const int b = bx / nrb;
   const int oy0 = (bx - b * nrb) * R;
   const int nt0 = by * NTC;
@@ -44,10 +98,11 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   const int hcw = CS4 ? 4 : 8;
   const int hcpp = Cs / hcw;
   const int nch = R_in * W_in * hcpp;
-  const int yb = oy0 * s - a.pad_t, xb0 = -a.pad_l;
-  const bf16* xbase = a.in_code ? a.x + (size_t)b * a.in_pH * a.in_pW * Cs : a.x + (size_t)b * a.H * a.W * Cs;
-  const uint8_t* cbase = a.in_code ? a.in_code + (size_t)b * a.in_pH * a.in_pW * Cs : nullptr;
-  const FastDiv fcpp(hcpp), fwin(W_in);
+  const int yb = oy0 * s - G::pad_t(a), xb0 = -G::pad_l(a);
+  const bf16* xbase = G::in_coded(a) ? a.x + (size_t)b * G::in_pH(a) * G::in_pW(a) * Cs
+                                     : a.x + (size_t)b * G::H(a) * G::W(a) * Cs;
+  const uint8_t* cbase = G::in_coded(a) ? a.in_code + (size_t)b * G::in_pH(a) * G::in_pW(a) * Cs : nullptr;
+  const Div fcpp(hcpp), fwin(W_in);
   auto coords = [&](int i, int& c, int& iy, int& ix) -> bool {
     const int pix = fcpp.div(i);
     c = (i - pix * hcpp) * hcw;
@@ -60,34 +115,34 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       iy /= dil;
       ix /= dil;
     }
-    return ok && iy < a.H && ix < a.W;
+    return ok && iy < G::H(a) && ix < G::W(a);
   };
   auto halo8 = [&](int i) {
     int c, iy, ix;
     const bool ok = coords(i, c, iy, ix);
-    if (cbase) return unpool_load8(xbase, cbase, a.in_pH, a.in_pW, Cs, iy, ix, c, ok);
-    return load_bf16x8_if(ok, xbase + ((size_t)iy * a.W + ix) * Cs + c, xbase);
+    if (cbase) return unpool_load8(xbase, cbase, G::in_pH(a), G::in_pW(a), Cs, iy, ix, c, ok);
+    return load_bf16x8_if(ok, xbase + ((size_t)iy * G::W(a) + ix) * Cs + c, xbase);
   };
   // weights -> LDS
   auto wload = [&](int i) {
     const int ks = i / (NTC * 64);   // compile-time power of two
     const int rem = i - ks * NTC * 64;
     const int nt = nt0 + (rem >> 6);
-    const bool ok = nt < a.NT;
-    return load_bf16x8_if(ok, a.wpk + ((size_t)(ks * a.NT + nt) * 64 + (rem & 63)) * 8, a.wpk);
+    const bool ok = nt < G::NT(a);
+    return load_bf16x8_if(ok, a.wpk + ((size_t)(ks * G::NT(a) + nt) * 64 + (rem & 63)) * 8, a.wpk);
   };
   auto wstore = [&](int i, const bf16x8& v) { *reinterpret_cast<bf16x8*>(wl + (size_t)i * 8) = v; };
   const int nw = KS * NTC * 64;
   auto build_tab = [&]() {   // k-chunk -> halo offset table
-    const int KHW = a.KH * a.KW;
+    const int KHW = G::KH(a) * G::KW(a);
     const int cw = CS4 ? 4 : 8;
     for (int c = tid; c < ntab; c += 256) {
       const int k0 = c * cw;
       const int tap = k0 / Cs;
       int e = -1;
       if (tap < KHW) {
-        const int ky = tap / a.KW;
-        e = (ky * W_in + (tap - ky * a.KW)) * XP + (k0 - tap * Cs);
+        const int ky = tap / G::KW(a);
+        e = (ky * W_in + (tap - ky * G::KW(a))) * XP + (k0 - tap * Cs);
       }
       tab[c] = e;
     }
@@ -95,15 +150,17 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   // Pooled input (dY = unpool(dP, codes)): load each pooled chunk ONCE and expand it into the
   // (up to) four full-resolution halo pixels of its window -- a quarter of the global loads of
   // rebuilding every pixel from its window (unpool_load8 per pixel).
-  const bool pooled_in = !CS4 && cbase && dil == 1 && !(dbg & 16);
-  const int Ha = 2 * a.in_pH, Wa = 2 * a.in_pW;
+  const bool pooled_in = !CS4 && (G::fixed ? G::in_coded(a) : cbase != nullptr) && dil == 1 && !(dbg & 16);
+  const int Ha = 2 * G::in_pH(a), Wa = 2 * G::in_pW(a);
   const int y_lo = max(yb, 0), y_hi = min(yb + R_in, Ha);
   const int x_lo = max(xb0, 0), x_hi = min(xb0 + W_in, Wa);
-  const bool pin = y_lo < y_hi && x_lo < x_hi;
+  // (fixed geometry: G::onebatch() has proved pin for every block, so npx and the column
+  // bounds are constants and npy / nq depend on the block row alone)
+  const bool pin = (G::fixed && G::onebatch()) || (y_lo < y_hi && x_lo < x_hi);
   const int py0 = y_lo >> 1, npy = pin ? ((y_hi - 1) >> 1) - py0 + 1 : 0;
   const int px0 = x_lo >> 1, npx = pin ? ((x_hi - 1) >> 1) - px0 + 1 : 1;
   const int nq = npy * npx * hcpp;
-  const FastDiv fnpx(npx);
+  const Div fnpx(npx);
   constexpr int UQ = 4;
   // halo pixels outside the pooled area (padding, odd edge) hold zeros: whole rows above /
   // below it and the columns left / right of it -- enumerated directly (the border is a few
@@ -143,7 +200,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       const int ry = fnpx.div(pp);
       qy[u] = py0 + ry;
       qx[u] = px0 + (pp - ry * npx);
-      const size_t o = ((size_t)qy[u] * a.in_pW + qx[u]) * Cs + qc[u];
+      const size_t o = ((size_t)qy[u] * G::in_pW(a) + qx[u]) * Cs + qc[u];
       raw[u] = *reinterpret_cast<const uint4*>(xbase + o);
       cwd[u] = *reinterpret_cast<const uint2*>(cbase + o);
     }
@@ -176,7 +233,14 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   // cover the halo loads, so the two global round trips overlap instead of running back to
   // back.  (Halo loads issued BEFORE the weights' were measured 3 us slower: the weights'
   // stores then wait behind them.)  dbg 32: the two-phase form (A/B, exact).
-  const bool onebatch = dbg_stage && pooled_in && pin && !(dbg & (8 | 32)) && nq <= 256 * UQ && nw <= 8 * 256;
+  // (fixed geometry: G::onebatch() has checked pin and the nq bound for every block of the
+  // layer, so the choice -- and with it the one WU and the kfast / table choice -- is made when
+  // the body is compiled)
+  const bool onebatch = G::fixed ? dbg_stage && pooled_in && !(dbg & (8 | 32)) && G::onebatch() && nw <= 8 * 256
+                                 : dbg_stage && pooled_in && pin && !(dbg & (8 | 32)) && nq <= 256 * UQ && nw <= 8 * 256;
+  // the table's only reader is the table k loop: a body whose geometry takes the kfast loop
+  // (below) does not fill it
+  const bool skip_tab = G::fixed && !CS4 && G::kpipe(a) && (Cs & 31) == 0 && !(dbg & 2);
   if (onebatch) {
     auto fused = [&](auto wu) {
       constexpr int WU = decltype(wu)::value;
@@ -188,7 +252,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       for (int u = 0; u < WU; ++u)
         if (tid + u * 256 < nw) wstore(tid + u * 256, wv[u]);
       HALO_STAMP(1);
-      build_tab();
+      if (!skip_tab) build_tab();
       zero_border();
       pq_expand(tid);
     };
@@ -199,7 +263,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   } else {
     if (dbg_stage && !(dbg & 8)) staged_copy<8, bf16x8>(nw, tid, 256, wload, wstore);
     HALO_STAMP(1);
-    build_tab();
+    if (!skip_tab) build_tab();
     // input halo -> LDS
     if (dbg_stage) {
       if (CS4) {
@@ -208,7 +272,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
             [&](int i) {
               int c, iy, ix;
               const bool ok = coords(i, c, iy, ix);
-              return load_bf16x4_if(ok, xbase + ((size_t)iy * a.W + ix) * 4, xbase);
+              return load_bf16x4_if(ok, xbase + ((size_t)iy * G::W(a) + ix) * 4, xbase);
             },
             [&](int i, const bf16x4& v) { *reinterpret_cast<bf16x4*>(xl + (size_t)i * 4) = v; });
       } else if (pooled_in) {
@@ -239,17 +303,18 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   HALO_STAMP(3);
 
   const int wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
-  const int rows = min(R, a.Ho - oy0);
-  const int nwin = a.pool ? (rows >> 1) * a.Wp : 0;
-  const int npix = rows * a.Wo;
-  const int ntiles = a.pool ? (nwin + 3) / 4 : (npix + 15) / 16;
+  // (fixed geometry with whole blocks only: the tile count and the passes are constants)
+  const int rows = (G::fixed && G::Ho(a) % R == 0) ? R : min(R, G::Ho(a) - oy0);
+  const int nwin = G::pool(a) ? (rows >> 1) * G::Wp(a) : 0;
+  const int npix = rows * G::Wo(a);
+  const int ntiles = G::pool(a) ? (nwin + 3) / 4 : (npix + 15) / 16;
   const uint32_t step = a.st ? (uint32_t)a.st->t : 0u;
 
-  const FastDiv fwp(a.Wp > 0 ? a.Wp : 1), fwo(a.Wo);
+  const Div fwp(G::Wp(a) > 0 ? G::Wp(a) : 1), fwo(G::Wo(a));
   // per-wave epilogue scratch [16 rows][NTC*16] fp32, after the 16-B aligned halo image
   constexpr int EPW = TM * 16 * 2 * NTC * 16 / 4;   // floats per wave: TM*16 rows x LDC bf16
   float* ep = reinterpret_cast<float*>(xl + (((size_t)R_in * W_in * XP + 7) & ~(size_t)7)) + wave * EPW;
-  const size_t qbase = ((size_t)b * a.Hp + (oy0 >> 1)) * a.Wp;
+  const size_t qbase = ((size_t)b * G::Hp(a) + (oy0 >> 1)) * G::Wp(a);
   for (int tb = wave * TM; tb < ntiles; tb += 4 * TM) {
     bool rv[TM];
     const bf16* xrow[TM];
@@ -257,19 +322,19 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
     for (int t = 0; t < TM; ++t) {
       const int tile = tb + t;
       int ry, rx;
-      if (a.pool) {
+      if (G::pool(a)) {
         const int w = tile * 4 + (r >> 2);
         rv[t] = w < nwin;
         const int wi = rv[t] ? w : 0;
         const int pyl = fwp.div(wi);
         ry = 2 * pyl + ((r >> 1) & 1);
-        rx = 2 * (wi - pyl * a.Wp) + (r & 1);
+        rx = 2 * (wi - pyl * G::Wp(a)) + (r & 1);
       } else {
         const int p = tile * 16 + r;
         rv[t] = p < npix;
         const int pi = rv[t] ? p : 0;
         ry = fwo.div(pi);
-        rx = pi - ry * a.Wo;
+        rx = pi - ry * G::Wo(a);
       }
       xrow[t] = xl + ((size_t)(ry * s) * W_in + rx * s) * XP;
     }
@@ -284,14 +349,16 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
     // LDS round trip the A-fragment reads depended on -- and the loop is software-pipelined:
     // step ks + 1's A / B fragments are requested before step ks's MFMAs issue.  Rows past
     // the block read pixel 0 (finite data, never stored); same k order as the table loop.
-    const bool kfast = !CS4 && a.kpipe && (Cs & 31) == 0 && dbg_mfma;
+    const bool kfast = !CS4 && G::kpipe(a) && (Cs & 31) == 0 && dbg_mfma;
     if (kfast) {
       const int cpk = Cs >> 5;                      // k-steps per tap
       const int g8 = 8 * g;
       auto kbase = [&](int ks) -> int {
         const int tap = ks / cpk;
-        const int ky = tap / a.KW;
-        return __builtin_amdgcn_readfirstlane((ky * W_in + (tap - ky * a.KW)) * XP + (ks - tap * cpk) * 32);
+        const int ky = tap / G::KW(a);
+        const int e = (ky * W_in + (tap - ky * G::KW(a))) * XP + (ks - tap * cpk) * 32;
+        if constexpr (G::fixed) return e;            // unrolled loop: a constant per k-step
+        return __builtin_amdgcn_readfirstlane(e);
       };
       bf16x8 af[2][TM], bw[2][NTC];
       auto load_k = [&](int ks, bf16x8* av, bf16x8* bv) {
@@ -310,16 +377,24 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       };
       load_k(0, af[0], bw[0]);
       int ks = 0;
-      for (; ks + 2 <= KS; ks += 2) {
-        load_k(ks + 1, af[1], bw[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_k(af[0], bw[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks + 2 < KS) load_k(ks + 2, af[0], bw[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_k(af[1], bw[1]);
-        __builtin_amdgcn_sched_barrier(0);
+#define HALO_K_LOOP                                                \
+  for (; ks + 2 <= KS; ks += 2) {                                  \
+    load_k(ks + 1, af[1], bw[1]);                                  \
+    __builtin_amdgcn_sched_barrier(0);                             \
+    mma_k(af[0], bw[0]);                                           \
+    __builtin_amdgcn_sched_barrier(0);                             \
+    if (ks + 2 < KS) load_k(ks + 2, af[0], bw[0]);                 \
+    __builtin_amdgcn_sched_barrier(0);                             \
+    mma_k(af[1], bw[1]);                                           \
+    __builtin_amdgcn_sched_barrier(0);                             \
+  }
+      if constexpr (G::fixed) {   // constant bound: fully unrolled, the same steps in the same order
+#pragma unroll
+        HALO_K_LOOP
+      } else {
+        HALO_K_LOOP
       }
+#undef HALO_K_LOOP
       if (ks < KS) mma_k(af[0], bw[0]);
     }
     for (int kc = 0; kc < ((dbg_mfma && !kfast) ? KS : 0); kc += KCH) {
@@ -376,11 +451,13 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
     // epilogue stages all TM tiles of the pass first (final bf16 values + pool codes), so
     // one copy loop writes TM*16 pixels / TM*4 windows with all lanes busy.
     const int LDC = NTC * 16;
-    const int csh = (mode == 1 ? a.bt.pCs : a.Cs_out) - nt0 * 16;   // channels this WG owns
-    const int C = csh < LDC ? csh : LDC;
+    const int csh = (mode == 1 ? G::pCs(a.bt) : G::Cs_out(a)) - nt0 * 16;   // channels this WG owns
+    // (fixed geometry whose n-tiles all lie inside the channel stride: every workgroup owns LDC)
+    const bool whole = G::fixed && mode == 1 && G::NT(a) % NTC == 0 && G::NT(a) * 16 <= G::pCs(a.bt);
+    const int C = whole ? LDC : (csh < LDC ? csh : LDC);
     const int cch = C >> 3;                                            // 8-channel chunks
-    const FastDiv fcch(cch > 0 ? cch : 1);
-    if (mode == 0 && a.pool) {
+    const Div fcch(cch > 0 ? cch : 1);
+    if (mode == 0 && G::pool(a)) {
       bf16* epb = reinterpret_cast<bf16*>(ep);                // [TM*4 windows][LDC]
       uint8_t* epc = reinterpret_cast<uint8_t*>(epb + TM * 4 * LDC);
 #pragma unroll
@@ -412,7 +489,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       const int nw = max(0, min(TM * 4, nwin - tb * 4));
       for (int c = lane; c < nw * cch; c += 64) {
         const int win = fcch.div(c), c8 = c - win * cch;
-        const size_t o = (qbase + tb * 4 + win) * a.Cs_out + nt0 * 16 + c8 * 8;
+        const size_t o = (qbase + tb * 4 + win) * G::Cs_out(a) + nt0 * 16 + c8 * 8;
         *reinterpret_cast<uint4*>(a.out + o) = *reinterpret_cast<const uint4*>(epb + win * LDC + c8 * 8);
         *reinterpret_cast<uint2*>(a.code + o) = *reinterpret_cast<const uint2*>(epc + win * LDC + c8 * 8);
       }
@@ -426,7 +503,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       const bool fwd = mode == 0;
       constexpr int CHM = NTC * 2 - 1;                        // chunk-index mask (LDC / 8 - 1)
       // the block is whole output rows: pixel p of the block is output pixel mrow0 + p
-      const size_t mrow0 = ((size_t)b * a.Ho + oy0) * a.Wo;
+      const size_t mrow0 = ((size_t)b * G::Ho(a) + oy0) * G::Wo(a);
       float bvn[NTC];
 #pragma unroll
       for (int nt = 0; nt < NTC; ++nt) {
@@ -470,12 +547,12 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
         const size_t m = mrow0 + (size_t)(tb * 16 + pr);
         const bf16x8 val = *reinterpret_cast<const bf16x8*>(epb + pr * LDC + ((c8 ^ (((pr >> 2) << 1) & CHM)) << 3));
         if (fwd) {
-          *reinterpret_cast<bf16x8*>(a.out + m * a.Cs_out + nt0 * 16 + c8 * 8) = val;
+          *reinterpret_cast<bf16x8*>(a.out + m * G::Cs_out(a) + nt0 * 16 + c8 * 8) = val;
         } else {
           float v[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) v[k] = bf2f(val[k]);
-          bwd_through_store8(a.bt, m, nt0 * 16 + c8 * 8, v, step);
+          bwd_through_store8<G>(a.bt, m, nt0 * 16 + c8 * 8, v, step);
         }
       }
       __builtin_amdgcn_wave_barrier();

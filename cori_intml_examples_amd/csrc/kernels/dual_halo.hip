@@ -67,6 +67,20 @@ int dual_halo_variant(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT
   return dual_sig_variant(ntc, wa, MT, NTT, dual_pick_tm(ca, ntc), xp);
 }
 
+// A launch that takes signature instance v (dual_sig_variant) runs the instance whose dgrad
+// geometry is fixed too (dual_halo_fix_body.h): ca.spec is set and the dgrad args are, field
+// by field, that signature's dgrad at its TM.
+static bool dual_fix_variant(const ConvMMArgs& ca, int ntc, int v, int tm) {
+  return v && ca.spec && dgrad_sig_matches(ca, ntc, tm, v);
+}
+
+// The host's query of that choice (false also for every launch launch_dual_halo declines or
+// serves with another kernel); the arguments of dual_halo_variant.
+bool dual_halo_dgrad_fixed(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp,
+                           bool extras) {
+  return dual_fix_variant(ca, ntc, dual_halo_variant(ca, ntc, wa, MT, NTT, xp, extras), dual_pick_tm(ca, ntc));
+}
+
 // Returns false (nothing launched) when the pair is not a supported combination; the caller
 // then launches the two kernels separately.
 bool launch_dual_halo(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, int splits,
@@ -86,7 +100,8 @@ bool launch_dual_halo(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT
   const int tm = dual_pick_tm(ca, ntc);
   // a layer-signature instance (wgrad geometry fixed at compile time) where one matches
   if (const int v = dual_sig_variant(ntc, wa, MT, NTT, tm, x.n_r && x.xp.on)) {
-    wgrad_sig_at(v).dual[tm == 4 ? 2 : tm - 1](ca, wa, wg, cgx, cgy, lds, x, s);
+    const WgradSig& sg = wgrad_sig_at(v);
+    (dual_fix_variant(ca, ntc, v, tm) ? sg.fix : sg.dual[tm == 4 ? 2 : tm - 1])(ca, wa, wg, cgx, cgy, lds, x, s);
     return true;
   }
   switch (ntc) {

@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "args.h"
 
 // the fixed values: the geometry fields (WG_GEO_INTS, args.h) and the launch's tile counts
@@ -33,7 +35,44 @@ WG_SIG(WgSigRpv3, 16, 16, 32, 16, 16, 1, 18, 4, 64, 8, 8, true, 8, 48, 18, 80, 9
 WG_SIG(WgSigMnist1, 28, 28, 4, 26, 26, 0, 3, 2, 32, 0, 0, false, 8, 4, 42, 48, 3, 2);
 WG_SIG(WgSigMnist2, 26, 26, 32, 24, 24, 0, 18, 4, 64, 12, 12, true, 5, 48, 26, 80, 9, 4);
 
+// Dgrad signatures: the co-scheduled dgrad (conv_halo_body.h in mode 1) of the SAME layer as a
+// wgrad signature, as executor_hip._dgrad_args and hip_geometry._halo_cfg produce it at default
+// tunes for every batch >= 128 (scripts/plan_dump.py at B = 128 and 256): the conv over the pooled
+// dY with the flipped taps, written through the previous stage's ReLU.  R (rows per block) and TM
+// (m-tiles per wave per pass, dual_pick_tm's choice for R) are part of the signature.
+#define DG_SIG(NAME, WG_, H_, W_, CS_, HO_, WO_, PAD_, KS_, NT_, R_, PH_, PW_, XPIX_, PC_, TM_)                     \
+  struct NAME {                                                                                                    \
+    using Wg = WG_;                                                                                                \
+    static constexpr int H = H_, W = W_, Cs_in = CS_, Ho = HO_, Wo = WO_, KH = 3, KW = 3, stride = 1, pad_t = PAD_, \
+                         pad_l = PAD_, in_dil = 1, KS = KS_, NT = NT_, pool = 0, Hp = 0, Wp = 0, Cs_out = 0, R = R_, \
+                         in_pH = PH_, in_pW = PW_, xpix = XPIX_, kpipe = 1, pCs = PC_, pC = PC_, prev_relu = 1,     \
+                         wt = 1, TM = TM_;                                                                         \
+    static constexpr bool pooled = true;                                                                           \
+  }
+//      name         wgrad sig    H   W   Cs  Ho  Wo  pad KS  NT R   pH  pW  xpix pC  TM
+DG_SIG(DgSigRpv2, WgSigRpv2, 32, 32, 32, 32, 32, 1, 9, 1, 16, 16, 16, 48, 16, 4);
+DG_SIG(DgSigRpv3, WgSigRpv3, 16, 16, 64, 16, 16, 1, 18, 2, 16, 8, 8, 80, 32, 4);
+DG_SIG(DgSigMnist2, WgSigMnist2, 24, 24, 64, 26, 26, 2, 18, 2, 13, 12, 12, 0, 32, 2);
+
 // ------------------------------------------------------------------------------ host side
+struct DgSigVals {
+#define F(n) int n;
+  CV_GEO_INTS(F)
+  CV_BT_INTS(F)
+#undef F
+  int pooled, TM;            // TM 0: the wgrad signature has no fixed dgrad
+};
+
+template <class S>
+constexpr DgSigVals dg_sig_vals() {
+  return DgSigVals{
+#define F(n) S::n,
+      CV_GEO_INTS(F) CV_BT_INTS(F)
+#undef F
+          S::pooled ? 1 : 0,
+      S::TM};
+}
+
 struct WgSigVals {
 #define F(n) int n;
   WG_SIG_INTS(F)
@@ -65,13 +104,21 @@ DUAL_SIG_DECL(dual_sig_rpv3_tm1);
 DUAL_SIG_DECL(dual_sig_rpv3_tm4);
 DUAL_SIG_DECL(dual_sig_mnist2_tm1);
 DUAL_SIG_DECL(dual_sig_mnist2_tm2);
+// ... and with the dgrad half's geometry fixed too (dual_halo_fix_body.h, dual_fix_*.hip)
+DUAL_SIG_DECL(dual_fix_rpv2_tm4);
+DUAL_SIG_DECL(dual_fix_rpv3_tm4);
+DUAL_SIG_DECL(dual_fix_mnist2_tm2);
 
 struct WgradSig {
   WgSigVals v;
   WgSigLaunch alone;          // standalone wgrad launch (null: none instantiated)
   DualSigLaunch dual[3];      // dual launch (NTC 1) at dgrad TM 1 / 2 / 4 (null: none)
+  DgSigVals dg;               // the layer's dgrad signature (dg.TM 0: none) ...
+  DualSigLaunch fix;          // ... and the dual launch with both halves fixed (NTC 1, TM dg.TM)
 };
 
 // 1 + index of the signature these args match (0: none), and the table entry
 int wgrad_sig_find(const WgradArgs& a, int MT, int NTT);
 const WgradSig& wgrad_sig_at(int v);
+// the dgrad args (NTC ntc, TM tm) are, field by field, signature v's dgrad and it has an instance
+bool dgrad_sig_matches(const ConvMMArgs& a, int ntc, int tm, int v);

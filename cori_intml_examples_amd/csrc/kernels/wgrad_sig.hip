@@ -19,12 +19,18 @@ static void wgrad_sig_launch(const WgradArgs& a, dim3 grid, size_t lds, bool pip
 }
 
 static const WgradSig kWgradSigs[] = {
-    {wg_sig_vals<WgSigRpv1>(), wgrad_sig_launch<WgSigRpv1>, {nullptr, nullptr, nullptr}},
-    {wg_sig_vals<WgSigRpv2>(), nullptr, {dual_sig_rpv2_tm1, nullptr, dual_sig_rpv2_tm4}},
-    {wg_sig_vals<WgSigRpv3>(), nullptr, {dual_sig_rpv3_tm1, nullptr, dual_sig_rpv3_tm4}},
-    {wg_sig_vals<WgSigMnist1>(), wgrad_sig_launch<WgSigMnist1>, {nullptr, nullptr, nullptr}},
-    {wg_sig_vals<WgSigMnist2>(), nullptr, {dual_sig_mnist2_tm1, dual_sig_mnist2_tm2, nullptr}},
+    {wg_sig_vals<WgSigRpv1>(), wgrad_sig_launch<WgSigRpv1>, {nullptr, nullptr, nullptr}, {}, nullptr},
+    {wg_sig_vals<WgSigRpv2>(), nullptr, {dual_sig_rpv2_tm1, nullptr, dual_sig_rpv2_tm4},
+     dg_sig_vals<DgSigRpv2>(), dual_fix_rpv2_tm4},
+    {wg_sig_vals<WgSigRpv3>(), nullptr, {dual_sig_rpv3_tm1, nullptr, dual_sig_rpv3_tm4},
+     dg_sig_vals<DgSigRpv3>(), dual_fix_rpv3_tm4},
+    {wg_sig_vals<WgSigMnist1>(), wgrad_sig_launch<WgSigMnist1>, {nullptr, nullptr, nullptr}, {}, nullptr},
+    {wg_sig_vals<WgSigMnist2>(), nullptr, {dual_sig_mnist2_tm1, dual_sig_mnist2_tm2, nullptr},
+     dg_sig_vals<DgSigMnist2>(), dual_fix_mnist2_tm2},
 };
+static_assert(std::is_same<DgSigRpv2::Wg, WgSigRpv2>::value && std::is_same<DgSigRpv3::Wg, WgSigRpv3>::value &&
+                  std::is_same<DgSigMnist2::Wg, WgSigMnist2>::value,
+              "a table row pairs a wgrad signature with its own layer's dgrad");
 
 // field by field over WG_GEO_INTS (an unpooled dY never reads dHp / dWp: not compared then)
 static bool wg_sig_matches(const WgradArgs& a, int MT, int NTT, const WgSigVals& v) {
@@ -50,3 +56,20 @@ int wgrad_sig_find(const WgradArgs& a, int MT, int NTT) {
 }
 
 const WgradSig& wgrad_sig_at(int v) { return kWgradSigs[v - 1]; }
+
+// field by field over CV_GEO_INTS (ConvMMArgs) and CV_BT_INTS (its BwdThrough); the fixed dual
+// is built for one n-tile per workgroup, the backward-through epilogue and a pooled dY
+bool dgrad_sig_matches(const ConvMMArgs& a, int ntc, int tm, int v) {
+  const DgSigVals& d = kWgradSigs[v - 1].dg;
+  if (!kWgradSigs[v - 1].fix || !d.TM || tm != d.TM || ntc != 1 || a.mode != 1) return false;
+  if ((a.in_code != nullptr) != (d.pooled != 0)) return false;
+#define F(n) \
+  if (a.n != d.n) return false;
+  CV_GEO_INTS(F)
+#undef F
+#define F(n) \
+  if (a.bt.n != d.n) return false;
+  CV_BT_INTS(F)
+#undef F
+  return true;
+}

@@ -311,6 +311,11 @@ class GeometryMixin:
         W_in = (Wo - 1) * a.stride + a.KW
         step = 2 if pool else 1
         a.kpipe = int(tune("conv_kpipe"))
+        if dual:
+            # the dual instance with the dgrad geometry fixed at compile time too
+            # (csrc/kernels/dual_halo_fix_body.h) where its signature matches; dgrad_spec=0: the
+            # dual launch without it (A/B, bit-identity tests).  Host-only: launch_dual_halo reads it.
+            a.spec = int(tune("dgrad_spec"))
         gy = cdiv(NT, ntc)
 
         def rows(XP):

@@ -120,6 +120,9 @@ KNOBS: Tuple[Knob, ...] = (
          "(profiles/r2_v12_wgrad_split_sweep.txt)", per_layer=LAYER, auto=True),
     Knob("wgrad_spec", 1, EXACT, "layer-signature halo wgrad instances (csrc/kernels/wgrad_sig.h) where "
          "one matches; 0: always the generic kernels (tests/test_wgrad_sig.py)"),
+    Knob("dgrad_spec", 1, EXACT, "dual launches whose co-scheduled dgrad geometry is fixed at compile time "
+         "too (csrc/kernels/dual_halo_fix_body.h) where the dgrad signature matches; 0: the dual launch "
+         "as without it (tests/test_dgrad_sig.py)"),
     # ---------------------------------------------------------------- dense
     Knob("dense_big_wgs", 256, PATH, "workgroups wanted for a large dense layer's forward (one per CU)"),
     Knob("dense_big_minks", 8, PATH, "fewest k-steps per split of a large dense layer's forward"),
