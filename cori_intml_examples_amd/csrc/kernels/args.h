@@ -250,6 +250,10 @@ struct ConvStackArgs {
   // spec: run a specialised (layer-signature) instance when one matches (conv_stack_variant);
   // 0 = always the generic kernel (A/B and the bit-identity tests)
   int spec = 1;
+  // fix: run the instance with the whole geometry fixed at compile time (stack_sig.h,
+  // conv_stack_fix.hip) where the args equal its signature and would otherwise take the 16-wave
+  // specialised instance (conv_stack_fixed); 0 = what spec alone selects (A/B, bit-identity tests)
+  int fix = 1;
 };
 
 // Weight gradient: dW[k][n] = sum_pixels im2col(x)[p][k] * dY[p][n]  (split over pixels)

@@ -79,6 +79,9 @@ class GeometryMixin:
         # 1 = 12-wave instances, 2 (default: +0.4 %, profiles/r5e_ab.txt) = a 16-wave instance first
         # where one exists, 0 = generic
         a.spec = int(tune("stack_spec"))
+        # ... and the whole geometry fixed at compile time where the args equal the signature
+        # (conv_stack_fix.hip; the launcher decides, K.conv_stack_fixed is the same decision)
+        a.fix = int(tune("stack_fix"))
         a.set_buf_offsets(off_b0, off_b1)
         a.splits = splits
         for l in range(n):

@@ -60,6 +60,9 @@ KNOBS: Tuple[Knob, ...] = (
     Knob("stack_spec", 2, EXACT, "layer-signature-specialised conv stack instance (conv_stack.hip "
          "kStackSigs): 0 generic, 1 12-wave instances, 2 a 16-wave instance first where one exists "
          "(+0.4 %, profiles/r5e_ab.txt)"),
+    Knob("stack_fix", 1, EXACT, "the conv stack instance with the whole geometry fixed at compile time "
+         "(stack_sig.h: the RPV stack at two row bands) where the plan's args equal its signature; 0: what "
+         "stack_spec selects (profiles/stack_fix_ab.txt; tests/test_stack_fix.py)"),
     Knob("wt", 7, EXACT, "write-through (16-byte sc1) stores, bit mask: 1 stage outputs / argmax codes, "
          "2 backward gradients dP / dH, 4 wgrad slabs (profiles/r4b_ab_rpv.txt; "
          "test_write_through_stores_bit_identical)"),
