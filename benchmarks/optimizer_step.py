@@ -2,6 +2,7 @@
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
                                         [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
+                                        [--pool avg] [--global-pool avg|max]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -27,7 +28,15 @@ those is the cost of the activation launches; the difference between ``<name>`` 
 
 ``--batch-norm`` adds ``<name>/perlayer`` likewise and ``<name>/bn`` (a BatchNormalization between
 every hidden Conv2D / Dense and its relu: that structure plus ``bn_stats``, ``bn_apply_fwd``,
-``bn_bwd_reduce`` and ``bn_bwd_apply`` per hidden stage, whose conv kernels run un-pooled)."""
+``bn_bwd_reduce`` and ``bn_bwd_apply`` per hidden stage, whose conv kernels run un-pooled).
+
+``--pool avg`` adds ``<name>/unstacked`` (the relu model built under ``INTML_TUNE=conv_stack=0``: the
+per-layer conv structure an average-pooled or globally pooled model takes, the head still running the
+last dense's epilogue) and ``<name>/pool-avg`` (AveragePooling2D in every conv block: that structure
+plus ``pool_fwd`` and ``pool_bwd`` per conv stage, whose conv kernels run un-pooled);
+``--global-pool avg|max`` adds ``<name>/unstacked`` likewise and ``<name>/gpool-<kind>`` (a global
+pooling layer in the Flatten's place: ``gpool_fwd`` and ``gpool_bwd``, and a Dense(128) over 64
+inputs instead of 4096)."""
 import argparse
 import json
 import os
@@ -49,15 +58,17 @@ REPLAY = 32
 
 UNFUSED = "fuse_optim=0,early_reduce=0"
 PERLAYER = "conv_stack=0,fuse_head=0"
+UNSTACKED = "conv_stack=0"
 
 
 def make_opt(name, **kw):
     return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
 
 
-def variants(names, clipnorm, l2=None, activations=(), batch_norm=False):
+def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
-    hidden activation -- or "relu+bn": relu behind a BatchNormalization)]"""
+    hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
+    "relu+gpool=<kind>": relu with that builder keyword)]"""
     out = []
     for nm in names:
         out.append((nm, nm, {}, None, 0.0, "relu"))
@@ -69,6 +80,12 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False):
             out.append((nm + "/l2", nm, {}, None, l2, "relu"))
         if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
+        if pool != "max" or global_pool:
+            out.append((nm + "/unstacked", nm, {}, UNSTACKED, 0.0, "relu"))
+        if pool != "max":
+            out.append((nm + "/pool-" + pool, nm, {}, None, 0.0, "relu+pool=" + pool))
+        if global_pool:
+            out.append((nm + "/gpool-" + global_pool, nm, {}, None, 0.0, "relu+gpool=" + global_pool))
         if batch_norm:
             out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
@@ -105,8 +122,12 @@ def main():
     ap.add_argument("--l2", type=float, default=None)
     ap.add_argument("--activation", default="", help="comma-separated hidden activations to time")
     ap.add_argument("--batch-norm", action="store_true", help="time the model with BatchNormalization layers")
+    ap.add_argument("--pool", choices=["max", "avg"], default="max", help="time the model with AveragePooling2D layers")
+    ap.add_argument("--global-pool", choices=["avg", "max"], default=None,
+                    help="time the model with a global pooling layer in the Flatten's place")
     a = ap.parse_args()
-    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n], a.batch_norm)
+    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n], a.batch_norm,
+                   a.pool, a.global_pool)
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -120,7 +141,9 @@ def main():
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
                             optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
                             **({"batch_norm": True} if act == "relu+bn" else {}),
-                            **({"activation": act} if act not in ("relu", "relu+bn") else {}))
+                            **({"pool": act.split("=")[1]} if act.startswith("relu+pool=") else {}),
+                            **({"global_pool": act.split("=")[1]} if act.startswith("relu+gpool=") else {}),
+                            **({"activation": act} if not act.startswith("relu") else {}))
         ex = m._executor
         d = ex.upload(x, y)
         perm = torch.arange(d.n, device=ex.device)

@@ -8,5 +8,6 @@ random / genetic / grid hyper-parameter search with live monitoring widgets.
 __version__ = "0.1.0"
 
 from . import activations, models, optim, regularizers, train, utils  # noqa: F401
-from .models import (ELU, Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, Input,  # noqa: F401
-                     LeakyReLU, MaxPooling2D, Model, Sequential, load_model)
+from .models import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout,  # noqa: F401
+                     Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, Input, LeakyReLU, MaxPooling2D, Model,
+                     Sequential, load_model)

@@ -41,16 +41,19 @@ def load_dataset(path: str, n_train: int = N_TRAIN, n_valid: int = N_VALID, n_te
 
 
 def build_model(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam",
-                lr=0.001, use_horovod=False, device=None, l2=0.0, activation="relu", batch_norm=False):
+                lr=0.001, use_horovod=False, device=None, l2=0.0, activation="relu", batch_norm=False, pool="max",
+                global_pool=None):
     """Functional CNN ``'RPVClassifier'`` (``rpv.py:38-71``): ``[Conv3x3 same+ReLU,
     MaxPool2]`` per conv size, Dropout, Flatten, ``[Dense+ReLU, Dropout]`` per fc size,
     Dense(1, sigmoid); BCE + accuracy; optimizer by name with ``lr``, Horovod-wrapped
     when ``use_horovod``.  ``l2`` > 0: an l2 kernel regularizer on every Conv2D / Dense.
     ``activation``: the hidden activation of every Conv2D / Dense instead of ReLU.
-    ``batch_norm``: a BatchNormalization between every hidden Conv2D / Dense and its activation."""
+    ``batch_norm``: a BatchNormalization between every hidden Conv2D / Dense and its activation.
+    ``pool``: "max" | "avg", the 2x2 pooling layers.  ``global_pool``: None | "avg" | "max", a global
+    pooling layer in the Flatten's place."""
     return rpv_cnn(tuple(input_shape), conv_sizes=list(conv_sizes), fc_sizes=list(fc_sizes), dropout=dropout,
                    optimizer=optimizer, lr=lr, use_horovod=use_horovod, device=device, l2=l2,
-                   activation=activation, batch_norm=batch_norm)
+                   activation=activation, batch_norm=batch_norm, pool=pool, global_pool=global_pool)
 
 
 def train_model(model, train_input, train_labels, valid_input, valid_labels, batch_size, n_epochs,

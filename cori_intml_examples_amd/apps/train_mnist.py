@@ -26,6 +26,9 @@ def build_parser():
                         "softplus, softsign")
     p.add_argument("--batch-norm", action="store_true",
                    help="a BatchNormalization between every hidden Conv2D / Dense and its activation")
+    p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
+    p.add_argument("--global-pool", choices=["avg", "max"], default=None,
+                   help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--valid-frac", type=float, default=0.17)
@@ -45,7 +48,8 @@ def main(argv=None):
     x, y = x[:a.n_train], y[:a.n_train]
     model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout,
                       optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
-                      use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm)
+                      use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm,
+                      pool=a.pool, global_pool=a.global_pool)
     cbs = []
     if hvd.size() > 1:
         cbs = [hvd.callbacks.BroadcastGlobalVariablesCallback(0), hvd.callbacks.MetricAverageCallback()]

@@ -46,6 +46,9 @@ def build_parser():
                         "softplus, softsign")
     p.add_argument("--batch-norm", action="store_true",
                    help="a BatchNormalization between every hidden Conv2D / Dense and its activation")
+    p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
+    p.add_argument("--global-pool", choices=["avg", "max"], default=None,
+                   help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--n-epochs", type=int, default=4)
     p.add_argument("--fom", choices=["best", "last"])
@@ -94,7 +97,7 @@ def main(argv=None):
                         dropout=args.dropout,
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
                         use_horovod=True, l2=args.l2, activation=args.activation,
-                        batch_norm=args.batch_norm)
+                        batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool)
     if hvd.rank() == 0:
         model.summary()
 

@@ -8,8 +8,8 @@
 """
 from __future__ import annotations
 
-from ..models import (Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, Input, MaxPooling2D, Model,
-                      Sequential)
+from ..models import (Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
+                      GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, Sequential)
 from .. import optim as optimizers
 from .. import regularizers
 
@@ -26,6 +26,21 @@ def _hidden(layer_cls, *args, activation="relu", batch_norm=False, **kw):
     if not batch_norm:
         return [layer_cls(*args, activation=activation, **kw)]
     return [layer_cls(*args, **kw), BatchNormalization(), Activation(activation)]
+
+
+def _pool(pool):
+    """The builders' ``pool=``: the 2x2 pooling layer of a conv block, "max" (the reference's) | "avg"."""
+    if pool not in ("max", "avg"):
+        raise ValueError("pool = %r (\"max\" or \"avg\")" % (pool,))
+    return (MaxPooling2D if pool == "max" else AveragePooling2D)(pool_size=(2, 2))
+
+
+def _bridge(global_pool):
+    """The builders' ``global_pool=``: the layer between the conv part and the dense part, Flatten
+    (None, the reference's) | GlobalAveragePooling2D ("avg") | GlobalMaxPooling2D ("max")."""
+    if global_pool not in (None, "avg", "max"):
+        raise ValueError("global_pool = %r (None, \"avg\" or \"max\")" % (global_pool,))
+    return {None: Flatten, "avg": GlobalAveragePooling2D, "max": GlobalMaxPooling2D}[global_pool]()
 
 
 def _chain(h, layers):
@@ -58,18 +73,20 @@ def _opt(optimizer, lr, use_horovod):
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
               n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu",
-              batch_norm=False, l2=0.0):
+              batch_norm=False, pool="max", global_pool=None, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
-    Activation(activation)."""
+    Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer.  ``global_pool``: None |
+    "avg" | "max", a global pooling layer in the Flatten's place (behind the Dropout: the plan wants
+    the conv stage's dropout ahead of it)."""
     reg = _kernel_l2(l2)
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     m = Sequential(device=device)
     for layer in (_hidden(Conv2D, h1, (3, 3), input_shape=input_shape, **hid) + _hidden(Conv2D, h2, (3, 3), **hid)):
         m.add(layer)
-    m.add(MaxPooling2D(pool_size=(2, 2)))
+    m.add(_pool(pool))
     m.add(Dropout(dropout))
-    m.add(Flatten())
+    m.add(_bridge(global_pool))
     for layer in _hidden(Dense, h3, **hid):
         m.add(layer)
     m.add(Dropout(dropout if dropout2 is None else dropout2))
@@ -80,19 +97,21 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
-            use_horovod=False, device=None, activation="relu", batch_norm=False, l2=0.0):
+            use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max", global_pool=None,
+            l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
-    Activation(activation)."""
+    Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer of every conv block.
+    ``global_pool``: None | "avg" | "max", a global pooling layer in the Flatten's place."""
     reg = _kernel_l2(l2)
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     inputs = Input(shape=input_shape)
     h = inputs
     for c in conv_sizes:
         h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), padding="same", **hid))
-        h = MaxPooling2D(pool_size=(2, 2))(h)
+        h = _pool(pool)(h)
     h = Dropout(dropout)(h)
-    h = Flatten()(h)
+    h = _bridge(global_pool)(h)
     for f in fc_sizes:
         h = _chain(h, _hidden(Dense, f, **hid))
         h = Dropout(dropout)(h)
@@ -103,15 +122,19 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
 
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
-                   use_horovod=False, device=None, activation="relu", batch_norm=False):
+                   use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max",
+                   global_pool=None):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
-    Activation(activation)."""
+    Activation(activation).  ``pool``: accepted for symmetry with the other builders (this model's
+    convs are strided, it has no 2x2 pooling layer).  ``global_pool``: None | "avg" | "max", a
+    global pooling layer in the Flatten's place: "avg" removes the 65,536-row Dense kernel."""
+    _pool(pool)
     hid = dict(activation=activation, batch_norm=batch_norm)
     h = inputs = Input(shape=input_shape)
     for c, st in ((h1, 1), (h2, 2), (h3, 1), (h4, 2)):
         h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), strides=st, padding="same", **hid))
-    h = Flatten()(h)
+    h = _bridge(global_pool)(h)
     h = _chain(h, _hidden(Dense, h5, **hid))
     outputs = Dense(1, activation="sigmoid")(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)

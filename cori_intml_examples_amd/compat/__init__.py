@@ -58,7 +58,7 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
     layers = _mod("keras.layers", **{k: getattr(_layers, k) for k in
                                      ("Input", "InputLayer", "Conv2D", "MaxPooling2D", "MaxPool2D", "Dropout",
                                       "Flatten", "Dense", "Activation", "LeakyReLU", "ELU", "BatchNormalization",
-                                      "Layer")
+                                      "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D", "Layer")
                                      if hasattr(_layers, k)})
     if not hasattr(layers, "MaxPool2D"):
         layers.MaxPool2D = _layers.MaxPooling2D

@@ -632,3 +632,34 @@ struct BnArgs {
   float* slab = nullptr;           // [nchunks][2][C]: partial dgamma, partial dbeta (gamma / beta's store order)
   bf16* dz = nullptr;              // [rows][Cs]
 };
+
+// Keras AveragePooling2D 2x2 / GlobalAveragePooling2D / GlobalMaxPooling2D (pool.hip): pool_fwd
+// behind the launches that stored the stage's input x, pool_bwd behind the launch that stored the
+// gradient dp wrt the stage output.  bf16 buffers [rows][Cs], C <= Cs real channels (Cs % 8 == 0).
+//   POOL_AVG2  x [B, H, W, Cs] the stage's un-pooled stored activation -> out [B, H/2, W/2, Cs];
+//              bwd: dp [B, H/2, W/2, Cs] -> dz [B, H, W, Cs], times (lin > 0) with relu
+//   POOL_GAVG / POOL_GMAX  x [B, H, W, Cs] the feeding stage's output -> out [B, Cs] (GMAX with idx:
+//              the first maximum's flat index, int32 [B, Cs]); bwd: dp [B, Cs] -> through ``bt``, the
+//              feeding stage's BwdThrough, over its whole output grid
+#define POOL_AVG2 1
+#define POOL_GAVG 2
+#define POOL_GMAX 3
+struct PoolArgs {
+  int mode = 0;
+  const bf16* x = nullptr;
+  bf16* out = nullptr;
+  int* idx = nullptr;              // POOL_GMAX: written by a forward that has one (training), read by the backward
+  int B = 0, H = 1, W = 1;         // the INPUT grid
+  int C = 0, Cs = 0;
+  uint32_t drop_thr = 0;           // fwd only (0: no dropout)
+  float drop_scale = 1.f;
+  uint32_t seed = 0, stream_id = 0;
+  const StepState* st = nullptr;   // the dropout counter's step (null: 0)
+  float inv_n = 1.f;               // fp32(1 / (H * W)): set by the launchers
+  // backward
+  const bf16* dp = nullptr;
+  bf16* dz = nullptr;              // POOL_AVG2
+  const bf16* lin = nullptr;       // POOL_AVG2 with relu: the un-pooled stored activation (x of the forward)
+  int relu = 0;
+  BwdThrough bt;                   // POOL_GAVG / POOL_GMAX
+};

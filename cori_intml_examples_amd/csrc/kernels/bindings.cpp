@@ -67,6 +67,8 @@ int reg_blocks(const RegArgs& a);
 void reg_set_ranges(RegArgs& a, const int* lo, const int* hi, const float* l1, const float* l2, int count);
 void launch_act_fwd(const ActArgs& a, hipStream_t s);
 void launch_act_bwd(const ActArgs& a, hipStream_t s);
+void launch_pool_fwd(const PoolArgs& a, hipStream_t s);
+void launch_pool_bwd(const PoolArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
 void launch_bn_stats(const BnArgs& a, hipStream_t s);
 void launch_bn_apply_fwd(const BnArgs& a, hipStream_t s);
@@ -537,6 +539,18 @@ PYBIND11_MODULE(_kernels, m) {
   }
   m.def("act_fwd", [](const ActArgs& a, uintptr_t s) { launch_act_fwd(a, S(s)); check_last("act_fwd"); });
   m.def("act_bwd", [](const ActArgs& a, uintptr_t s) { launch_act_bwd(a, S(s)); check_last("act_bwd"); });
+  // Keras AveragePooling2D 2x2 / global average / global max pooling (pool.hip)
+  py::class_<PoolArgs>(m, "PoolArgs")
+      .def(py::init<>())
+      RW(PoolArgs, mode) PTR(PoolArgs, x) PTR(PoolArgs, out) PTR(PoolArgs, idx) RW(PoolArgs, B) RW(PoolArgs, H)
+      RW(PoolArgs, W) RW(PoolArgs, C) RW(PoolArgs, Cs) RW(PoolArgs, drop_thr) RW(PoolArgs, drop_scale)
+      RW(PoolArgs, seed) RW(PoolArgs, stream_id) PTR(PoolArgs, st) PTR(PoolArgs, dp) PTR(PoolArgs, dz)
+      PTR(PoolArgs, lin) RW(PoolArgs, relu) RW(PoolArgs, bt);
+  m.attr("POOL_AVG2") = POOL_AVG2;
+  m.attr("POOL_GAVG") = POOL_GAVG;
+  m.attr("POOL_GMAX") = POOL_GMAX;
+  m.def("pool_fwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_fwd(a, S(s)); check_last("pool_fwd"); });
+  m.def("pool_bwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_bwd(a, S(s)); check_last("pool_bwd"); });
   // Keras BatchNormalization (bn.hip): two launches per direction around a stage's linear kernels
   py::class_<BnArgs>(m, "BnArgs")
       .def(py::init<>())

@@ -13,7 +13,11 @@ boundaries"), captured once per batch size into a HIP graph and replayed:
   forward kernels -> act_fwd, and the launch that stores its gradient -> act_bwd; a stage with a
   BatchNormalization: its linear forward kernels (un-pooled) -> bn_stats -> bn_apply_fwd [-> act_fwd],
   and the launch that stores its gradient [-> act_bwd] -> bn_bwd_reduce -> bn_bwd_apply -> its wgrad /
-  dgrad in their un-pooled linear form)
+  dgrad in their un-pooled linear form; a conv stage with an AveragePooling2D: its conv kernel
+  (un-pooled, relu in it) [-> act_fwd] -> pool_fwd, and the launch that stores its pooled gradient ->
+  pool_bwd [-> act_bwd] -> its wgrad / dgrad in their un-pooled form; a global pooling layer: gpool_fwd
+  behind the last conv stage, and the launch that stores its gradient -> gpool_bwd -> the last conv
+  stage's own backward tail)
 
 Activations are bf16 NHWC with channel strides padded to 8 (input: 4); weights live in
 ONE fp32 master buffer (Keras layout) and are mirrored into bf16 fragment-major packs by
@@ -38,9 +42,9 @@ from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin
 from .plan import Plan
-from .step_program import (ConvGeo, DenseGeo, Exchange, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
-                           cdiv, check_bucket_cover, defer_after_readers, dropout_pair, splice_bucket_launches,
-                           stage_geometry, stream_program)
+from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
+                           cdiv, check_bucket_cover, defer_after_readers, dropout_pair, gpool_geometry,
+                           splice_bucket_launches, stage_geometry, stream_program)
 
 BF16 = torch.bfloat16
 # views of the optimizer-kind table (optim/optimizers.py KINDS); STANDALONE_KINDS: see
@@ -52,12 +56,14 @@ RED_CONVW, RED_BIAS, RED_FLATW = 0, 1, 2
 
 class StageBufs(NamedTuple):
     """The buffers of one hidden stage in one BatchPlan (BatchPlan.stage_bufs)."""
-    lin_out: torch.Tensor          # where the linear kernel / epilogue writes: ``out``, or a BatchNormalization's z
+    lin_out: torch.Tensor          # where the linear kernel / epilogue writes: ``out``, or a BatchNormalization's z,
+    #                                or an average-pooled stage's un-pooled activation
     out: torch.Tensor              # the stage output
     code: Optional[torch.Tensor]   # the pooling argmax codes
     dout: Optional[torch.Tensor]   # the gradient wrt the stage output: what the next stage's BwdThrough
     #                                stores and act_bwd scales (training)
-    dz: Optional[torch.Tensor]     # what the stage's own wgrad and dgrad read: ``dout``, or bn_bwd_apply's dz
+    dz: Optional[torch.Tensor]     # what the stage's own wgrad and dgrad read: ``dout``, or bn_bwd_apply's /
+    #                                pool_bwd's un-pooled dz
 
 
 class HipExecutor(Executor):
@@ -142,10 +148,12 @@ class HipExecutor(Executor):
     def _build_geometry(self):
         inp, self.convs, self.denses, self.head_src, self.head_act = stage_geometry(self.plan)
         self.in_C, self.in_Cs, self.in_H, self.in_W = inp.C, inp.Cs, inp.H, inp.W
+        # the global pooling stage behind the last conv stage (None: the model has none)
+        self.gpool = gpool_geometry(self.plan, self.convs[-1].out_src) if self.convs else None
 
     def stage_of(self, src: Src):
         """The hidden stage whose output ``src`` describes (None: the model input)."""
-        return {"input": [None], "conv": self.convs, "dense": self.denses}[src.kind][src.idx]
+        return {"input": [None], "conv": self.convs, "dense": self.denses, "gpool": [self.gpool]}[src.kind][src.idx]
 
     def _build_packs(self):
         K = self.K
@@ -514,7 +522,16 @@ class BatchPlan(GeometryMixin):
         # slabs and the BnArgs.  Such a stage's conv_dy / dense_dh is dz: un-pooled, what its wgrad
         # and dgrad read as the dY of a linear stage.  Read through stage_bufs
         self.bn: Dict[Tuple[str, int], SimpleNamespace] = {}
+        # average-pooled conv stages: index -> lin (the un-pooled activation the conv kernel and
+        # act_fwd store), dp (the pooled gradient the next stage's BwdThrough stores); conv_out is
+        # the pooled output and conv_dy the un-pooled dz of pool_bwd.  The global pooling stage: its
+        # output, its gradient and GlobalMaxPooling2D's first-maximum indices
+        self.avg: Dict[int, SimpleNamespace] = {}
+        self.gp = None
         for g in ex.convs:
+            if g.avg:
+                self.avg[g.i] = SimpleNamespace(lin=z(bs, g.Ho, g.Wo, g.Cs_out),
+                                                dp=z(bs, g.Hp, g.Wp, g.Cs_out) if self.training else None)
             self.conv_out.append(z(bs, g.Hp, g.Wp, g.Cs_out))
             self.conv_code.append(z(bs, g.Hp, g.Wp, g.Cs_out, dt=torch.uint8) if g.pool else None)
             # gradient wrt the stage OUTPUT resolution (pooled dP for pooled convs; the
@@ -523,6 +540,11 @@ class BatchPlan(GeometryMixin):
             if g.bn is not None:
                 self.bn["conv", g.i] = self._bn_buffers(z, bs * g.Ho * g.Wo, (bs, g.Ho, g.Wo, g.Cs_out),
                                                         (bs, g.Hp, g.Wp, g.Cs_out))
+        if ex.gpool is not None:
+            g = ex.gpool
+            self.gp = SimpleNamespace(out=z(bs, g.Cs), dout=z(bs, g.Cs) if self.training else None,
+                                      idx=(z(bs, g.Cs, dt=torch.int32)
+                                           if self.training and g.mode == "max" else None))
         self.dense_out, self.dense_part, self.dense_dh = [], [], []
         self.dense_splits = []
         for g in ex.denses:
@@ -567,7 +589,12 @@ class BatchPlan(GeometryMixin):
 
     def stage_bufs(self, g) -> StageBufs:
         """Which buffer holds what for hidden stage ``g`` (a ConvGeo / DenseGeo)."""
+        if g.kind == "gpool":
+            return StageBufs(self.gp.out, self.gp.out, None, self.gp.dout, self.gp.dout)
         out, code, dz = (lst[g.idx] for lst in self._stage_lists[g.kind])
+        if g.avg:
+            av = self.avg[g.idx]
+            return StageBufs(av.lin, out, None, av.dp, dz)
         b = self.bn.get((g.kind, g.idx))
         return StageBufs(out, out, code, dz, dz) if b is None else StageBufs(b.z, out, code, b.dp, dz)
 
@@ -649,7 +676,9 @@ class BatchPlan(GeometryMixin):
         bt.prev_out = bufs.out.data_ptr()
         if bufs.code is not None:
             bt.prev_code = bufs.code.data_ptr()
-        bt.prev_relu, bt.prev_pool = int(g.relu), int(g.pool)
+        # (an average-pooled stage: no mask from the pooled output -- pool_bwd takes the relu mask
+        # from the un-pooled activation)
+        bt.prev_relu, bt.prev_pool = int(g.relu and not g.avg), int(g.pool)
         (bt.pH, bt.pW), bt.pC, bt.pCs = g.out_grid, g.C, g.Cs
         bt.cH, bt.cW = g.lin_grid
         bt.dy = bufs.dout.data_ptr()
@@ -673,7 +702,17 @@ class BatchPlan(GeometryMixin):
         Hp, Wp = g.out_grid
         a.rows, a.C, a.Cs = self.bs * Hp * Wp, g.C, g.Cs
         a.act, a.alpha = K.ACT_CODES[g.act], g.act_alpha
-        if bwd:
+        if g.avg:
+            # an average-pooled stage: A at un-pooled resolution, in place on the un-pooled activation
+            # (no dropout: pool_fwd carries it) and on dz (the saved activation is not dropout-scaled)
+            Ho, Wo = g.lin_grid
+            a.rows = self.bs * Ho * Wo
+            if bwd:
+                a.x, a.y = bufs.dz.data_ptr(), bufs.lin_out.data_ptr()
+            else:
+                a.x = bufs.lin_out.data_ptr()
+                a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
+        elif bwd:
             a.x, a.y = bufs.dout.data_ptr(), bufs.out.data_ptr()
             if g.rate > 0:       # the saved output carries the dropout scale: undo it (fp32(1 - rate))
                 a.y_scale = float(np.float32(1.0 - g.rate))
@@ -687,7 +726,7 @@ class BatchPlan(GeometryMixin):
     def _add_stage_tail_fwd(self, g):
         """Behind stage g's linear kernels, as the stage has them: bn_stats (training) ->
         bn_apply_fwd -> act_fwd (A and, unless an earlier launch carried it, the stage's dropout,
-        in place)."""
+        in place) -> pool_fwd (an average-pooled stage: the average and the stage's dropout)."""
         K = self.ex.K
         if g.bn is not None:
             a = self._bn_args(g)
@@ -697,16 +736,67 @@ class BatchPlan(GeometryMixin):
         if g.act is not None:
             fa = self._act_args(g, False)
             self._add("act_fwd_" + g.tag, lambda s, a=fa: K.act_fwd(a, s), act=fa)
+        if g.avg:
+            self.avg[g.idx].args = pa = self._pool_args(g)
+            self._add("pool_fwd_" + g.tag, lambda s, a=pa: K.pool_fwd(a, s), pool=pa)
+
+    def _pool_args(self, g):
+        """The PoolArgs of average-pooled conv stage g or of the global pooling stage: one struct for
+        the stage's forward and backward launch."""
+        ex, K, bufs = self.ex, self.ex.K, self.stage_bufs(g)
+        a = K.PoolArgs()
+        a.B, a.C, a.Cs = self.bs, g.C, g.Cs
+        if g.kind == "gpool":
+            feed = self.stage_bufs(ex.stage_of(g.src))
+            a.mode = K.POOL_GAVG if g.mode == "avg" else K.POOL_GMAX
+            a.H, a.W = g.src.H, g.src.W
+            a.x = feed.out.data_ptr()
+            if self.gp.idx is not None:
+                a.idx = self.gp.idx.data_ptr()
+        else:
+            a.mode = K.POOL_AVG2
+            a.H, a.W = g.lin_grid
+            a.x = bufs.lin_out.data_ptr()
+        a.out = bufs.out.data_ptr()
+        if self.training and g.rate > 0:
+            a.drop_thr, a.drop_scale = dropout_pair(g.rate)
+        a.seed, a.stream_id, a.st = ex.seed, g.stream, ex.state.data_ptr()
+        if self.training:
+            a.dp = bufs.dout.data_ptr()
+            if g.kind == "gpool":
+                a.bt = self._bt_for(g.src)
+            else:
+                a.dz, a.lin, a.relu = bufs.dz.data_ptr(), bufs.lin_out.data_ptr(), int(g.relu)
+        return a
+
+    def _build_gpool_fwd(self):
+        """gpool_fwd behind the last conv stage: the global pooling stage and its dropout."""
+        g, K = self.ex.gpool, self.ex.K
+        if g is None:
+            return
+        self.gp.args = pa = self._pool_args(g)
+        self._add("gpool_fwd", lambda s, a=pa: K.pool_fwd(a, s), pool=pa)
 
     def _add_stage_tail_bwd(self, g):
         """Behind the launch that stored the gradient wrt stage g's output (None: the model input)
-        through its BwdThrough (dropout mask applied, prev_relu = 0): act_bwd, the multiplication by
+        through its BwdThrough (dropout mask applied, prev_relu = 0): gpool_bwd of the global pooling
+        stage, then the tail of the conv stage that feeds it; pool_bwd of an average-pooled stage (the
+        un-pooled dz from the pooled gradient); act_bwd, the multiplication by
         A' of a stage with a hidden activation, before anything reads that gradient buffer; and for
         a stage with a BatchNormalization bn_bwd_reduce -> bn_bwd_apply (the dbeta / dgamma slabs,
         and the dense dz the stage's wgrad / dgrad read)."""
         if g is None:
             return
         K = self.ex.K
+        if g.kind == "gpool":
+            # the global stage's gradient goes through the last conv stage's BwdThrough over its
+            # whole output grid; that stage's own tail follows
+            pa = self.gp.args
+            self._add("gpool_bwd", lambda s, a=pa: K.pool_bwd(a, s), pool=pa)
+            return self._add_stage_tail_bwd(self.ex.stage_of(g.src))
+        if g.avg:
+            pa = self.avg[g.idx].args
+            self._add("pool_bwd_" + g.tag, lambda s, a=pa: K.pool_bwd(a, s), pool=pa)
         if g.act is not None:
             a = self._act_args(g, True)
             self._add("act_bwd_" + g.tag, lambda s, a=a: K.act_bwd(a, s), act=a)
@@ -720,6 +810,7 @@ class BatchPlan(GeometryMixin):
         ex = self.ex
         stack, sb = self._build_prologue()
         self._build_conv_fwd(stack)
+        self._build_gpool_fwd()
         head_epi = self._build_dense_fwd(sb)
         self._build_head(head_epi)
         if not self.training:
@@ -761,7 +852,10 @@ class BatchPlan(GeometryMixin):
         # of conv_stack=0, each such layer's linear kernel followed by its act_fwd launch)
         # (a conv stage with a BatchNormalization likewise: its linear kernel stores the un-pooled
         # pre-activation for the bn.hip launches)
-        stack = self._conv_stack_args(training) if tune("conv_stack") and all(g.plain for g in ex.convs) else None
+        # (an average-pooled stage or a global pooling layer likewise: the pool.hip launches sit
+        # between the per-layer kernels)
+        stack = (self._conv_stack_args(training)
+                 if tune("conv_stack") and all(g.plain for g in ex.convs) and ex.gpool is None else None)
         # Prologue-free step (conv stack + a hidden dense layer + optimizer-written packs): the
         # stack reads its images straight from the dataset through the cursor and permutation
         # (recording each image's dataset row for the first layer's wgrad and the head's

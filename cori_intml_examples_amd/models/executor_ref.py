@@ -10,7 +10,10 @@ hidden denses, every stage output after its dropout, the hidden denses' dH and e
 dP after their masks; for a stage with a hidden activation also its pre-activation, which the
 GPU stores between its linear kernels and the activation launch, and its gradient on both sides of
 the multiplication by A'; for a BatchNormalization stage its pre-activation z before the
-statistics, the pooled gradient buffer and dz), everything else in fp32 -- so the whole-step gradient test can use
+statistics, the pooled gradient buffer and dz; for an average-pooled stage its un-pooled activation
+before the averaging, the pooled output once, the pooled gradient and dz; the global pooling
+stage's output and gradient, the GlobalMaxPooling2D index taken on the stored values the GPU
+kernel reads), everything else in fp32 -- so the whole-step gradient test can use
 the per-kernel tests' tight tolerances instead of the loose fp32-vs-bf16 bound.
 """
 from __future__ import annotations
@@ -131,7 +134,11 @@ class RefExecutor(Executor):
                 r = R.act(cs.act, cs.act_alpha, self._q(z))
             code = None
             p = r
-            if cs.pool is not None:
+            if cs.pool_kind == "avg":
+                # Keras' order, dropout(avgpool(A(conv))): the un-pooled activation is stored, then averaged
+                r = self._q(r)
+                p = R.avgpool2x2(r)
+            elif cs.pool is not None:
                 p, code = R.maxpool2x2(r)
                 if cs.bn is not None:
                     code = R.maxpool2x2(z_code)[1]
@@ -146,6 +153,16 @@ class RefExecutor(Executor):
                 p = p * mask
             a_in, a = a, self._q(p)
             saved.append((a_in, r, code, mask, a))
+        gp = self.plan.gpool
+        if gp is not None:
+            # the global pooling stage reads the last conv stage's STORED output (so does its index)
+            p, idx = (R.global_avgpool(a), None) if gp.mode == "avg" else R.global_maxpool(a)
+            mask = None
+            if training and gp.rate > 0:
+                mask = self._mask(p.numel(), gp.rate, gp.stream, step).view(p.shape)
+                p = p * mask
+            self._gp_ctx = (tuple(a.shape[1:3]), idx, mask)
+            a = self._q(p)
         a = a.reshape(a.shape[0], -1)
         for ds in self.plan.denses:
             w = self._q(st.view(ds.dense, "kernel"))
@@ -208,7 +225,14 @@ class RefExecutor(Executor):
             if ds.dense.use_bias:
                 st.view(ds.dense, "bias", grad=True).copy_(da.sum(0))
             da = da @ self._q(st.view(ds.dense, "kernel")).t()
-        if nconv:
+        gp = self.plan.gpool
+        if gp is not None:
+            hw, idx, mask = self._gp_ctx
+            if mask is not None:
+                da = da * mask
+            da = self._q(da)                                   # the stored bf16 gradient of the global stage
+            da = R.global_avgpool_backward(da, hw) if gp.mode == "avg" else R.global_maxpool_backward(da, idx, hw)
+        elif nconv:
             cs_last = self.plan.convs[-1]
             da = da.reshape((da.shape[0],) + tuple(cs_last.out_shape))
         for i in reversed(range(nconv)):
@@ -216,18 +240,29 @@ class RefExecutor(Executor):
             a_in, r, code, mask, out = saved[i]
             if mask is not None:
                 da = da * mask
-            if self.emulate_bf16:
+            if cs.pool_kind == "avg":
+                # the stored pooled dP (dropout mask only) -> dz = 0.25 dP [* relu mask of the stored
+                # un-pooled activation], stored -> [* A' of that activation, stored]
+                da = R.avgpool2x2_backward(self._q(da), r.shape[1:3])
+                if cs.relu:
+                    da = da * (r > 0).to(da.dtype)
+                da = self._q(da)
+                if cs.act is not None:
+                    da = self._q(da * self._act_slope(cs, r, False))
+            elif self.emulate_bf16:
                 # the HIP step stores this gradient (masked by the dropout and the ReLU of
                 # the stage output, at the stage's output resolution) as bf16 before routing it
                 if cs.relu:
                     pooled = R.maxpool2x2(r)[0] if cs.pool is not None else r
                     da = da * (pooled > 0).to(da.dtype)
                 da = self._q(da)
-            if cs.act is not None:
+            if cs.pool_kind == "avg":
+                pass
+            elif cs.act is not None:
                 da = self._q(da * self._act_slope(cs, out, mask is not None))
-            if cs.pool is not None:
+            if cs.pool_kind == "max":
                 da = R.maxpool2x2_backward(da, code, r.shape[1:3])
-            if cs.relu:
+            if cs.relu and cs.pool_kind != "avg":
                 da = da * (r > 0).to(da.dtype)
             if cs.bn is not None:
                 da = self._bn_backward(cs.bn, da, self._bn_ctx[id(cs)])

@@ -299,6 +299,45 @@ class MaxPooling2D(Layer):
                    strides=cfg.get("strides"), padding=cfg.get("padding", "valid"))
 
 
+class AveragePooling2D(MaxPooling2D):
+    """``keras.layers.AveragePooling2D``, 2x2 / stride 2 / 'valid' only: takes MaxPooling2D's place in
+    a conv stage (plan.py).  A row or column an odd size leaves outside every window contributes
+    nothing and receives no gradient."""
+
+
+class _GlobalPooling2D(Layer):
+    def __init__(self, data_format=None, **kw):
+        super().__init__(**kw)
+        if data_format not in (None, "channels_last"):
+            raise NotImplementedError("only channels_last (reference forces it, mnist.py:30)")
+
+    def compute_output_shape(self, s):
+        # (a misplaced layer -- behind a Flatten or Dense -- is the plan's error, which names the layers)
+        return (s[-1],)
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg["data_format"] = "channels_last"
+        return cfg
+
+    @classmethod
+    def from_config(cls, cfg):
+        return cls(name=cfg.get("name"))
+
+
+class GlobalAveragePooling2D(_GlobalPooling2D):
+    """``keras.layers.GlobalAveragePooling2D``: the mean over H and W, (H, W, C) -> (C,); stands in
+    Flatten's place behind the last conv stage (plan.py)."""
+    mode = "avg"
+
+
+class GlobalMaxPooling2D(_GlobalPooling2D):
+    """``keras.layers.GlobalMaxPooling2D``: the maximum over H and W, (H, W, C) -> (C,).  The gradient
+    goes to the FIRST maximum in row-major (y, x) order, MaxPooling2D's rule here (TensorFlow's
+    reduce_max splits it evenly among exactly tied maxima)."""
+    mode = "max"
+
+
 class Dropout(Layer):
     def __init__(self, rate, noise_shape=None, seed=None, **kw):
         super().__init__(**kw)
@@ -507,4 +546,5 @@ def activation_of(layer):
 
 
 LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
-                                         LeakyReLU, ELU, BatchNormalization)}
+                                         LeakyReLU, ELU, BatchNormalization, AveragePooling2D,
+                                         GlobalAveragePooling2D, GlobalMaxPooling2D)}

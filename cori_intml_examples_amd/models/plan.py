@@ -19,6 +19,12 @@ A BatchNormalization directly behind a linear Conv2D / hidden Dense (``bn``) mak
 bn.hip launches normalise, activate (relu), pool and drop.  gamma may be negative, so the pool is
 never taken before BN.
 
+An AveragePooling2D in MaxPooling2D's place (``pool_kind`` 'avg') makes the stage
+``dropout(avgpool(A(conv)))``, Keras' own order: averaging does not commute with A, so the conv
+kernel (with its relu) and the activation launch run un-pooled, and the pool.hip launches average
+and drop.  A GlobalAveragePooling2D / GlobalMaxPooling2D in Flatten's place is a stage of its own
+without weights (``Plan.gpool``), with the Dropout behind it.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -27,8 +33,8 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .layers import (ELU, Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten, InputLayer, Layer, LeakyReLU,
-                     MaxPooling2D, activation_of)
+from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
+                     GlobalAveragePooling2D, GlobalMaxPooling2D, InputLayer, Layer, LeakyReLU, MaxPooling2D, activation_of)
 from ..ops.reference import conv_pads
 
 
@@ -45,6 +51,11 @@ class ConvStage:
     act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
     act_alpha: float = 0.0
     bn: Optional[BatchNormalization] = None  # dropout(maxpool(A(BN(conv)))): the pool is NOT taken before BN
+
+    @property
+    def pool_kind(self) -> Optional[str]:
+        """'max' | 'avg' | None: what ``pool`` is."""
+        return None if self.pool is None else "avg" if isinstance(self.pool, AveragePooling2D) else "max"
 
     @property
     def rate(self) -> float:
@@ -80,6 +91,25 @@ class DenseStage:
 
 
 @dataclass
+class GlobalPoolStage:
+    """GlobalAveragePooling2D / GlobalMaxPooling2D behind the last conv stage [+ Dropout]: a stage
+    of its own without weights, (H, W, C) -> (C,)."""
+    layer: Layer
+    mode: str                               # 'avg' | 'max'
+    in_shape: Tuple[int, int, int]          # H, W, C: the last conv stage's output
+    dropout: Optional[Dropout] = None
+    stream: int = 0
+    relu = False
+    act = None
+    act_alpha = 0.0
+    bn = None
+
+    @property
+    def rate(self) -> float:
+        return self.dropout.rate if self.dropout is not None else 0.0
+
+
+@dataclass
 class HeadStage:
     dense: Dense
     K: int
@@ -95,10 +125,12 @@ class Plan:
     convs: List[ConvStage] = field(default_factory=list)
     denses: List[DenseStage] = field(default_factory=list)
     head: Optional[HeadStage] = None
+    gpool: Optional[GlobalPoolStage] = None
 
     @property
     def stages(self):
-        return list(self.convs) + list(self.denses) + ([self.head] if self.head else [])
+        return (list(self.convs) + ([self.gpool] if self.gpool else []) + list(self.denses)
+                + ([self.head] if self.head else []))
 
 
 def canonical_loss(loss) -> str:
@@ -184,6 +216,9 @@ def build_plan(layers: List[Layer], loss) -> Plan:
             if name is not None:
                 open_stage = None
         elif isinstance(layer, Conv2D):
+            if plan.gpool is not None:
+                raise NotImplementedError("layer %s follows %s: Conv2D after a global pooling layer"
+                                          % (layer.name, plan.gpool.layer.name))
             if plan.denses or flat_from is not None:
                 raise NotImplementedError("Conv2D after Flatten/Dense")
             relu, act, alpha = _stage_act(layer, layer.activation, 1.0 if layer.activation == "elu" else 0.0, "conv")
@@ -193,14 +228,33 @@ def build_plan(layers: List[Layer], loss) -> Plan:
             plan.convs.append(cur_conv)
             cur_dense = None
             open_stage = (cur_conv, layer) if layer.activation is None else None
-        elif isinstance(layer, MaxPooling2D):
-            if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None:
-                raise NotImplementedError("MaxPooling2D must directly follow a Conv2D")
+        elif isinstance(layer, MaxPooling2D):       # (AveragePooling2D too)
+            if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None or plan.gpool is not None:
+                raise NotImplementedError("%s must directly follow a Conv2D" % type(layer).__name__)
+            if isinstance(layer, AveragePooling2D) and cur_conv.bn is not None:
+                raise NotImplementedError("layer %s follows %s on the stage of %s: AveragePooling2D on a "
+                                          "BatchNormalization stage is not implemented"
+                                          % (layer.name, cur_conv.bn.name, cur_conv.conv.name))
             cur_conv.pool = layer
             cur_conv.out_shape = tuple(layer.output_shape_)
+        elif isinstance(layer, (GlobalAveragePooling2D, GlobalMaxPooling2D)):
+            what = type(layer).__name__
+            if plan.gpool is not None:
+                raise NotImplementedError("layer %s follows %s: two global pooling layers"
+                                          % (layer.name, plan.gpool.layer.name))
+            if flat_from is not None or plan.denses:
+                raise NotImplementedError("layer %s follows %s: %s behind a Flatten or Dense"
+                                          % (layer.name, before.name, what))
+            if cur_conv is None:
+                raise NotImplementedError("layer %s follows %s: %s must follow the last conv stage (not the "
+                                          "model input)" % (layer.name, before.name, what))
+            plan.gpool = GlobalPoolStage(layer=layer, mode=layer.mode, in_shape=tuple(layer.input_shape))
+            cur_conv = None
         elif isinstance(layer, Dropout):
             stream += 1
             tgt = cur_dense if cur_dense is not None else cur_conv
+            if tgt is None and plan.gpool is not None and not plan.denses and plan.head is None:
+                tgt = plan.gpool
             if tgt is None:
                 raise NotImplementedError("Dropout directly on the model input")
             if tgt.dropout is not None:
@@ -208,6 +262,9 @@ def build_plan(layers: List[Layer], loss) -> Plan:
             tgt.dropout = layer
             tgt.stream = stream
         elif isinstance(layer, Flatten):
+            if plan.gpool is not None:
+                raise NotImplementedError("layer %s follows %s: Flatten behind a global pooling layer"
+                                          % (layer.name, plan.gpool.layer.name))
             if flat_from is not None or plan.denses:
                 raise NotImplementedError("Flatten after Dense")
             flat_from = tuple(layer.input_shape)

@@ -22,7 +22,7 @@ def r8(x):
 @dataclass
 class Src:
     """An activation buffer feeding the next stage (for flatten mapping / bwd-through)."""
-    kind: str            # 'input' | 'conv' | 'dense'
+    kind: str            # 'input' | 'conv' | 'dense' | 'gpool' (the global pooling stage)
     idx: int
     C: int               # logical channels (flatten mapping)
     Cs: int              # padded channel stride
@@ -46,12 +46,14 @@ class Stage:
     act: Optional[str] = None      # hidden activation other than relu / linear
     act_alpha: float = 0.0
     bn: Optional[object] = None    # the stage's BatchNormalization layer
+    avg: bool = False              # a conv stage with an AveragePooling2D: dropout(avgpool(A(conv)))
     lin_grid = out_grid = (1, 1)
 
     @classmethod
     def of(cls, st, *geo):
         """The record of plan stage ``st`` with the positional geometry ``geo``."""
-        return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn)
+        return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn,
+                   avg=getattr(st, "pool_kind", None) == "avg")
 
     @property
     def tag(self):
@@ -64,17 +66,21 @@ class Stage:
 
     @property
     def plain(self):
-        """Neither a table activation nor a BatchNormalization: the linear kernels are the whole
-        stage (the condition for the conv stack and for the head launch running the epilogue)."""
-        return self.act is None and self.bn is None
+        """Neither a table activation nor a BatchNormalization nor an average pool: the linear kernels
+        are the whole stage (the condition for the conv stack and for the head launch running the
+        epilogue)."""
+        return self.act is None and self.bn is None and not self.avg
 
     @property
     def dropout_in(self):
         """The launch that carries the stage's dropout in a training step (plan.py): the 'linear'
         kernel iff the stage is plain, bn_apply_fwd ('bn') iff it has a BatchNormalization and no
-        table activation, else act_fwd ('act'); None at rate 0."""
+        table activation, else act_fwd ('act'); pool_fwd ('pool') of an average-pooled stage and of
+        the global pooling stage; None at rate 0."""
         if not self.rate > 0:
             return None
+        if self.avg or getattr(self, "kind", None) == "gpool":
+            return "pool"
         return "linear" if self.plain else "bn" if self.act is None else "act"
 
 
@@ -115,8 +121,13 @@ class ConvGeo(Stage):
     @property
     def linear(self):
         """The form the stage's conv kernels run in: a BatchNormalization stage's forward, wgrad and
-        dgrad are those of a linear, un-pooled, dropout-free stage (the bn.hip launches do the rest)."""
-        return self if self.bn is None else replace(self, pool=False, relu=False, rate=0.0, Hp=self.Ho, Wp=self.Wo)
+        dgrad are those of a linear, un-pooled, dropout-free stage (the bn.hip launches do the rest);
+        an average-pooled stage's are un-pooled and dropout-free with the relu left in the conv kernel
+        (the pool.hip launches average, drop and route the gradient back)."""
+        if self.bn is None and not self.avg:
+            return self
+        return replace(self, pool=False, relu=self.relu and self.bn is None, rate=0.0, Hp=self.Ho, Wp=self.Wo,
+                       avg=False)
 
 
 @dataclass
@@ -136,6 +147,21 @@ class DenseGeo(Stage):
     idx, C, Cs = _alias("j"), _alias("N"), _alias("Ns")
 
 
+@dataclass
+class GPoolGeo(Stage):
+    """The global pooling stage (plan.GlobalPoolStage): no weights, ``src`` the last conv stage's
+    output -> [B, Cs]; ``mode`` 'avg' | 'max'.  rate / stream are those of the Dropout behind it."""
+    src: Src
+    mode: str
+    kind, pool, idx = "gpool", False, 0
+    C, Cs = property(lambda g: g.src.C), property(lambda g: g.src.Cs)
+
+
+def gpool_geometry(plan, src):
+    """The GPoolGeo of ``plan``'s global pooling stage fed by ``src`` (None: the plan has none)."""
+    return GPoolGeo.of(plan.gpool, src, plan.gpool.mode) if getattr(plan, "gpool", None) is not None else None
+
+
 def stage_geometry(plan):
     """(input Src, [ConvGeo], [DenseGeo], head Src, head activation code) of a models.plan.Plan."""
     shape = plan.input_shape
@@ -149,7 +175,7 @@ def stage_geometry(plan):
         pt, _, pl, _ = cs.pads
         kh, kw = cs.conv.kernel_size
         g = ConvGeo.of(cs, i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
-                       cs.pool is not None)
+                       cs.pool is not None and getattr(cs, "pool_kind", "max") == "max")
         g.KS = cdiv(kh * kw * Cs_in, 32)
         g.NT = cdiv(Cout, 16)
         if i > 0:
@@ -158,6 +184,9 @@ def stage_geometry(plan):
         convs.append(g)
         H, W, Cin, Cs_in = Hp, Wp, Cout, g.Cs_out
         src = g.out_src
+    gp = gpool_geometry(plan, src)
+    if gp is not None:
+        src = gp.out_src
     for j, ds in enumerate(plan.denses):
         g = DenseGeo.of(ds, j, src, ds.K, ds.N, r8(ds.N))
         if g.K != src.H * src.W * src.C:

@@ -94,6 +94,55 @@ def maxpool2x2_backward(dy: torch.Tensor, code: torch.Tensor, in_hw: Tuple[int, 
     return out
 
 
+def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
+    """2x2/2 valid average pool on NHWC: 0.25 * ((a + b) + (c + d)) with a b / c d the window in
+    row-major order (pool.hip's order); a leftover odd row / column contributes nothing."""
+    B, H, W, C = x.shape
+    Hp, Wp = H // 2, W // 2
+    xw = x[:, :Hp * 2, :Wp * 2, :].reshape(B, Hp, 2, Wp, 2, C)
+    return ((xw[:, :, 0, :, 0] + xw[:, :, 0, :, 1]) + (xw[:, :, 1, :, 0] + xw[:, :, 1, :, 1])) * 0.25
+
+
+def avgpool2x2_backward(dy: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Tensor:
+    """0.25 * dy at each of a window's four pixels; zero in a leftover odd row / column."""
+    B, Hp, Wp, C = dy.shape
+    out = torch.zeros(B, in_hw[0], in_hw[1], C, dtype=dy.dtype, device=dy.device)
+    out[:, :Hp * 2, :Wp * 2, :] = (dy * 0.25).repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+    return out
+
+
+def global_avgpool(x: torch.Tensor) -> torch.Tensor:
+    """Mean over H and W of NHWC: the sum times fp32(1 / (H * W))."""
+    B, H, W, C = x.shape
+    return x.reshape(B, H * W, C).sum(1) * torch.tensor(1.0 / (H * W), dtype=x.dtype)
+
+
+def global_avgpool_backward(dy: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Tensor:
+    H, W = in_hw
+    g = dy * torch.tensor(1.0 / (H * W), dtype=dy.dtype)
+    return g[:, None, None, :].expand(-1, H, W, -1).clone()
+
+
+def global_maxpool(x: torch.Tensor):
+    """Maximum over H and W of NHWC.  Returns (y, index) with index the flat y * W + x of the FIRST
+    maximum in row-major order (int64 [B, C])."""
+    B, H, W, C = x.shape
+    xf = x.reshape(B, H * W, C)
+    y = xf.max(dim=1).values
+    pos = torch.arange(H * W, device=x.device).view(1, H * W, 1)
+    idx = torch.where(xf == y.unsqueeze(1), pos, torch.full_like(pos, H * W)).min(dim=1).values
+    return y, idx
+
+
+def global_maxpool_backward(dy: torch.Tensor, idx: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Tensor:
+    """The whole gradient at the saved index, zero elsewhere."""
+    H, W = in_hw
+    B, C = dy.shape
+    out = torch.zeros(B, H * W, C, dtype=dy.dtype, device=dy.device)
+    out.scatter_(1, idx.view(B, 1, C), dy.view(B, 1, C))
+    return out.reshape(B, H, W, C)
+
+
 # --------------------------------------------------------------------------- activations
 # The hidden activations beyond relu / linear (Keras 2.2.4 keras/activations.py and the
 # LeakyReLU / ELU layers): name -> whether it takes an alpha.  Every function is non-decreasing
