@@ -3,6 +3,7 @@
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
                                         [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
+                                        [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -36,7 +37,14 @@ last dense's epilogue) and ``<name>/pool-avg`` (AveragePooling2D in every conv b
 plus ``pool_fwd`` and ``pool_bwd`` per conv stage, whose conv kernels run un-pooled);
 ``--global-pool avg|max`` adds ``<name>/unstacked`` likewise and ``<name>/gpool-<kind>`` (a global
 pooling layer in the Flatten's place: ``gpool_fwd`` and ``gpool_bwd``, and a Dense(128) over 64
-inputs instead of 4096)."""
+inputs instead of 4096).
+
+``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
+them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
+``<name>/weighted-data`` (the default model on sample-weighted data: the weighted head instances, no new
+launch) and ``<name>/metrics+weighted`` (both lists compiled in, on that data: ``roc_accum`` feeds the
+weighted set too).  ``--eval-samples N`` also times, for every model, an evaluation pass over N samples at
+the batch size (eval-step graph replays between two device events, the epoch's metric read included)."""
 import argparse
 import json
 import os
@@ -65,13 +73,21 @@ def make_opt(name, **kw):
     return optim.Adam(amsgrad=True, **kw) if name == "AMSGrad" else getattr(optim, name)(**kw)
 
 
-def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None):
+def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
+             metrics=None, weighted_metrics=None):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
-    "relu+gpool=<kind>": relu with that builder keyword)]"""
+    "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
+    metric keywords, "weighted_data": True for sample-weighted data)]"""
     out = []
     for nm in names:
         out.append((nm, nm, {}, None, 0.0, "relu"))
+        if metrics:
+            out.append((nm + "/metrics", nm, {}, None, 0.0, "relu", {"metrics": metrics}))
+        if weighted_metrics:
+            out.append((nm + "/weighted-data", nm, {}, None, 0.0, "relu", {"weighted_data": True}))
+            out.append((nm + "/metrics+weighted", nm, {}, None, 0.0, "relu",
+                        {"metrics": metrics or ["accuracy"], "weighted_metrics": weighted_metrics, "weighted_data": True}))
         if clipnorm is not None or l2:
             out.append((nm + "/unfused", nm, {}, UNFUSED, 0.0, "relu"))
         if clipnorm is not None:
@@ -125,17 +141,23 @@ def main():
     ap.add_argument("--pool", choices=["max", "avg"], default="max", help="time the model with AveragePooling2D layers")
     ap.add_argument("--global-pool", choices=["avg", "max"], default=None,
                     help="time the model with a global pooling layer in the Flatten's place")
+    ap.add_argument("--metrics", default="", help="comma-separated compile metrics to time (e.g. accuracy,auc)")
+    ap.add_argument("--weighted-metrics", default="", help="comma-separated weighted_metrics to time, on weighted data")
+    ap.add_argument("--eval-samples", type=int, default=0, help="also time an evaluation pass over this many samples")
     a = ap.parse_args()
-    var = variants(a.opts.split(","), a.clipnorm, a.l2, [n for n in a.activation.split(",") if n], a.batch_norm,
-                   a.pool, a.global_pool)
+    split = lambda t: [n for n in t.split(",") if n]
+    var = [v if len(v) == 7 else v + ({},) for v in
+           variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
+                    split(a.metrics), split(a.weighted_metrics))]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
     rs = np.random.RandomState(0)
     x = rs.rand(bs * REPLAY, 64, 64, 3).astype(np.float32)
     y = (rs.rand(bs * REPLAY) > 0.5).astype(np.float32)
-    runs = {}
-    for nm, oname, kw, tv, l2, act in var:
+    w = rs.uniform(0.5, 2.0, bs * REPLAY).astype(np.float32)
+    runs, keys = {}, {}
+    for nm, oname, kw, tv, l2, act, extra in var:
         set_random_seed(1)
         with tuned(tv):
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
@@ -143,9 +165,11 @@ def main():
                             **({"batch_norm": True} if act == "relu+bn" else {}),
                             **({"pool": act.split("=")[1]} if act.startswith("relu+pool=") else {}),
                             **({"global_pool": act.split("=")[1]} if act.startswith("relu+gpool=") else {}),
-                            **({"activation": act} if not act.startswith("relu") else {}))
+                            **({"activation": act} if not act.startswith("relu") else {}),
+                            **{k: v for k, v in extra.items() if k != "weighted_data"})
         ex = m._executor
-        d = ex.upload(x, y)
+        d = ex.upload(x, y, w) if extra.get("weighted_data") else ex.upload(x, y)
+        keys[nm] = (bs, "train", "w") if extra.get("weighted_data") else (bs, "train")
         perm = torch.arange(d.n, device=ex.device)
         runs[nm] = (m, ex, d, perm)
 
@@ -167,13 +191,40 @@ def main():
         for nm in names:
             timed(nm, 2)                # back under load after the other models' turn
             us[nm].append(timed(nm, reps))
+    ev = {}
+    if a.eval_samples:
+        # an evaluation pass: eval_samples / bs eval-step replays over the resident set, then the metric read
+        nb = max(1, a.eval_samples // bs)
+
+        def eval_pass(nm):
+            m, ex, d, _ = runs[nm]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ex.reset_metrics()
+            for b in range(nb):
+                ex.eval_step(d, (b % REPLAY) * bs, bs)
+            m._metric_values(*ex.read_metrics()[:2])
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3
+
+        ev = {nm: [] for nm in names}
+        for nm in names:
+            eval_pass(nm)
+        for _ in range(a.rounds):
+            for nm in names:
+                ev[nm].append(eval_pass(nm))
     out = {"workload": "rpv_cnn 64x64x3 [16,32,64]/[128] B=%d" % bs, "steps_per_run": reps * REPLAY, "rounds": a.rounds,
            "us_per_step_median": {nm: round(statistics.median(v), 2) for nm, v in us.items()},
            "us_per_step_runs": {nm: [round(t, 2) for t in v] for nm, v in us.items()},
-           "optim_fused": {nm: bool(runs[nm][1]._plans[(bs, "train")].optim_fused) for nm in names},
-           "launches": {nm: [it[0] for it in runs[nm][1]._plans[(bs, "train")].launches] for nm in names},
+           "optim_fused": {nm: bool(runs[nm][1]._plans[keys[nm]].optim_fused) for nm in names},
+           "launches": {nm: [it[0] for it in runs[nm][1]._plans[keys[nm]].launches] for nm in names},
            "finite": {nm: bool(np.isfinite(runs[nm][0].store.master[:runs[nm][0].store.numel].sum().item()))
                       for nm in names}}
+    if ev:
+        out["eval_samples"] = max(1, a.eval_samples // bs) * bs
+        out["eval_pass_us_median"] = {nm: round(statistics.median(v), 1) for nm, v in ev.items()}
+        out["eval_pass_us_runs"] = {nm: [round(t, 1) for t in v] for nm, v in ev.items()}
     print(json.dumps(out))
 
 

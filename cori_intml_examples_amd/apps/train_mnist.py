@@ -34,6 +34,11 @@ def build_parser():
     p.add_argument("--valid-frac", type=float, default=0.17)
     p.add_argument("--n-train", type=int, default=60000)
     p.add_argument("--fom", choices=["best", "last"], default="best")
+    p.add_argument("--metrics", default=None, help="compile metrics, comma separated: accuracy, auc")
+    p.add_argument("--weighted-metrics", default=None,
+                   help="compile weighted_metrics, comma separated")
+    p.add_argument("--fom-metric", default="val_loss",
+                   help="the logged val_ name the FoM line reports (acc and the ROC family print 1 - value)")
     p.add_argument("--verbose", type=int, default=2)
     return p
 
@@ -42,21 +47,21 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     from ..parallel import hvd
     from .mnist import load_data
-    from .zoo import clipped_optimizer, mnist_cnn
+    from .zoo import clipped_optimizer, fom_from_history, mnist_cnn, parse_metric_list
     hvd.init()
     x, y, _, _ = load_data(n_train=a.n_train)
     x, y = x[:a.n_train], y[:a.n_train]
     model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout,
                       optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
                       use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm,
-                      pool=a.pool, global_pool=a.global_pool)
+                      pool=a.pool, global_pool=a.global_pool, metrics=parse_metric_list(a.metrics),
+                      weighted_metrics=parse_metric_list(a.weighted_metrics))
     cbs = []
     if hvd.size() > 1:
         cbs = [hvd.callbacks.BroadcastGlobalVariablesCallback(0), hvd.callbacks.MetricAverageCallback()]
     h = model.fit(x, y, batch_size=a.batch_size, epochs=a.epochs, validation_split=a.valid_frac,
                   verbose=a.verbose if hvd.rank() == 0 else 0, callbacks=cbs)
-    from ..hpo.evaluator import figure_of_merit
-    print("FoM:", figure_of_merit(h.history["val_loss"], a.fom))
+    print("FoM:", fom_from_history(h.history, a.fom_metric, a.fom))
     sys.stdout.flush()
     hvd.shutdown()
     return h

@@ -10,7 +10,8 @@ One rank per GPU:
 
 Extra flags (not in the reference): ``--synthetic`` (auto-enabled when ``--input-dir``
 has no ``train.h5``: synthetic events of the RPV schema), ``--channels``, ``--seed``,
-``--verbose``, ``--use-weights`` (the per-event weights as ``sample_weight`` of the training
+``--verbose``, ``--metrics`` / ``--weighted-metrics`` (compile's lists: auc, purity, efficiency on the device),
+``--fom-metric`` (which logged ``val_`` name the FoM line reports), ``--use-weights`` (the per-event weights as ``sample_weight`` of the training
 and validation loss; default off), ``--shard`` / ``--replicate`` (data-parallel sampling: each rank reads a
 disjoint shard, or -- the reference's semantics -- the full dataset with its own shuffle).
 """
@@ -59,6 +60,11 @@ def build_parser():
     p.add_argument("--verbose", type=int, default=2)
     p.add_argument("--use-weights", action="store_true",
                    help="weight the training and validation loss by the per-event weights")
+    p.add_argument("--metrics", default=None, help="compile metrics, comma separated: accuracy, auc, purity, efficiency")
+    p.add_argument("--weighted-metrics", default=None,
+                   help="compile weighted_metrics, comma separated (needs --use-weights)")
+    p.add_argument("--fom-metric", default="val_loss",
+                   help="the logged val_ name the FoM line reports (acc and the ROC family print 1 - value)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--shard", dest="shard", action="store_true", default=None)
     g.add_argument("--replicate", dest="shard", action="store_false")
@@ -66,11 +72,14 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.weighted_metrics and not args.use_weights:
+        parser.error("--weighted-metrics needs --use-weights")
     from ..parallel import hvd
     from ..utils import set_random_seed
     from .rpv import build_model, load_dataset, train_model
-    from .zoo import clipped_optimizer
+    from .zoo import clipped_optimizer, fom_from_history, parse_metric_list
 
     st = hvd.init(shard_data=args.shard)
     print("[train_rpv] rank %d/%d (local %d) on %s, data plane %s" % (
@@ -97,7 +106,9 @@ def main(argv=None):
                         dropout=args.dropout,
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
                         use_horovod=True, l2=args.l2, activation=args.activation,
-                        batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool)
+                        batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool,
+                        metrics=parse_metric_list(args.metrics),
+                        weighted_metrics=parse_metric_list(args.weighted_metrics))
     if hvd.rank() == 0:
         model.summary()
 
@@ -110,10 +121,9 @@ def main(argv=None):
     if hvd.rank() == 0 and getattr(history, "data_plane", None):
         print("[train_rpv] gradient reducer %s" % history.data_plane)
     if args.fom in ("best", "last"):
-        from ..hpo.evaluator import figure_of_merit
         # one write per line: the ranks share the launcher's pipe, and print's separate writes
         # of "FoM:" and the value interleave across ranks
-        sys.stdout.write("FoM: %s\n" % figure_of_merit(history.history["val_loss"], args.fom))
+        sys.stdout.write("FoM: %s\n" % fom_from_history(history.history, args.fom_metric, args.fom))
         sys.stdout.flush()
     sys.stdout.flush()
 

@@ -71,10 +71,36 @@ def _opt(optimizer, lr, use_horovod):
     return opt
 
 
+def _metric_lists(metrics, weighted_metrics):
+    """compile()'s metric arguments: the builders' defaults compile what they always compiled."""
+    kw = {"metrics": ["accuracy"] if metrics is None else list(metrics)}
+    if weighted_metrics:
+        kw["weighted_metrics"] = list(weighted_metrics)
+    return kw
+
+
+def parse_metric_list(text):
+    """'a,b' of a CLI flag -> ['a', 'b'] (None / '' -> None: the builder's default)."""
+    return [t.strip() for t in text.split(",") if t.strip()] if text else None
+
+
+def fom_from_history(history, name: str, mode: str) -> float:
+    """The FoM a training CLI prints for logged name ``name`` (a ``val_`` key of the History): the
+    best or last epoch's value; for the larger-is-better names (acc and the ROC family) 1 - value,
+    so the evaluators keep minimising ("best" is then the best epoch by that metric)."""
+    from ..hpo.evaluator import figure_of_merit
+    from ..metrics import larger_is_better
+    if name not in history:
+        raise ValueError("--fom-metric %s: not a logged metric (logged: %s)" % (name, ", ".join(sorted(history))))
+    vals = [float(v) for v in history[name]]
+    return figure_of_merit([1.0 - v for v in vals] if larger_is_better(name) else vals, mode)
+
+
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
               n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu",
-              batch_norm=False, pool="max", global_pool=None, l2=0.0):
+              batch_norm=False, pool="max", global_pool=None, metrics=None, weighted_metrics=None, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer.  ``global_pool``: None |
     "avg" | "max", a global pooling layer in the Flatten's place (behind the Dropout: the plan wants
@@ -91,15 +117,15 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
         m.add(layer)
     m.add(Dropout(dropout if dropout2 is None else dropout2))
     m.add(Dense(n_classes, activation="softmax", **reg))
-    m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy",
-              metrics=["accuracy"])
+    m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy", **_metric_lists(metrics, weighted_metrics))
     return m
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
             use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max", global_pool=None,
-            l2=0.0):
+            metrics=None, weighted_metrics=None, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer of every conv block.
     ``global_pool``: None | "avg" | "max", a global pooling layer in the Flatten's place."""
@@ -117,14 +143,16 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
         h = Dropout(dropout)(h)
     outputs = Dense(1, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
-    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy",
+                  **_metric_lists(metrics, weighted_metrics))
     return model
 
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
                    use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max",
-                   global_pool=None):
+                   global_pool=None, metrics=None, weighted_metrics=None):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: accepted for symmetry with the other builders (this model's
     convs are strided, it has no 2x2 pooling layer).  ``global_pool``: None | "avg" | "max", a
@@ -138,5 +166,6 @@ def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2
     h = _chain(h, _hidden(Dense, h5, **hid))
     outputs = Dense(1, activation="sigmoid")(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
-    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy",
+                  **_metric_lists(metrics, weighted_metrics))
     return model

@@ -663,3 +663,42 @@ struct PoolArgs {
   int relu = 0;
   BwdThrough bt;                   // POOL_GAVG / POOL_GMAX
 };
+
+// ROC / AUC, purity, efficiency and weighted metrics (roc.hip).  The ROC state is a device buffer of
+// its own, int64 words (StepState's layout stays):
+//   [0] k, the fixed-point shift of the weighted set: a weight w enters as llrint(w * 2^k)
+//   [1] the bits of the double 2^k (what the kernel multiplies by), [2..ROC_HDR) spare
+//   then one block of ROC_BLOCK words per (set, class), set 0 unweighted (exact counts), set 1 weighted:
+//   pos[ROC_BINS], neg[ROC_BINS], then the ROC_TAIL exact sums below.
+// The key of an fp32 score s in [0, 1] (roc_key): s < 0.5 -> bits(s) >> ROC_SHIFT, else
+// 2 * ROC_H - (bits(1 - s) >> ROC_SHIFT); 1 - s is exact there, the key is non-decreasing in s.
+#define ROC_SHIFT 16
+#define ROC_H 0x3F00
+#define ROC_BINS (2 * ROC_H + 1)
+#define ROC_HDR 8
+#define ROC_TAIL 8
+#define ROC_T_TP 0
+#define ROC_T_FP 1
+#define ROC_T_TN 2
+#define ROC_T_FN 3
+#define ROC_T_WC 4            // softmax, class 0's block only: sum(w * correct) over the rows
+#define ROC_T_WS 5            // ... and sum(w)
+#define ROC_T_INVALID 6       // scores that are NaN, negative or > 1 (not binned, not in the sums)
+#define ROC_BLOCK (2 * ROC_BINS + ROC_TAIL)
+#define ROC_RES_WORDS 16      // roc_finish's result per (set, class): [0] auc (double bits), [1] P, [2] N,
+//                               [3 .. 3 + ROC_TAIL) the block's tail
+#define ROC_THREADS 256
+#define ROC_MAX_N 16
+struct RocArgs {
+  const float* probs = nullptr;  // [M][N] the head's fp32 probabilities
+  int M = 0, N = 0;
+  int softmax = 0;               // 0: sigmoid head (N == 1, positive iff y > 0.5); 1: one-vs-rest, class n
+  //                                positive iff n is the first argmax of the target row
+  const float* y = nullptr;      // targets [M][N] (the gathered batch) ...
+  const int* yidx = nullptr;     // ... or, non-null: row m is dataset row yidx[m] of st->data_y / st->data_w
+  const StepState* st = nullptr;
+  const float* wb = nullptr;     // gathered weights [M] (weighted instance without yidx)
+  int weighted = 0;              // 1: roc_accum_kernel<true> feeds the weighted set in the same pass
+  long long* state = nullptr;    // ROC_HDR + 2 * N * ROC_BLOCK words
+  long long* res = nullptr;      // roc_finish: 2 * N * ROC_RES_WORDS words
+};

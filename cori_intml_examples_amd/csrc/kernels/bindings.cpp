@@ -69,6 +69,8 @@ void launch_act_fwd(const ActArgs& a, hipStream_t s);
 void launch_act_bwd(const ActArgs& a, hipStream_t s);
 void launch_pool_fwd(const PoolArgs& a, hipStream_t s);
 void launch_pool_bwd(const PoolArgs& a, hipStream_t s);
+void launch_roc_accum(const RocArgs& a, hipStream_t s);
+void launch_roc_finish(const RocArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
 void launch_bn_stats(const BnArgs& a, hipStream_t s);
 void launch_bn_apply_fwd(const BnArgs& a, hipStream_t s);
@@ -551,6 +553,21 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("POOL_GMAX") = POOL_GMAX;
   m.def("pool_fwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_fwd(a, S(s)); check_last("pool_fwd"); });
   m.def("pool_bwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_bwd(a, S(s)); check_last("pool_bwd"); });
+  // ROC / AUC, purity, efficiency and weighted metrics (roc.hip): roc_accum behind the head in a step,
+  // roc_finish once when the metrics are read
+  py::class_<RocArgs>(m, "RocArgs")
+      .def(py::init<>())
+      PTR(RocArgs, probs) RW(RocArgs, M) RW(RocArgs, N) RW(RocArgs, softmax) PTR(RocArgs, y) PTR(RocArgs, yidx)
+      PTR(RocArgs, st) PTR(RocArgs, wb) RW(RocArgs, weighted) PTR(RocArgs, state) PTR(RocArgs, res);
+  m.attr("ROC_BINS") = ROC_BINS;
+  m.attr("ROC_SHIFT") = ROC_SHIFT;
+  m.attr("ROC_H") = ROC_H;
+  m.attr("ROC_HDR") = ROC_HDR;
+  m.attr("ROC_TAIL") = ROC_TAIL;
+  m.attr("ROC_BLOCK") = ROC_BLOCK;
+  m.attr("ROC_RES_WORDS") = ROC_RES_WORDS;
+  m.def("roc_accum", [](const RocArgs& a, uintptr_t s) { launch_roc_accum(a, S(s)); check_last("roc_accum"); });
+  m.def("roc_finish", [](const RocArgs& a, uintptr_t s) { launch_roc_finish(a, S(s)); check_last("roc_finish"); });
   // Keras BatchNormalization (bn.hip): two launches per direction around a stage's linear kernels
   py::class_<BnArgs>(m, "BnArgs")
       .def(py::init<>())

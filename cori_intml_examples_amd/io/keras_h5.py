@@ -166,10 +166,13 @@ def save_model(model, filepath: str, overwrite: bool = True, include_optimizer: 
             _write_weights(f, model)
             if include_optimizer and model.optimizer is not None and model._compiled:
                 from ..optim import optimizers
-                a["training_config"] = json.dumps({
-                    "optimizer_config": optimizers.serialize(model.optimizer),
-                    "loss": _loss_name(model.loss), "metrics": list(model.metrics),
-                    "sample_weight_mode": None, "loss_weights": None})
+                tc = {"optimizer_config": optimizers.serialize(model.optimizer),
+                      "loss": _loss_name(model.loss), "metrics": list(model.metrics),
+                      "sample_weight_mode": None, "loss_weights": None}
+                if getattr(model, "weighted_metrics", None):
+                    # (only when there are any: other checkpoints keep their bytes)
+                    tc["weighted_metrics"] = list(model.weighted_metrics)
+                a["training_config"] = json.dumps(tc)
                 _write_optimizer(f, model)
         os.replace(tmp, filepath)
     finally:
@@ -253,7 +256,8 @@ def load_model(filepath: str, custom_objects=None, compile: bool = True, device=
         if compile and tc:
             tc = json.loads(tc)
             opt = optimizers.deserialize(tc["optimizer_config"])
-            model.compile(optimizer=opt, loss=tc["loss"], metrics=tc.get("metrics") or None)
+            model.compile(optimizer=opt, loss=tc["loss"], metrics=tc.get("metrics") or None,
+                          weighted_metrics=tc.get("weighted_metrics") or None)
             if "optimizer_weights" in f:
                 names = f.attrs("optimizer_weights")["weight_names"]
                 vals = [f.read_dataset("optimizer_weights/" + n) for n in names]

@@ -89,6 +89,9 @@ class Executor:
         self.seed = int(seed) & 0xFFFFFFFF
         self.reducer = None          # data-parallel gradient reducer (parallel.dist)
         self.lr_warmup = None        # (t0, steps, spe, size, epochs, base) device LR schedule
+        # the ROC metrics (metrics.py): off unless configure_metrics asks for one
+        self.roc_on = False          # auc / purity / efficiency or a weighted metric is compiled in
+        self.roc_weighted = False    # ... a weighted one: weighted data feeds the weighted set too
 
     # learning-rate schedule ---------------------------------------------------------------
     def set_lr_warmup(self, t0: int, steps: int, spe: int, size: int, epochs: float, base: float) -> None:
@@ -136,6 +139,35 @@ class Executor:
         raise NotImplementedError
 
     def last_batch_metrics(self):
+        raise NotImplementedError
+
+    def configure_metrics(self, names, weighted_names) -> None:
+        """The canonical metric names of Model.compile (``metrics`` / ``weighted_metrics``), before the
+        first step.  Anything beyond the plain accuracy turns the ROC state on: the steps then
+        accumulate the score histograms and confusion sums of metrics.py."""
+        self.roc_weighted = bool(weighted_names)
+        self.roc_on = self.roc_weighted or any(n != "acc" for n in names)
+        if self.roc_on:
+            self._init_roc()
+
+    def _init_roc(self) -> None:
+        raise NotImplementedError
+
+    def roc_shift(self, data: DeviceData) -> int:
+        """The fixed-point shift k of a weighted data set (sum(w) * 2^k <= 2^61), found once per set;
+        ValueError for negative or non-finite weights."""
+        k = getattr(data, "_roc_k", None)
+        if k is None:
+            from ..metrics import BAD_WEIGHTS, weight_shift
+            w = data.w.detach()
+            if w.numel() and (not bool(torch.isfinite(w).all()) or bool((w < 0).any())):
+                raise ValueError(BAD_WEIGHTS)
+            k = data._roc_k = weight_shift(float(w.double().sum()))
+        return k
+
+    def extra_metrics(self) -> dict:
+        """{name: value} of the ROC metrics since the last reset ('acc', 'auc', 'purity', 'efficiency'
+        and their 'weighted_' twins, as far as the head defines them); synchronises."""
         raise NotImplementedError
 
     # params -------------------------------------------------------------------------------

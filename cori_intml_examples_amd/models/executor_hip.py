@@ -142,7 +142,54 @@ class HipExecutor(Executor):
         self._perm_buf = None
         self._metrics_prev = (0.0, 0.0, 0.0)
         self.grad_scale = 1.0
+        # the ROC state (args.h RocArgs; a buffer of its own, StepState's layout stays), its result
+        # block and the bound data set's fixed-point shift: configure_metrics -> _init_roc
+        self.roc_state = self.roc_res = None
+        self._roc_k = 0
+        self._roc_w_seen = False
         self.params_changed()
+
+    # ------------------------------------------------------------------ ROC metrics
+    def _init_roc(self):
+        K, N = self.K, self.plan.head.N
+        self.roc_state = torch.zeros(K.ROC_HDR + 2 * N * K.ROC_BLOCK, dtype=torch.int64, device=self.device)
+        self.roc_state[1:2].view(torch.float64)[0] = 1.0       # 2^k, k = 0
+        self.roc_res = torch.zeros(2 * N * K.ROC_RES_WORDS, dtype=torch.int64, device=self.device)
+        self._plans.clear()
+
+    def _roc_args(self):
+        a = self.K.RocArgs()
+        hd = self.plan.head
+        a.N, a.softmax = hd.N, int(hd.activation == "softmax")
+        a.state, a.res = self.roc_state.data_ptr(), self.roc_res.data_ptr()
+        return a
+
+    def _bind_roc(self, data: DeviceData):
+        """The weighted set's shift k of the bound data set into the state's header: device memory,
+        not a kernel argument, so captured graphs stay data-set independent (like data_w)."""
+        if not (self.roc_weighted and data.w is not None):
+            return
+        self._roc_w_seen = True
+        k = self.roc_shift(data)
+        if k != self._roc_k:
+            self.roc_state[0] = k
+            self.roc_state[1:2].view(torch.float64)[0] = float(np.ldexp(1.0, k))
+            self._roc_k = k
+
+    def extra_metrics(self):
+        from ..metrics import named_metrics
+        K, N = self.K, self.plan.head.N
+        K.roc_finish(self._roc_args(), torch.cuda.current_stream().cuda_stream)
+        r = self.roc_res.cpu().numpy().reshape(2, N, K.ROC_RES_WORDS)
+        aucs = r[:, :, 0].copy().view(np.float64)
+        return named_metrics(self.plan.head.activation == "softmax", aucs.tolist(), r[:, :, 3:3 + K.ROC_TAIL],
+                             self._roc_w_seen)
+
+    def roc_histograms(self):
+        """(pos, neg, tail) int64 numpy [2][N][...]: the whole ROC state (tests, curves)."""
+        K, N = self.K, self.plan.head.N
+        b = self.roc_state[K.ROC_HDR:].cpu().numpy().reshape(2, N, K.ROC_BLOCK)
+        return b[:, :, :K.ROC_BINS], b[:, :, K.ROC_BINS:2 * K.ROC_BINS], b[:, :, 2 * K.ROC_BINS:]
 
     # ------------------------------------------------------------------ geometry
     def _build_geometry(self):
@@ -352,6 +399,9 @@ class HipExecutor(Executor):
             wt = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).reshape(-1).to(self.device)
             if wt.shape[0] != n:
                 raise ValueError("sample weights have %d entries for %d samples" % (wt.shape[0], n))
+            if self.roc_weighted:
+                from ..metrics import check_weights
+                check_weights(w)
         return DeviceData(xs.reshape(n, -1), yt, n, wt)
 
     def _bind_data(self, data: DeviceData, perm: Optional[torch.Tensor]):
@@ -409,6 +459,8 @@ class HipExecutor(Executor):
         if self._expected_pos != pos:
             self._st_i32[1] = pos
         bp = self._plan_for(bs, "train", data.w is not None)
+        if self.roc_on:
+            self._bind_roc(data)
         bp.run(k)
         self._expected_pos = pos + k * bs
         self.opt.iterations += k
@@ -421,6 +473,8 @@ class HipExecutor(Executor):
     def eval_step(self, data, pos, bs):
         self._bind_data(data, None)
         self._set_eval_pos(pos, bs)
+        if self.roc_on:
+            self._bind_roc(data)
         self._plan_for(bs, "eval", data.w is not None).run()
 
     def predict_step(self, data, pos, bs):
@@ -445,6 +499,9 @@ class HipExecutor(Executor):
         o = self.K.STEP_STATE_METRICS_OFFSET // 8
         self._st_f64[o:o + 4 * self.K.STEP_STATE_METRIC_SLOTS].zero_()
         self._metrics_prev = (0.0, 0.0, 0.0)
+        if self.roc_on:
+            self.roc_state[self.K.ROC_HDR:].zero_()
+            self._roc_w_seen = False
 
     def read_metrics(self):
         ls, cs, n = self._metrics()
@@ -570,7 +627,9 @@ class BatchPlan(GeometryMixin):
         hd = ex.plan.head
         self.head_blocks = cdiv(bs, K.head_rows_per_block(False))   # re-set below if the head fuses the epilogue
         head_slab_blocks = cdiv(bs, K.head_rows_per_block(True))
-        self.probs = z(bs, hd.N, dt=torch.float32) if mode == "predict" else None
+        # (a plan with a ROC metric: roc_accum reads the head's probabilities in train and eval mode too)
+        self.roc = ex.roc_on and mode != "predict"
+        self.probs = z(bs, hd.N, dt=torch.float32) if mode == "predict" or self.roc else None
         if self.training:
             self.head_wslab = z(head_slab_blocks, hd.K, hd.N, dt=torch.float32)
             self.head_bslab = z(head_slab_blocks, hd.N, dt=torch.float32)
@@ -991,6 +1050,16 @@ class BatchPlan(GeometryMixin):
         # of each row group running the head -- measured 15.6 us against 13.3 us for the split-K
         # dense launch + this head launch at RPV B=128, and was removed in round 5)
         self._add("head", lambda s, a=h: K.head(a, s), head=h)
+        if self.roc:
+            # directly behind the head, on the main stream, inside the captured step
+            r = ex._roc_args()
+            r.probs, r.M = self.probs.data_ptr(), self.bs
+            r.y, r.st = self.yb.data_ptr(), ex.state.data_ptr()
+            if self.pro_free:
+                r.yidx = self.srcidx.data_ptr()
+            if self.weighted and ex.roc_weighted:
+                r.wb, r.weighted = self.wb.data_ptr(), 1
+            self._add("roc_accum", lambda s, a=r: K.roc_accum(a, s), roc=r)
 
     # ---------------------------------------------------------------- step program: backward
     def _add_group(self, spec, descs, bias_spec=None, more=()):

@@ -43,6 +43,13 @@ class RefExecutor(Executor):
         self.emulate_bf16 = bool(tune("ref_bf16"))
         # Keras weight regularizers [(lo, hi, l1, l2)], read here (at compile) like the clip values
         self.regs = store.regularized_ranges()
+        self._roc = None             # metrics.RocState, the numpy twin of the HIP executor's ROC state
+        self._roc_w_seen = False
+
+    def _init_roc(self):
+        from ..metrics import RocState
+        hd = self.plan.head
+        self._roc = RocState(hd.N, hd.activation == "softmax")
 
     # ------------------------------------------------------------------------------ data
     def upload(self, x, y, w=None):
@@ -54,6 +61,9 @@ class RefExecutor(Executor):
         wt = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).reshape(-1) if w is not None else None
         if wt is not None and wt.shape[0] != xt.shape[0]:
             raise ValueError("sample weights have %d entries for %d samples" % (wt.shape[0], xt.shape[0]))
+        if wt is not None and self.roc_weighted:
+            from ..metrics import check_weights
+            check_weights(wt.numpy())
         return DeviceData(xt, yt, xt.shape[0], wt)
 
     # ------------------------------------------------------------------------------ core
@@ -341,6 +351,7 @@ class RefExecutor(Executor):
                 self.reducer.reduce_all(self.store.grad)
             self._apply_update()
         self._accumulate(loss, corr, bs, penalty)
+        self._roc_accumulate(z, y, w, data)
 
     def _penalty(self) -> float:
         return float(R.regularization_penalty(self.regs, self.store.master)) if self.regs else 0.0
@@ -358,10 +369,9 @@ class RefExecutor(Executor):
             z, _, _ = self._forward(x, False, 0)
             loss, _, corr = self._head_loss(z, y, w)
         self._accumulate(loss, corr, bs, self._penalty())
+        self._roc_accumulate(z, y, w, data)
 
-    def predict_step(self, data: DeviceData, pos: int, bs: int) -> torch.Tensor:
-        with torch.no_grad():
-            z, _, _ = self._forward(data.x[pos:pos + bs], False, 0)
+    def _probs(self, z):
         act = self.plan.head.activation
         if act == "softmax":
             return torch.softmax(z, -1)
@@ -369,8 +379,33 @@ class RefExecutor(Executor):
             return torch.sigmoid(z)
         return z
 
+    def _roc_accumulate(self, z, y, w, data):
+        """The batch's probabilities (what predict_step returns for these rows) into the ROC state."""
+        if self._roc is None:
+            return
+        if w is not None and self.roc_weighted:
+            self._roc.k = self.roc_shift(data)
+            self._roc_w_seen = True
+        else:
+            w = None
+        self._roc.accumulate(self._probs(z).numpy(), y.numpy(), None if w is None else w.numpy())
+
+    def extra_metrics(self):
+        from ..metrics import hist_auc, named_metrics
+        st = self._roc
+        aucs = [[hist_auc(st.pos[s, n], st.neg[s, n]) for n in range(st.N)] for s in range(2)]
+        return named_metrics(st.softmax, aucs, st.tail, self._roc_w_seen)
+
+    def predict_step(self, data: DeviceData, pos: int, bs: int) -> torch.Tensor:
+        with torch.no_grad():
+            z, _, _ = self._forward(data.x[pos:pos + bs], False, 0)
+        return self._probs(z)
+
     def reset_metrics(self):
         self._acc.zero_()
+        if self._roc is not None:
+            self._roc.reset()
+            self._roc_w_seen = False
 
     def read_metrics(self):
         ls, cs, n = self._acc.tolist()

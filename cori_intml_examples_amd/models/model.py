@@ -42,6 +42,9 @@ class Model:
         self.optimizer = None
         self.loss = None
         self.metrics = []
+        self.weighted_metrics = []
+        self._metric_names = []          # canonical names of metrics / weighted_metrics (metrics.CANONICAL)
+        self._weighted_names = []
         self._executor = None
         self._plan = None
         self.stop_training = False
@@ -147,7 +150,7 @@ class Model:
 
     # ------------------------------------------------------------------ compile
     def compile(self, optimizer, loss=None, metrics=None, loss_weights=None, sample_weight_mode=None,
-                **kwargs):
+                weighted_metrics=None, **kwargs):
         if not self._chain:
             raise RuntimeError("model has no layers")
         if loss_weights is not None or sample_weight_mode is not None:
@@ -155,13 +158,34 @@ class Model:
         self.optimizer = optimizers.get(optimizer)
         self.loss = loss
         canonical_loss(loss)
+        from ..metrics import canonical_metric
         self.metrics = list(metrics or [])
-        for m in self.metrics:
-            if m not in ("accuracy", "acc"):
-                raise NotImplementedError("metric %r" % (m,))
+        self.weighted_metrics = list(weighted_metrics or [])
+        self._metric_names = [canonical_metric(m) for m in self.metrics]
+        self._weighted_names = [canonical_metric(m) for m in self.weighted_metrics]
         self._plan = build_plan(self._chain, loss)
+        self._check_metrics()
         self._compiled = True
         self._make_executor()
+
+    def _check_metrics(self):
+        """Which head takes which metric: a sigmoid head of one column all of them; a softmax head of
+        2..16 classes the accuracy and the one-vs-rest AUC; a linear / mse head the plain accuracy only."""
+        hd = self._plan.head
+        new = [n for n in self._metric_names if n != "acc"] + ["weighted_" + n for n in self._weighted_names]
+        if not new:
+            return
+        where = "output layer %s (%s, %d columns)" % (hd.dense.name, hd.activation or "linear", hd.N)
+        if hd.activation == "sigmoid" and hd.N == 1:
+            return
+        if hd.activation == "softmax" and 2 <= hd.N <= 16:
+            bad = [n for n in new if n.split("weighted_")[-1] in ("purity", "efficiency")]
+            if bad:
+                raise NotImplementedError("metric %r on %s: purity / efficiency need a sigmoid head of one column"
+                                          % (bad[0], where))
+            return
+        raise NotImplementedError("metric %r on %s: the ROC and weighted metrics need a sigmoid head of one "
+                                  "column or a softmax head of 2..16 classes" % (new[0], where))
 
     def _make_executor(self):
         base = getattr(self.optimizer, "_base_optimizer", self.optimizer)
@@ -175,13 +199,20 @@ class Model:
         else:
             from .executor_ref import RefExecutor
             self._executor = RefExecutor(self._plan, self.store, base, self._seed)
+        self._executor.configure_metrics(self._metric_names, self._weighted_names)
         if getattr(self.optimizer, "distributed", False):
             from ..parallel import dist
             self._executor.reducer = dist.make_reducer(self._executor, self.optimizer)
 
     @property
     def metrics_names(self):
-        return ["loss"] + (["acc"] if self.metrics else [])
+        return ["loss"] + list(self._metric_names) + ["weighted_" + n for n in self._weighted_names]
+
+    def _metric_values(self, loss, acc):
+        """[loss] + one value per metrics_names entry, from the executor's counters since the last reset."""
+        names = self.metrics_names[1:]
+        extra = self._executor.extra_metrics() if self._executor.roc_on else {}
+        return [loss] + [acc if n == "acc" else extra[n] for n in names]
 
     def _check_compiled(self):
         if not self._compiled:
@@ -205,10 +236,31 @@ class Model:
         data = self._upload_weighted(x, y, sample_weight, None)
         self._run_eval(data, batch_size or 32)
         loss, acc, _ = ex.read_metrics()
+        vals = self._metric_values(loss, acc)
         if verbose:
-            print("%d/%d [==============================] - loss: %.4f%s" % (
-                data.n, data.n, loss, (" - acc: %.4f" % acc) if self.metrics else ""))
-        return [loss, acc] if self.metrics else loss
+            print("%d/%d [==============================] - %s" % (
+                data.n, data.n, " - ".join("%s: %.4f" % nv for nv in zip(self.metrics_names, vals))))
+        return vals if len(vals) > 1 else loss
+
+    def evaluate_roc(self, x, y, sample_weight=None, batch_size=32):
+        """The ROC curve and threshold-0.5 statistics (metrics.RocResult) of the model's probabilities
+        on (x, y): one result for a sigmoid head, a list of one-vs-rest results, one per class, for a
+        softmax head.  Works whether or not the ROC metrics were compiled in."""
+        from ..metrics import check_weights, per_class_curves, roc_curve
+        from .executor_base import prepare_targets
+        self._check_compiled()
+        hd = self._plan.head
+        if not ((hd.activation == "sigmoid" and hd.N == 1) or (hd.activation == "softmax" and 2 <= hd.N <= 16)):
+            raise NotImplementedError("evaluate_roc on output layer %s (%s, %d columns)"
+                                      % (hd.dense.name, hd.activation or "linear", hd.N))
+        w = standardize_weights(y, len(x), sample_weight, None)
+        if w is not None:
+            check_weights(w)
+        p = self.predict(x, batch_size=batch_size)
+        t = prepare_targets(y, self._plan)
+        if hd.activation == "sigmoid":
+            return roc_curve(t[:, 0], p[:, 0], w)
+        return per_class_curves(t, p, w)
 
     def _upload_weighted(self, x, y, sample_weight=None, class_weight=None):
         """(x, y) on the executor's device with the per-sample loss weights Keras'
@@ -220,6 +272,9 @@ class Model:
                                     sample_weight, class_weight)
             if w is None:
                 return x
+            if self._weighted_names:
+                from ..metrics import check_weights
+                check_weights(w)
             return DeviceData(x.x, x.y, x.n, torch.as_tensor(w).to(x.y.device))
         w = standardize_weights(y, len(x), sample_weight, class_weight)
         return ex.upload(x, y, w) if w is not None else ex.upload(x, y)
@@ -272,7 +327,8 @@ class Model:
         perm = torch.arange(data.n, device=ex.device)
         ex.train_step(data, perm, 0, data.n)
         loss, acc, _ = ex.read_metrics()
-        return [loss, acc] if self.metrics else loss
+        vals = self._metric_values(loss, acc)
+        return vals if len(vals) > 1 else loss
 
     def test_on_batch(self, x, y, sample_weight=None):
         return self.evaluate(x, y, batch_size=len(x), verbose=0, sample_weight=sample_weight)

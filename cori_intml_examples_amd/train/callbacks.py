@@ -187,6 +187,11 @@ class ProgbarLogger(Callback):
             self._out().flush()
 
 
+def _auto_max(monitor: str) -> bool:
+    """mode='auto': larger is better for an accuracy and for the ROC metrics (auc, purity, efficiency)."""
+    return any(k in monitor for k in ("acc", "auc", "purity", "efficiency"))
+
+
 class ModelCheckpoint(Callback):
     """Whole-model Keras-HDF5 save every epoch (``rpv.py:100-101``)."""
     needs_batch_logs = False
@@ -203,7 +208,7 @@ class ModelCheckpoint(Callback):
         self.epochs_since_last_save = 0
         if mode not in ("auto", "min", "max"):
             mode = "auto"
-        if mode == "min" or (mode == "auto" and not ("acc" in monitor or monitor.startswith("fmeasure"))):
+        if mode == "min" or (mode == "auto" and not (_auto_max(monitor) or monitor.startswith("fmeasure"))):
             self.monitor_op, self.best = np.less, np.inf
         else:
             self.monitor_op, self.best = np.greater, -np.inf
@@ -255,7 +260,7 @@ class ReduceLROnPlateau(Callback):
         self._reset()
 
     def _reset(self):
-        if self.mode == "min" or (self.mode == "auto" and "acc" not in self.monitor):
+        if self.mode == "min" or (self.mode == "auto" and not _auto_max(self.monitor)):
             self.monitor_op = lambda a, b: np.less(a, b - self.min_delta)
             self.best = np.inf
         else:
@@ -303,7 +308,7 @@ class EarlyStopping(Callback):
         self.monitor, self.patience, self.verbose = monitor, patience, verbose
         self.baseline, self.min_delta = baseline, abs(min_delta)
         self.restore_best_weights = restore_best_weights
-        if mode == "min" or (mode == "auto" and "acc" not in monitor):
+        if mode == "min" or (mode == "auto" and not _auto_max(monitor)):
             self.monitor_op = np.less
             self.min_delta *= -1
         else:

@@ -10,7 +10,8 @@ per graph launch.
 Reference behaviour reproduced: ``validation_split`` takes the *last* fraction
 before shuffling (``DistHPO_mnist.ipynb:188,293``: 60000 -> 49800/10200), the final
 partial batch is processed, ``Train on N samples, validate on M samples`` banner,
-History keys ``loss, acc, val_loss, val_acc`` (+ ``lr`` from ReduceLROnPlateau).
+History keys ``loss, acc, val_loss, val_acc`` (+ ``lr`` from ReduceLROnPlateau; + the ROC and weighted
+metrics the model was compiled with, epoch logs only).
 """
 from __future__ import annotations
 
@@ -161,7 +162,7 @@ def fit_loop(model, x, y, batch_size, epochs, verbose, callbacks, validation_spl
                 if need_batch_logs:
                     l, a = ex.last_batch_metrics()
                     logs = {"batch": b, "size": bs, "loss": l}
-                    if model.metrics:
+                    if "acc" in out_labels:        # (batch logs stay loss / acc: no per-batch ROC metrics)
                         logs["acc"] = a
                     cb.on_batch_end(b, logs)
                 if progbar is not None and verbose == 1:
@@ -173,15 +174,11 @@ def fit_loop(model, x, y, batch_size, epochs, verbose, callbacks, validation_spl
             if model.stop_training:
                 break
         loss, acc, _ = ex.read_metrics()
-        epoch_logs = {"loss": loss}
-        if model.metrics:
-            epoch_logs["acc"] = acc
+        epoch_logs = dict(zip(out_labels, model._metric_values(loss, acc)))
         if do_val:
             model._run_eval(val, batch_size)
             vloss, vacc, _ = ex.read_metrics()
-            epoch_logs["val_loss"] = vloss
-            if model.metrics:
-                epoch_logs["val_acc"] = vacc
+            epoch_logs.update(zip(["val_" + n for n in out_labels], model._metric_values(vloss, vacc)))
         if check_dp:
             # before the callbacks: a checkpoint / early-stop decision never sees diverged ranks
             model.history.dp_consistency.append(dp_consistency_check(model, epoch))

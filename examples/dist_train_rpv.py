@@ -44,7 +44,10 @@ test_output = model.predict(test[0], batch_size=1024)
         from cori_intml_examples_amd.apps.rpv import classification_report
         print("unweighted:", classification_report(labels, out))
         print("weighted:  ", classification_report(labels, out, weights))
-        from sklearn.metrics import roc_auc_score
+        try:
+            from sklearn.metrics import roc_auc_score
+        except ImportError:       # the project's own histogram AUC (metrics.py)
+            from cori_intml_examples_amd.metrics import roc_auc_score
         print("ROC AUC: %.4f" % roc_auc_score(labels, out))
     finally:
         c.close()
