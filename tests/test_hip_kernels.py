@@ -11,6 +11,7 @@ from cori_intml_examples_amd.ops import reference as R
 from cori_intml_examples_amd.ops.rng import dropout_keep
 from cori_intml_examples_amd.utils import set_random_seed
 
+from helpers import conv_oracle as O
 from test_hip_model import _build, _data
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +22,19 @@ def _rel(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-12)
 
 
-def _step(kind, drop, cin, hw=16, n=40, opt="SGD"):
+def _step(kind, drop, cin, hw=16, n=40, opt="SGD", perm=None, pos=0, data=None):
+    """One training step of n rows.  perm / pos: the step trains rows perm[pos:pos + n] of a data
+    set of len(perm) samples (default: the identity over n samples at pos 0); data: that data
+    set's (x, y) builder, called with (model, samples)."""
     set_random_seed(99)
     m = _build(kind, "cuda", opt=opt, drop=drop, cin=cin, hw=hw)
     ex = m._executor
-    x, y = _data(m, n, seed=4)
+    total = n if perm is None else len(perm)
+    x, y = _data(m, total, seed=4) if data is None else data(m, total)
     d = ex.upload(x, y)
     w_before = m.store.master.clone()
-    ex.train_step(d, torch.arange(n, device=ex.device), 0, n)
+    perm = torch.arange(n, device=ex.device) if perm is None else torch.as_tensor(perm).to(ex.device)
+    ex.train_step(d, perm, pos, n)
     torch.cuda.synchronize()
     bp = ex._plans[(n, "train")]
     return m, ex, bp, w_before
@@ -82,7 +88,14 @@ def test_conv_forward(kind, drop, cin, hw, n):
         z = R.conv2d(x, w, b, cs.stride, cs.conv.padding)
         r = torch.relu(z) if g.relu else z
         if g.pool:
-            r, code = R.maxpool2x2(r)
+            r, _ = R.maxpool2x2(r)
+            # the kernel's codes, by the oracle's near-tie rule: the first maximum wherever no other window
+            # element lies within the two elements' float64-derived bounds of it
+            z64, A = O.conv_forward(x, w, b, cs.stride, cs.conv.padding)
+            p = O.relu_pool(z64, (g.KH * g.KW * g.Cin + 3) * O.U * A, g.relu, True)
+            res, share = O.compare_codes("conv%d" % g.i, bp.conv_code[g.i].cpu()[..., :g.Cout], p)
+            print("conv%d codes: near-tie share %.3f %%, %s" % (g.i, 100 * share, "; ".join(map(str, res))))
+            assert all(c.ok for c in res), [str(c) for c in res if not c.ok]
         if g.rate > 0:
             r = r * _mask(r.numel(), g.rate, ex.seed, g.stream, step).view(r.shape)
         got = _f(bp.conv_out[g.i])
