@@ -306,10 +306,18 @@ struct WgradArgs {
   // dense): X-halo pixel stride in elements, X-halo row stride in pixels, dY row stride
   int xpix = 0, xrow = 0, dyld = 0;
   int kperm = 0;                 // bit0: k index 8g+j <-> pixel 4g+j / 16+4g+j-4; bit1: no row-aligned fast path
+  // halo kernels, signature launches: blocks of a split whose staging loads are in flight at once
+  // (wgrad_halo_body.h DEPTH; wgrad_halo_depth): 0 = the depth of the signature's deep instance,
+  // 1 = the depth-one kernels (A/B and the bit-identity tests), d = that depth where it is
+  // instantiated.  Host-only; it sits in the 4 bytes of padding before xidx, so the
+  // kernel-argument layout of every WgradArgs kernel is what it was without it.
+  int depth = 0;
   // xidx != null: image b of x is dataset row xidx[b] of st->data_x (prologue-free step)
   const int* xidx = nullptr;
   const StepState* xst = nullptr;
 };
+static_assert(offsetof(WgradArgs, xidx) == offsetof(WgradArgs, depth) + 4 && offsetof(WgradArgs, depth) % 8 == 4,
+              "WgradArgs::depth fills padding: no kernel argument moves");
 
 // The WgradArgs fields that are geometry of the halo kernels: the ONE list behind the body's
 // geometry traits (wgrad_halo_body.h), the layer signatures and the host's field-by-field

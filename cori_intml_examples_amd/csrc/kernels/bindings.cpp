@@ -25,6 +25,7 @@ int wgrad_halo_resident(const WgradArgs& a, int MT, int NTT, bool bias);
 int wgrad_halo_variant(const WgradArgs& a, int MT, int NTT);
 int dual_halo_variant(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp, bool extras);
 bool dual_halo_dgrad_fixed(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, bool xp, bool extras);
+int wgrad_halo_depth(const WgradArgs& a, int MT, int NTT, int splits);
 int head_rows_per_block(bool fused);
 int head_epi_max();
 void launch_wgrad(const WgradArgs& a, int ktw, int ntt, int splits, hipStream_t s);
@@ -163,7 +164,8 @@ PYBIND11_MODULE(_kernels, m) {
       RW(WgradArgs, dbg) PTR(WgradArgs, ts) PTR(WgradArgs, ts2) RW(WgradArgs, opt) RW(WgradArgs, opt_w)
       RW(WgradArgs, opt_b) RW(WgradArgs, xpix) RW(WgradArgs, xrow) RW(WgradArgs, dyld) RW(WgradArgs, kperm)
       PTR(WgradArgs, xidx) PTR(WgradArgs, xst) RW(WgradArgs, pk_fwd) RW(WgradArgs, pk_bwd) RW(WgradArgs, pk_NT)
-      RW(WgradArgs, pk_NTb) RW(WgradArgs, wt) RW(WgradArgs, opt_nograd) RW(WgradArgs, spec);
+      RW(WgradArgs, pk_NTb) RW(WgradArgs, wt) RW(WgradArgs, opt_nograd) RW(WgradArgs, spec)
+      RW(WgradArgs, depth);
 
   py::class_<DenseFwdArgs>(m, "DenseFwdArgs")
       .def(py::init<>())
@@ -383,6 +385,8 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("NTT"), py::arg("xp") = false, py::arg("extras") = false);
   m.def("dual_halo_dgrad_fixed", &dual_halo_dgrad_fixed, py::arg("ca"), py::arg("ntc"), py::arg("wa"), py::arg("MT"),
         py::arg("NTT"), py::arg("xp") = false, py::arg("extras") = false);
+  // the staging depth the standalone halo wgrad launch of these args runs at (launch_wgrad_halo)
+  m.def("wgrad_depth_variant", &wgrad_halo_depth, py::arg("wa"), py::arg("MT"), py::arg("NTT"), py::arg("splits"));
   m.def("head_rows_per_block", &head_rows_per_block, py::arg("fused") = false);
   m.def("conv_tile_lds_bytes", &conv_tile_lds_bytes);
   m.def("conv_tile", [](const ConvMMArgs& a, int ntc, uintptr_t s, bool big, int nbuf) {

@@ -66,14 +66,31 @@ int wgrad_halo_variant(const WgradArgs& a, int MT, int NTT) {
   return v && wgrad_sig_at(v).alone ? v : 0;
 }
 
+static dim3 wh_grid(const WgradArgs& a, int MT, int NTT, int splits) {
+  return dim3(splits, (a.NT + NTT - 1) / NTT, (a.Ktiles + MT - 1) / MT);
+}
+// wh_t's rule
+static bool wh_pipe(const WgradArgs& a, dim3 grid) { return grid.x * grid.y * grid.z < 512 && a.blocks_per_split > 1; }
+
+// The staging depth the standalone launch runs at: where it takes a signature's non-pipelined
+// form, that signature has a deep instance (wgrad_deep.hip) and a.depth is 0 or the instance's
+// depth, that depth; 1 everywhere else.
+int wgrad_halo_depth(const WgradArgs& a, int MT, int NTT, int splits) {
+  const int v = wgrad_halo_variant(a, MT, NTT);
+  if (!v || wh_pipe(a, wh_grid(a, MT, NTT, splits))) return 1;
+  const WgradDeep& dp = wgrad_deep_at(v);
+  return dp.alone && (a.depth == 0 || a.depth == dp.depth) ? dp.depth : 1;
+}
+
 // MT m-tiles x NTT n-tiles per workgroup; each wave owns ceil((MT+bias)/4) m-tiles
 // (MTW <= 4, MTW*NTT <= 16); grid = (splits, n-groups, m-groups)
 void launch_wgrad_halo(const WgradArgs& a, int MT, int NTT, int splits, hipStream_t s) {
   const bool cs4 = a.Cs_in == 4;
-  dim3 grid(splits, (a.NT + NTT - 1) / NTT, (a.Ktiles + MT - 1) / MT);
+  const dim3 grid = wh_grid(a, MT, NTT, splits);
   const size_t lds = wgrad_halo_lds_bytes(a, MT, NTT);
-  if (const int v = wgrad_halo_variant(a, MT, NTT)) {   // (pipe: wh_t's rule)
-    wgrad_sig_at(v).alone(a, grid, lds, grid.x * grid.y * grid.z < 512 && a.blocks_per_split > 1, s);
+  if (const int v = wgrad_halo_variant(a, MT, NTT)) {
+    if (wgrad_halo_depth(a, MT, NTT, splits) > 1) wgrad_deep_at(v).alone(a, grid, lds, s);
+    else wgrad_sig_at(v).alone(a, grid, lds, wh_pipe(a, grid), s);
     return;
   }
   const int mtw = (MT + (a.bslab ? 1 : 0) + 3) / 4;

@@ -1,6 +1,8 @@
 // Body of the halo-staged weight-gradient kernel (see wgrad_halo.hip for the design), as
 // a device function of the block index (co-scheduled with dgrad by dual_halo.hip).
 #pragma once
+#include <type_traits>
+
 #include "bwd_through.h"
 
 // a staged X-halo chunk and its LDS element offset
@@ -34,6 +36,7 @@ struct WgGeoRt {
   __device__ __forceinline__ static bool pooled(const WgradArgs& a) { return a.dy_code != nullptr; }
   __device__ __forceinline__ static bool bias(const WgradArgs& a) { return a.bslab != nullptr; }
   __device__ __forceinline__ static bool xidx(const WgradArgs& a) { return a.xidx != nullptr; }
+  static constexpr bool fixed = false;
 };
 template <class S, bool XIDX>
 struct WgGeoFix {
@@ -45,6 +48,8 @@ struct WgGeoFix {
   __device__ __forceinline__ static constexpr bool pooled(const WgradArgs&) { return S::pooled; }
   __device__ __forceinline__ static constexpr bool bias(const WgradArgs&) { return S::bias; }
   __device__ __forceinline__ static constexpr bool xidx(const WgradArgs&) { return XIDX; }
+  static constexpr bool fixed = true;
+  using Sig = S;
 };
 
 // image b of the wgrad input: the activation buffer, or (prologue-free step, first layer)
@@ -62,7 +67,11 @@ __device__ __forceinline__ const bf16* wg_xbase(const WgradArgs& a, int b) {
 // INSTR: the ablation switches (dbg) and diagnostics stamps (a.ts2) are compiled in (the
 // co-scheduled dual launch instantiates false)
 // G: the geometry source (WgGeoRt / WgGeoFix above); MT_launch is read by WgGeoRt only
-template <int MTW, int NTT, bool CS4, bool PIPE, bool INSTR = true, class G = WgGeoRt>
+// DEPTH: blocks whose staging loads are in flight at once.  1: the pipeline above (one block
+// ahead).  > 1 (PIPE, a WgGeoFix geometry with the pooled expansion, no INSTR): a ring of DEPTH
+// register stages, each one block's chunks at the signature's own chunk counts -- a commit then
+// waits for loads issued DEPTH - 1 MFMA phases and commits earlier, not one MFMA phase earlier.
+template <int MTW, int NTT, bool CS4, bool PIPE, bool INSTR = true, class G = WgGeoRt, int DEPTH = 1>
 __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT_launch, const int bx, const int by,
                                                 const int bz, char* smem) {
   const int MT = G::MT(MT_launch);
@@ -259,11 +268,116 @@ __device__ __forceinline__ void wgrad_halo_body(const WgradArgs& a, const int MT
       }
   };
 
+  constexpr int WH_PX = 4, WH_PY = 4;
+  if constexpr (DEPTH > 1) {
+    // The pipeline below with DEPTH blocks in flight.  Same LDS images, commit order, barriers
+    // and MFMA order, so the accumulators are bit-identical; only the distance between a
+    // block's loads and its commit grows.  Every load is of a block in [blk0, blk1) (the
+    // clamp to blk1 - 1, as below: unconditional loads keep the commit's wait a count of the
+    // younger loads, where a skipped fetch would make it a wait for all of them).
+    static_assert(PIPE && !INSTR && G::fixed, "the deep pipeline is built for production signature instances");
+    using S = typename G::Sig;
+    constexpr int c_Rin = (S::R - 1) * S::stride + S::KH, c_Win = (S::Wo - 1) * S::stride + S::KW;
+    constexpr int NX = (c_Rin * c_Win * (S::Cs_in / (CS4 ? 4 : 8)) + 255) / 256;      // X-halo chunks per thread
+    constexpr int NY = ((S::R >> 1) * (S::Wo >> 1) * NTT * 2 + 255) / 256;            // pooled dY chunks per thread
+    static_assert(S::pooled && (S::R & 1) == 0 && S::Ho % S::R == 0 && (S::Wo & 1) == 0 && ((S::R * S::Wo) & 31) == 0 &&
+                      S::NT % NTT == 0 && S::NT * 16 <= S::Cs_dy && 2 * S::dHp >= S::Ho && 2 * S::dWp >= S::Wo,
+                  "a deep stage holds pooled dY chunks (pexp)");
+    static_assert(NX <= WH_PX && NY <= WH_PY, "one block's staging fits the pipeline's chunk budget");
+    using XT = typename std::conditional<CS4, uint2, uint4>::type;
+    struct Stage {
+      XT xr[NX];
+      uint4 yr[NY];
+      uint2 yc[NY];
+    };
+    Stage st[DEPTH];
+    // per-lane staging constants, the same for every block (as below)
+    int xa[NX], xrow[NX], xoff[NX], qoff[NY], qdst[NY];
+    uint32_t xcol = 0;
+#pragma unroll
+    for (int u = 0; u < NX; ++u) {
+      const int idx = min(tid + u * 256, nch_x - 1);
+      const int pix = fcpp.div(idx), c = (idx - pix * cpp) * cw;
+      const int r = fwin.div(pix), px = pix - r * W_in;
+      const int ix = px - G::pad_l(a);
+      xa[u] = (r * XR + px) * XP + c;
+      xrow[u] = r;
+      xoff[u] = (r * G::W(a) + ix) * Cs + c;
+      if (ix >= 0 && ix < G::W(a)) xcol |= 1u << u;
+    }
+#pragma unroll
+    for (int u = 0; u < NY; ++u) {
+      const int q = min(tid + u * 256, nq - 1);
+      const int p2 = fcpr.div(q), ch = q - p2 * cpr;
+      const int ry = fhw.div(p2), wx = p2 - ry * hw;
+      qoff[u] = (ry * G::dWp(a) + wx) * G::Cs_dy(a) + nt0 * 16 + ch * 8;
+      qdst[u] = ((2 * ry) * G::Wo(a) + 2 * wx) * ldb + ch * 8;
+    }
+    // chunk u of block blk's halo lies inside the image (else it is staged as zeros)
+    auto x_ok = [&](const int u, const int blk) {
+      const int b = blk / nrb, iy = (blk - b * nrb) * R * s - G::pad_t(a) + xrow[u];
+      return ((xcol >> u) & 1u) && iy >= 0 && iy < G::H(a);
+    };
+    // A block's X-halo and pooled dY chunks in ONE batch of independent loads.  Nothing here
+    // uses a loaded value (the padding chunks' zeros are selected in commit): a use would wait
+    // for the batch where it is issued.
+    auto fetch = [&](Stage& t, const int blk) {
+      const int b = blk / nrb, oy0 = (blk - b * nrb) * R;
+      const bf16* xbase = wg_xbase<G>(a, b);
+      const bf16* xrow0 = xbase + (ptrdiff_t)(oy0 * s - G::pad_t(a)) * G::W(a) * Cs;   // may point before xbase
+#pragma unroll
+      for (int u = 0; u < NX; ++u) t.xr[u] = *reinterpret_cast<const XT*>(x_ok(u, blk) ? xrow0 + xoff[u] : xbase);
+      const size_t qb = (((size_t)b * G::dHp(a) + (oy0 >> 1)) * G::dWp(a)) * G::Cs_dy(a);
+#pragma unroll
+      for (int u = 0; u < NY; ++u) {
+        const size_t o = qb + qoff[u];
+        t.yr[u] = *reinterpret_cast<const uint4*>(a.dy + o);
+        t.yc[u] = *reinterpret_cast<const uint2*>(a.dy_code + o);
+      }
+    };
+    // Branch-free: a thread past the last chunk holds the last chunk's own offset and data (the
+    // clamped indices above), so its store repeats that chunk's -- the same LDS image, and no
+    // exec-masked block between the loads and their wait.
+    auto commit = [&](const Stage& t, const int blk) {
+#pragma unroll
+      for (int u = 0; u < NX; ++u) {
+        const bool ok = x_ok(u, blk);
+        XT v = t.xr[u];
+        v.x = ok ? v.x : 0u, v.y = ok ? v.y : 0u;
+        if constexpr (!CS4) v.z = ok ? v.z : 0u, v.w = ok ? v.w : 0u;
+        *reinterpret_cast<XT*>(xl + xa[u]) = v;
+      }
+#pragma unroll
+      for (int u = 0; u < NY; ++u) pq_store_at(qdst[u], t.yr[u], t.yc[u]);
+    };
+    // (the batches leave stage by stage, as in the loop: the scheduler must not interleave them,
+    // or the first commit's wait -- and, the loop header being shared, every later one -- counts
+    // the other stages' loads in)
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+      fetch(st[d], min(blk0 + d, blk1 - 1));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // (unrolled by DEPTH: block blk0 + n lives in stage n % DEPTH, a compile-time index.  The
+    // last block leaves by a jump past the loop: a `break` to the outer test left an edge from the
+    // middle of a round to its head, and the head's wait then counted no younger batch)
+    for (int blk = blk0;;) {
+#pragma unroll
+      for (int d = 0; d < DEPTH; ++d, ++blk) {
+        if (blk >= blk1) goto deep_done;
+        if (blk != blk0) __syncthreads();   // previous block's readers are done
+        commit(st[d], blk);
+        __syncthreads();
+        fetch(st[d], min(blk + DEPTH, blk1 - 1));   // the freed stage takes block blk + DEPTH
+        mma_block(npb);
+      }
+    }
+  deep_done:;
+  } else
   // Software pipeline over the workgroup's blocks (when one block's staging fits WH_PX + WH_PY
   // chunks per thread): block blk+1's X-halo and dY chunks are loaded into registers while
   // block blk's MFMAs run, and go to LDS after the barrier that retires blk's readers --
   // the staging loads' latency, not the MFMAs, was the per-block cost.
-  constexpr int WH_PX = 4, WH_PY = 4;
   if (PIPE && dbg_stage && nch_x <= WH_PX * 256 && (pexp ? nq : nch_y) <= WH_PY * 256) {
     uint4 xr[WH_PX], yr[WH_PY];
     int xa[WH_PX];

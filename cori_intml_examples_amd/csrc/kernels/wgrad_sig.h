@@ -117,6 +117,19 @@ struct WgradSig {
   DualSigLaunch fix;          // ... and the dual launch with both halves fixed (NTC 1, TM dg.TM)
 };
 
+// ... and the standalone first-layer wgrad that keeps several blocks of a split in flight
+// (wgrad_halo_body.h DEPTH; wgrad_deep.hip, both input forms chosen inside)
+typedef void (*WgDeepLaunch)(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t s);
+void wgrad_deep_rpv1(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t s);
+
+// The deep instance of a signature (a row per row of the signature table): it replaces the
+// non-pipelined form of WgradSig::alone.  depth 1, alone null: the signature has none.
+struct WgradDeep {
+  int depth;
+  WgDeepLaunch alone;
+};
+const WgradDeep& wgrad_deep_at(int v);
+
 // 1 + index of the signature these args match (0: none), and the table entry
 int wgrad_sig_find(const WgradArgs& a, int MT, int NTT);
 const WgradSig& wgrad_sig_at(int v);

@@ -32,6 +32,18 @@ static_assert(std::is_same<DgSigRpv2::Wg, WgSigRpv2>::value && std::is_same<DgSi
                   std::is_same<DgSigMnist2::Wg, WgSigMnist2>::value,
               "a table row pairs a wgrad signature with its own layer's dgrad");
 
+// the deep instances, row for row of kWgradSigs
+// (the RPV duals' wgrad halves at depths 2 and 3 gained less than their launches' noise bar --
+// the dgrad half is as long -- and the MNIST first layer's unpooled dY has no pooled-chunk
+// stage: docs/ARCHITECTURE.md section 15)
+static const WgradDeep kWgradDeep[] = {
+    {2, wgrad_deep_rpv1}, {1, nullptr}, {1, nullptr}, {1, nullptr}, {1, nullptr},
+};
+static_assert(sizeof(kWgradDeep) / sizeof(kWgradDeep[0]) == sizeof(kWgradSigs) / sizeof(kWgradSigs[0]),
+              "a deep row per signature");
+
+const WgradDeep& wgrad_deep_at(int v) { return kWgradDeep[v - 1]; }
+
 // field by field over WG_GEO_INTS (an unpooled dY never reads dHp / dWp: not compared then)
 static bool wg_sig_matches(const WgradArgs& a, int MT, int NTT, const WgSigVals& v) {
   if ((a.dy_code != nullptr) != (v.pooled != 0) || (a.bslab != nullptr) != (v.bias != 0)) return false;

@@ -469,6 +469,10 @@ class GeometryMixin:
         # The split count above is sized by the GENERIC instance's residency either way, so the
         # slab layout and the reduction order do not depend on this switch.
         a.spec = int(tune("wgrad_spec"))
+        # ... and, where a signature launch has an instance that keeps several blocks of a split in
+        # flight (K.wgrad_depth_variant), its depth: 0 the instance's own, 1 the depth-one kernels
+        # (A/B, bit-identity tests).  Host-only, like spec; S and blocks_per_split do not depend on it.
+        a.depth = int(tune("wgrad_depth"))
         return Wgrad(a, (MT, NTT), S, slab, bslab)
 
     def _wgrad_args(self, xin, width, dy, Cs_dy, N, bias, direct=None):

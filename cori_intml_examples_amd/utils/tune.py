@@ -126,6 +126,10 @@ KNOBS: Tuple[Knob, ...] = (
     Knob("dgrad_spec", 1, EXACT, "dual launches whose co-scheduled dgrad geometry is fixed at compile time "
          "too (csrc/kernels/dual_halo_fix_body.h) where the dgrad signature matches; 0: the dual launch "
          "as without it (tests/test_dgrad_sig.py)"),
+    Knob("wgrad_depth", 0, EXACT, "blocks of a halo wgrad split whose staging loads are in flight at once, in "
+         "the launches that have a deep instance (csrc/kernels/wgrad_deep.hip: the RPV first layer): 0 the "
+         "instance's own depth, 1 the depth-one kernels, d that depth where it is built "
+         "(profiles/wgrad_depth_ab.txt; tests/test_wgrad_depth.py)"),
     # ---------------------------------------------------------------- dense
     Knob("dense_big_wgs", 256, PATH, "workgroups wanted for a large dense layer's forward (one per CU)"),
     Knob("dense_big_minks", 8, PATH, "fewest k-steps per split of a large dense layer's forward"),
