@@ -304,6 +304,11 @@ PYBIND11_MODULE(_kernels, m) {
       .def(py::init([]() { RedTable t; memset(&t, 0, sizeof(t)); return t; }))
       .def_readonly("n", &RedTable::n)
       .def_readonly("nblocks", &RedTable::nblocks)
+      .def("flags", [](const RedTable& t, int i) {
+        // read-only view of what add() decided for descriptor i: (tpe, vec4, tile, blk0)
+        if (i < 0 || i >= t.n) throw std::out_of_range("RedTable descriptor index");
+        return py::make_tuple(t.d[i].tpe, t.d[i].vec4, t.d[i].tile, t.d[i].blk0);
+      })
       .def("owned_blocks", [](const RedTable& t, long long lo, int chunk, int rank) {
         // [b_lo, b_hi): the table blocks some element of which falls in owner chunk `rank` of
         // the bucket starting at flat element lo (the blocks a mode-4 launch must cover) --
@@ -333,8 +338,9 @@ PYBIND11_MODULE(_kernels, m) {
         // traffic (an explicit tpe keeps the scalar path)
         const bool ident = type == RED_BIAS || ((type == RED_FLATW || type == RED_CONVW) && Cin == Cs && ld == Cout);
         d.vec4 = (ident && numel % 4 == 0 && dst_off % 4 == 0 && stride_s % 4 == 0 && tpe <= 0) ? 1 : 0;
-        d.tile = (d.vec4 && type == RED_FLATW && 1024 % Cout == 0 && (1024 / Cout) % 8 == 0 && numel % 1024 == 0)
-                     ? 1 : 0;
+        // (Cout >= 8: update_vec4's backward half splits a row into Cout / 8 vectors of 8 columns)
+        d.tile = (d.vec4 && type == RED_FLATW && Cout >= 8 && 1024 % Cout == 0 && (1024 / Cout) % 8 == 0 &&
+                  numel % 1024 == 0) ? 1 : 0;
         // threads per element (power of 2, <= 64): E = 256 / tpe consecutive elements per
         // workgroup keep each slab-row read >= 16 contiguous bytes; each thread sums its
         // S / tpe partials 8 independent loads at a time

@@ -205,6 +205,7 @@ def test_optimizer_kernel_matches_keras_math(opt):
     """Fused optimizer kernel vs Keras-2.2 update math applied to the SAME gradients,
     over 3 steps (exercises slot state, bias correction, Nadam's schedule)."""
     from cori_intml_examples_amd.ops import reference as R
+    from helpers import param_oracle as PO
     set_random_seed(5)
     g = _build("rpv", "cuda", opt=opt)
     ex = g._executor
@@ -218,6 +219,8 @@ def test_optimizer_kernel_matches_keras_math(opt):
     msched = 1.0
     lr = float(o.lr)
     for t in range(1, 4):
+        prev = [g.store.master[:n].cpu().numpy()] + [s.cpu().numpy() for s in ex.optimizer_state()]
+        ms_prev = msched
         ex.train_step(d, torch.arange(d.n, device=ex.device), 32 * (t - 1), 32)
         torch.cuda.synchronize()
         gr = g.store.grad[:n].cpu().double()
@@ -233,6 +236,12 @@ def test_optimizer_kernel_matches_keras_math(opt):
             R.rmsprop_update(w, gr, s0, lr, o.rho, o.epsilon)
         got = g.store.master[:n].cpu().double()
         assert float((got - w).abs().max()) < 2e-5 * max(1.0, lr * 100), (opt, t)
+        # per element, from the device's own state before the step: the derived bounds of
+        # helpers/param_oracle.py
+        ratio, _ = PO.keras_step_ratio(o, t, prev[0], gr.numpy(), prev[1:], got.numpy(),
+                                       [s.cpu().numpy() for s in ex.optimizer_state()], ms_prev)
+        print("%s step %d: worst per-element error / bound %.3f" % (opt, t, ratio))
+        assert ratio <= 1.0, (opt, t, ratio)
     # bf16 pack mirrors the fp32 master after the update
     bp = ex._plans[(32, "train")]
     assert ex.arena.abs().sum().item() > 0

@@ -18,6 +18,7 @@ from cori_intml_examples_amd.io.keras_h5 import load_model
 from cori_intml_examples_amd.utils import set_random_seed
 
 from helpers import optim_oracle as O
+from helpers import param_oracle as P
 from test_hip_model import _build, _data
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,12 +60,18 @@ def test_kernel_matches_keras_math(name, model, fused, monkeypatch):
     assert len(ex.slots) == NSLOTS[name]
     bound = 2e-5 * max(1.0, 100 * float(o.lr))
     for t in range(1, 4):
+        prev = [m.store.master[:n].cpu().numpy()] + [s.cpu().numpy() for s in ex.optimizer_state()]
         ex.train_step(d, torch.arange(d.n, device=ex.device), 32 * (t - 1), 32)
         torch.cuda.synchronize()
         gr = m.store.grad[:n].cpu().double().numpy()
         assert np.abs(gr).max() > 0
         p, slots = O.step(o.kind, p, gr, slots, t, o)
         got = m.store.master[:n].cpu().double().numpy()
+        # per element, from the device's own state before the step: the derived bounds of
+        # helpers/param_oracle.py
+        ratio, _ = P.keras_step_ratio(o, t, prev[0], gr, prev[1:], got, [s.cpu().numpy() for s in ex.optimizer_state()])
+        print("%s %s fused=%d step %d: worst per-element error / bound %.3f" % (name, model, fused, t, ratio))
+        assert ratio <= 1.0, (name, model, fused, t, ratio)
         errs = [float(np.abs(got - p).max())] + [float(np.abs(s.cpu().double().numpy() - r).max())
                                                  for s, r in zip(ex.optimizer_state(), slots)]
         print("%s %s fused=%d step %d: max |err| master %.3g, slots %s (bound %.3g)" % (
