@@ -6,6 +6,8 @@
 // gradient at pooled resolution; the full-resolution gradient dY is never materialised:
 // consumers rebuild it on load from (dP, argmax code) -- see unpool_load8.
 #pragma once
+#include <type_traits>
+
 #include "args.h"
 
 __device__ __forceinline__ void bwd_through_store(const BwdThrough& t, int b, int y, int x, int c,
@@ -38,31 +40,79 @@ struct BtGeoRt {
 };
 
 // Vectorised form: 8 consecutive channels [c0, c0+8) of output pixel qi (flat index over
-// the previous stage's output grid); one 16-byte load of the saved output, one 16-byte store.
-template <class G = BtGeoRt>
-__device__ __forceinline__ void bwd_through_store8(const BwdThrough& t, size_t qi, int c0, const float* g,
-                                                   uint32_t step) {
-  if (c0 >= G::pCs(t)) return;
-  const size_t o = qi * G::pCs(t) + c0;
+// the previous stage's output grid); one 16-byte load of the saved output, one 16-byte store
+// (bwd_through_store8, below).
+// The two halves of it, for callers that know (qi, c0) long before they have the gradient: the
+// load of the saved output needs nothing the kernel computes, so it can be in flight while the
+// MFMAs run and only arithmetic and the store remain behind them.
+//
+// fetch8: the saved output's 8 values (zeros without a ReLU mask).  Branch-free: the load is
+// always issued, so (qi, c0) must be an in-range chunk -- callers clamp.  (The _at forms take the
+// element offset o = qi * pCs + c0, which store8 computes once for both halves; ALWAYS false: the
+// load sits under the prev_relu test, the form bwd_through_store8 has always had.)
+template <class G, bool ALWAYS>
+__device__ __forceinline__ bf16x8 bwd_through_fetch8_at(const BwdThrough& t, size_t o) {
+  if (ALWAYS) {
+    const bf16x8 v = load_bf16x8(t.prev_out + o);
+    return G::prev_relu(t) ? v : zero_bf16x8();
+  }
   bf16x8 prev = zero_bf16x8();
   if (G::prev_relu(t)) prev = load_bf16x8(t.prev_out + o);
+  return prev;
+}
+template <class G = BtGeoRt>
+__device__ __forceinline__ bf16x8 bwd_through_fetch8(const BwdThrough& t, size_t qi, int c0) {
+  return bwd_through_fetch8_at<G, true>(t, qi * G::pCs(t) + c0);
+}
+
+// finish8: dropout scale, then ReLU mask (prev: fetch8's value), then f2bf and the store.
+// WHOLE: the caller has proved c0 + 8 <= pC (== pCs), no channel test is compiled.  HOIST: the
+// dropout threshold is tested once per chunk instead of around each element's hash.
+// (DROP 1 / 0: the chunk's dropout is known on / off, -1: the threshold is tested per element)
+template <class G, bool WHOLE, int DROP>
+__device__ __forceinline__ bf16x8 bwd_through_mask8(const BwdThrough& t, size_t qi, int c0, const float* g,
+                                                    const bf16x8 prev, uint32_t step) {
   bf16x8 outv;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int c = c0 + k;
     float v = g[k];
-    if (c >= G::pC(t)) {
+    if (!WHOLE && c >= G::pC(t)) {
       v = 0.f;
     } else {
-      if (t.drop_thr)
+      if (DROP > 0 || (DROP < 0 && t.drop_thr))
         v = dropout_keep((uint32_t)(qi * (size_t)G::pC(t) + c), t.seed, t.stream_id, step, t.drop_thr) ? v * t.drop_scale
                                                                                                       : 0.f;
       if (G::prev_relu(t) && !(bf2f(prev[k]) > 0.f)) v = 0.f;
     }
     outv[k] = f2bf(v);
   }
+  return outv;
+}
+template <class G, bool WHOLE, bool HOIST>
+__device__ __forceinline__ void bwd_through_finish8_at(const BwdThrough& t, size_t qi, int c0, size_t o, const float* g,
+                                                       const bf16x8 prev, uint32_t step) {
+  bf16x8 outv;
+  if (!HOIST) outv = bwd_through_mask8<G, WHOLE, -1>(t, qi, c0, g, prev, step);
+  else if (t.drop_thr) outv = bwd_through_mask8<G, WHOLE, 1>(t, qi, c0, g, prev, step);
+  else outv = bwd_through_mask8<G, WHOLE, 0>(t, qi, c0, g, prev, step);
   if (G::wt(t)) st_wt16(t.dy, (unsigned)(o * 2), __builtin_bit_cast(u32x4, outv));
   else *reinterpret_cast<bf16x8*>(t.dy + o) = outv;
+}
+template <class G, bool WHOLE>
+__device__ __forceinline__ void bwd_through_finish8(const BwdThrough& t, size_t qi, int c0, const float* g,
+                                                    const bf16x8 prev, uint32_t step) {
+  bwd_through_finish8_at<G, WHOLE, true>(t, qi, c0, qi * G::pCs(t) + c0, g, prev, step);
+}
+
+// The composition (the load under the prev_relu test, the channel tests, the threshold tested
+// per element: the form every run-time-geometry caller has always had).
+template <class G = BtGeoRt>
+__device__ __forceinline__ void bwd_through_store8(const BwdThrough& t, size_t qi, int c0, const float* g,
+                                                   uint32_t step) {
+  if (c0 >= G::pCs(t)) return;
+  const size_t o = qi * G::pCs(t) + c0;
+  bwd_through_finish8_at<G, false, false>(t, qi, c0, o, g, bwd_through_fetch8_at<G, false>(t, o), step);
 }
 
 // Full-resolution gradient of a max-pooled conv at pixel (y, x), channels [c, c+8), rebuilt

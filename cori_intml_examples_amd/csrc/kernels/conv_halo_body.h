@@ -17,7 +17,7 @@
 //     epilogue with whole n-tiles, and the tile / pass counts of whole blocks.
 // (CV_GEO_INTS / CV_BT_INTS, args.h: the one list of the geometry fields)
 struct CvGeoRt : BtGeoRt {
-  static constexpr bool fixed = false;
+  static constexpr bool fixed = false, epi_pre = false;
   using Div = FastDiv;
 #define F(n) \
   __device__ __forceinline__ static int n(const ConvMMArgs& a) { return a.n; }
@@ -35,6 +35,8 @@ struct CvConstDiv {
 template <class S>
 struct CvGeoFix {
   static constexpr bool fixed = true;
+  // the mode-1 epilogue's ReLU-mask operands are fetched ahead of the MFMAs (the signature's switch)
+  static constexpr bool epi_pre = S::epi_pre;
   using Sig = S;
   using Div = CvConstDiv;
 #define F(n) \
@@ -241,6 +243,31 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   // the table's only reader is the table k loop: a body whose geometry takes the kfast loop
   // (below) does not fill it
   const bool skip_tab = G::fixed && !CS4 && G::kpipe(a) && (Cs & 31) == 0 && !(dbg & 2);
+  // Backward-through masks ahead of the MFMAs (fixed geometry, mode 1, the signature's epi_pre):
+  // the saved-output chunks a wave's copy loop masks with depend on block, wave and lane alone,
+  // so a pass's EPC chunks per lane are fetched (bwd_through_fetch8) before its k loop -- the
+  // first pass's inside the one-batch prologue, behind the weight and halo loads and in front
+  // of the weights' stores, whose in-order vmcnt wait then does not cover them -- and only
+  // arithmetic and the stores are left behind the last MFMA (bwd_through_finish8).  A chunk
+  // past the block (ragged last pass) is clamped to the block's last pixel, as pq_load clamps.
+  constexpr bool epi_pre = G::epi_pre && MODE == 1;
+  constexpr int EPC = epi_pre ? TM * 16 * NTC * 2 / 64 : 1;
+  bf16x8 mk[EPC];
+  auto mk_fetch = [&](int tb) {
+    if constexpr (epi_pre) {
+      using S = typename G::Sig;
+      static_assert(G::onebatch() && S::KS * NTC * 64 <= 8 * 256 && S::Ho % S::R == 0 && S::NT % NTC == 0 &&
+                        S::NT * 16 <= S::pCs && S::pC == S::pCs && (TM * 16 * NTC * 2) % 64 == 0,
+                    "the one-batch prologue; whole blocks, whole n-tiles of real channels, whole copy rounds");
+      const size_t m0 = ((size_t)b * S::Ho + oy0) * S::Wo;
+#pragma unroll
+      for (int i = 0; i < EPC; ++i) {
+        const int c = (tid & 63) + i * 64;
+        const int p = min(tb * 16 + c / (NTC * 2), S::R * S::Wo - 1);
+        mk[i] = bwd_through_fetch8<G>(a.bt, m0 + p, nt0 * 16 + (c % (NTC * 2)) * 8);
+      }
+    }
+  };
   if (onebatch) {
     auto fused = [&](auto wu) {
       constexpr int WU = decltype(wu)::value;
@@ -248,6 +275,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
 #pragma unroll
       for (int u = 0; u < WU; ++u) wv[u] = wload(min(tid + u * 256, nw - 1));
       pq_load(tid);
+      mk_fetch((tid >> 6) * TM);
 #pragma unroll
       for (int u = 0; u < WU; ++u)
         if (tid + u * 256 < nw) wstore(tid + u * 256, wv[u]);
@@ -316,6 +344,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
   float* ep = reinterpret_cast<float*>(xl + (((size_t)R_in * W_in * XP + 7) & ~(size_t)7)) + wave * EPW;
   const size_t qbase = ((size_t)b * G::Hp(a) + (oy0 >> 1)) * G::Wp(a);
   for (int tb = wave * TM; tb < ntiles; tb += 4 * TM) {
+    if (epi_pre && tb != wave * TM) mk_fetch(tb);   // (the first pass's: in the prologue)
     bool rv[TM];
     const bf16* xrow[TM];
 #pragma unroll
@@ -542,17 +571,36 @@ __device__ __forceinline__ void conv_halo_body(const ConvMMArgs& a, const int bx
       }
       __builtin_amdgcn_wave_barrier();
       const int np = max(0, min(TM * 16, npix - tb * 16));
-      for (int c = lane; c < np * cch; c += 64) {
-        const int pr = fcch.div(c), c8 = c - pr * cch;
-        const size_t m = mrow0 + (size_t)(tb * 16 + pr);
-        const bf16x8 val = *reinterpret_cast<const bf16x8*>(epb + pr * LDC + ((c8 ^ (((pr >> 2) << 1) & CHM)) << 3));
-        if (fwd) {
-          *reinterpret_cast<bf16x8*>(a.out + m * G::Cs_out(a) + nt0 * 16 + c8 * 8) = val;
-        } else {
-          float v[8];
+      if constexpr (epi_pre) {
+        // the same chunks in the same order, EPC unrolled rounds; masks from mk_fetch
+        constexpr int NPIX = G::Sig::R * G::Sig::Wo;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = bf2f(val[k]);
-          bwd_through_store8<G>(a.bt, m, nt0 * 16 + c8 * 8, v, step);
+        for (int i = 0; i < EPC; ++i) {
+          const int c = lane + i * 64;
+          const int pr = c / (NTC * 2), c8 = c % (NTC * 2);
+          if (NPIX % (TM * 16) == 0 || tb * 16 + pr < NPIX) {
+            const bf16x8 val =
+                *reinterpret_cast<const bf16x8*>(epb + pr * LDC + ((c8 ^ (((pr >> 2) << 1) & CHM)) << 3));
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = bf2f(val[k]);
+            bwd_through_finish8<G, true>(a.bt, mrow0 + (size_t)(tb * 16 + pr), nt0 * 16 + c8 * 8, v, mk[i], step);
+          }
+        }
+      } else {
+        for (int c = lane; c < np * cch; c += 64) {
+          const int pr = fcch.div(c), c8 = c - pr * cch;
+          const size_t m = mrow0 + (size_t)(tb * 16 + pr);
+          const bf16x8 val =
+              *reinterpret_cast<const bf16x8*>(epb + pr * LDC + ((c8 ^ (((pr >> 2) << 1) & CHM)) << 3));
+          if (fwd) {
+            *reinterpret_cast<bf16x8*>(a.out + m * G::Cs_out(a) + nt0 * 16 + c8 * 8) = val;
+          } else {
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = bf2f(val[k]);
+            bwd_through_store8<G>(a.bt, m, nt0 * 16 + c8 * 8, v, step);
+          }
         }
       }
       __builtin_amdgcn_wave_barrier();

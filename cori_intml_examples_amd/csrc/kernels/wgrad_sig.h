@@ -39,20 +39,24 @@ WG_SIG(WgSigMnist2, 26, 26, 32, 24, 24, 0, 18, 4, 64, 12, 12, true, 5, 48, 26, 8
 // wgrad signature, as executor_hip._dgrad_args and hip_geometry._halo_cfg produce it at default
 // tunes for every batch >= 128 (scripts/plan_dump.py at B = 128 and 256): the conv over the pooled
 // dY with the flipped taps, written through the previous stage's ReLU.  R (rows per block) and TM
-// (m-tiles per wave per pass, dual_pick_tm's choice for R) are part of the signature.
-#define DG_SIG(NAME, WG_, H_, W_, CS_, HO_, WO_, PAD_, KS_, NT_, R_, PH_, PW_, XPIX_, PC_, TM_)                     \
+// (m-tiles per wave per pass, dual_pick_tm's choice for R) are part of the signature.  epi_pre
+// is no geometry but a choice made per instance from its measurement: the epilogue's ReLU-mask
+// operands are fetched ahead of the MFMAs (conv_halo_body.h); false keeps the in-place loads.
+#define DG_SIG(NAME, WG_, H_, W_, CS_, HO_, WO_, PAD_, KS_, NT_, R_, PH_, PW_, XPIX_, PC_, TM_, EPI_)               \
   struct NAME {                                                                                                    \
     using Wg = WG_;                                                                                                \
     static constexpr int H = H_, W = W_, Cs_in = CS_, Ho = HO_, Wo = WO_, KH = 3, KW = 3, stride = 1, pad_t = PAD_, \
                          pad_l = PAD_, in_dil = 1, KS = KS_, NT = NT_, pool = 0, Hp = 0, Wp = 0, Cs_out = 0, R = R_, \
                          in_pH = PH_, in_pW = PW_, xpix = XPIX_, kpipe = 1, pCs = PC_, pC = PC_, prev_relu = 1,     \
                          wt = 1, TM = TM_;                                                                         \
-    static constexpr bool pooled = true;                                                                           \
+    static constexpr bool pooled = true, epi_pre = EPI_;                                                           \
   }
-//      name         wgrad sig    H   W   Cs  Ho  Wo  pad KS  NT R   pH  pW  xpix pC  TM
-DG_SIG(DgSigRpv2, WgSigRpv2, 32, 32, 32, 32, 32, 1, 9, 1, 16, 16, 16, 48, 16, 4);
-DG_SIG(DgSigRpv3, WgSigRpv3, 16, 16, 64, 16, 16, 1, 18, 2, 16, 8, 8, 80, 32, 4);
-DG_SIG(DgSigMnist2, WgSigMnist2, 24, 24, 64, 26, 26, 2, 18, 2, 13, 12, 12, 0, 32, 2);
+// (docs/ARCHITECTURE.md §16: conv2's dual gains 1.5 us with it; conv3's, whose wgrad half binds, and
+// the MNIST one stayed under three noises of their launches and keep the in-place loads)
+//      name         wgrad sig    H   W   Cs  Ho  Wo  pad KS  NT R   pH  pW  xpix pC  TM epi_pre
+DG_SIG(DgSigRpv2, WgSigRpv2, 32, 32, 32, 32, 32, 1, 9, 1, 16, 16, 16, 48, 16, 4, true);
+DG_SIG(DgSigRpv3, WgSigRpv3, 16, 16, 64, 16, 16, 1, 18, 2, 16, 8, 8, 80, 32, 4, false);
+DG_SIG(DgSigMnist2, WgSigMnist2, 24, 24, 64, 26, 26, 2, 18, 2, 13, 12, 12, 0, 32, 2, false);
 
 // ------------------------------------------------------------------------------ host side
 struct DgSigVals {
