@@ -4,6 +4,7 @@
                                         [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
                                         [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
+                                        [--loss NAME[,NAME..]]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -39,6 +40,12 @@ plus ``pool_fwd`` and ``pool_bwd`` per conv stage, whose conv kernels run un-poo
 pooling layer in the Flatten's place: ``gpool_fwd`` and ``gpool_bwd``, and a Dense(128) over 64
 inputs instead of 4096).
 
+``--loss NAME[,NAME..]`` adds ``<name>/unfused-head`` (the default model built under
+``INTML_TUNE=fuse_head=0``: ``dense_epi`` as a launch of its own, then the first head kernel) and one
+``<name>/loss-<NAME>`` model per name (that structure with the ``loss_head`` launch in the head's
+place; ``NAME@N`` puts the loss on a sigmoid output of N columns, ``binary_crossentropy@8`` being the
+multi-label head).  The difference between those is the cost of the second head kernel.
+
 ``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
 them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
 ``<name>/weighted-data`` (the default model on sample-weighted data: the weighted head instances, no new
@@ -67,6 +74,7 @@ REPLAY = 32
 UNFUSED = "fuse_optim=0,early_reduce=0"
 PERLAYER = "conv_stack=0,fuse_head=0"
 UNSTACKED = "conv_stack=0"
+UNFUSED_HEAD = "fuse_head=0"
 
 
 def make_opt(name, **kw):
@@ -74,7 +82,7 @@ def make_opt(name, **kw):
 
 
 def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
-             metrics=None, weighted_metrics=None):
+             metrics=None, weighted_metrics=None, losses=()):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
     "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
@@ -106,6 +114,14 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
             out.append((nm + "/" + act, nm, {}, None, 0.0, act))
+        if losses:
+            # the loss head's structure with the first head kernel: the default model under fuse_head=0
+            out.append((nm + "/unfused-head", nm, {}, UNFUSED_HEAD, 0.0, "relu"))
+        for ls in losses:
+            # NAME@N: the loss on a sigmoid output of N columns (binary_crossentropy@8: the multi-label head)
+            name, _, cols = ls.partition("@")
+            out.append((nm + "/loss-" + ls, nm, {}, None, 0.0, "relu",
+                        dict({"loss": name}, **({"outputs": int(cols)} if cols else {}))))
     return out
 
 
@@ -141,6 +157,9 @@ def main():
     ap.add_argument("--pool", choices=["max", "avg"], default="max", help="time the model with AveragePooling2D layers")
     ap.add_argument("--global-pool", choices=["avg", "max"], default=None,
                     help="time the model with a global pooling layer in the Flatten's place")
+    ap.add_argument("--loss", default="", metavar="NAME[,NAME]",
+                    help="time the model with these Keras losses in binary_crossentropy's place (the loss head), "
+                         "and the default model under fuse_head=0 (the same structure with the first head kernel)")
     ap.add_argument("--metrics", default="", help="comma-separated compile metrics to time (e.g. accuracy,auc)")
     ap.add_argument("--weighted-metrics", default="", help="comma-separated weighted_metrics to time, on weighted data")
     ap.add_argument("--eval-samples", type=int, default=0, help="also time an evaluation pass over this many samples")
@@ -148,7 +167,7 @@ def main():
     split = lambda t: [n for n in t.split(",") if n]
     var = [v if len(v) == 7 else v + ({},) for v in
            variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
-                    split(a.metrics), split(a.weighted_metrics))]
+                    split(a.metrics), split(a.weighted_metrics), split(a.loss))]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -168,7 +187,8 @@ def main():
                             **({"activation": act} if not act.startswith("relu") else {}),
                             **{k: v for k, v in extra.items() if k != "weighted_data"})
         ex = m._executor
-        d = ex.upload(x, y, w) if extra.get("weighted_data") else ex.upload(x, y)
+        yv = y if extra.get("outputs", 1) == 1 else (rs.rand(bs * REPLAY, extra["outputs"]) > 0.5).astype(np.float32)
+        d = ex.upload(x, yv, w) if extra.get("weighted_data") else ex.upload(x, yv)
         keys[nm] = (bs, "train", "w") if extra.get("weighted_data") else (bs, "train")
         perm = torch.arange(d.n, device=ex.device)
         runs[nm] = (m, ex, d, perm)

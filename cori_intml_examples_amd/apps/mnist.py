@@ -47,13 +47,13 @@ def load_data(synthetic_ok: bool = True, n_train: int = 60000, n_test: int = 100
 
 def build_model(h1=4, h2=8, h3=32, dropout=0.5, optimizer="Adadelta", device=None, use_horovod=False,
                 l2=0.0, activation="relu", batch_norm=False, pool="max", global_pool=None,
-                metrics=None, weighted_metrics=None):
+                metrics=None, weighted_metrics=None, loss=None):
     """Sequential CNN of ``mnist.py:44-59`` compiled with CCE + accuracy.  ``l2`` > 0: an l2 kernel
     regularizer on every Conv2D / Dense.  ``activation``: the hidden activation of every Conv2D / Dense.
     ``batch_norm``: a BatchNormalization between every hidden Conv2D / Dense and its activation.
     ``pool``: "max" | "avg", the 2x2 pooling layer.  ``global_pool``: None | "avg" | "max", a global
-    pooling layer in the Flatten's place."""
+    pooling layer in the Flatten's place.  ``loss``: a Keras loss name in categorical_crossentropy's place."""
     return mnist_cnn(h1=h1, h2=h2, h3=h3, dropout=dropout, optimizer=optimizer, n_classes=n_classes,
                      input_shape=(img_rows, img_cols, 1), use_horovod=use_horovod, device=device, l2=l2,
                      metrics=metrics, weighted_metrics=weighted_metrics,
-                     activation=activation, batch_norm=batch_norm, pool=pool, global_pool=global_pool)
+                     activation=activation, batch_norm=batch_norm, pool=pool, global_pool=global_pool, loss=loss)

@@ -42,7 +42,7 @@ def load_dataset(path: str, n_train: int = N_TRAIN, n_valid: int = N_VALID, n_te
 
 def build_model(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam",
                 lr=0.001, use_horovod=False, device=None, l2=0.0, activation="relu", batch_norm=False, pool="max",
-                global_pool=None, metrics=None, weighted_metrics=None):
+                global_pool=None, metrics=None, weighted_metrics=None, loss=None):
     """Functional CNN ``'RPVClassifier'`` (``rpv.py:38-71``): ``[Conv3x3 same+ReLU,
     MaxPool2]`` per conv size, Dropout, Flatten, ``[Dense+ReLU, Dropout]`` per fc size,
     Dense(1, sigmoid); BCE + accuracy; optimizer by name with ``lr``, Horovod-wrapped
@@ -50,11 +50,11 @@ def build_model(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5
     ``activation``: the hidden activation of every Conv2D / Dense instead of ReLU.
     ``batch_norm``: a BatchNormalization between every hidden Conv2D / Dense and its activation.
     ``pool``: "max" | "avg", the 2x2 pooling layers.  ``global_pool``: None | "avg" | "max", a global
-    pooling layer in the Flatten's place."""
+    pooling layer in the Flatten's place.  ``loss``: a Keras loss name in binary_crossentropy's place."""
     return rpv_cnn(tuple(input_shape), conv_sizes=list(conv_sizes), fc_sizes=list(fc_sizes), dropout=dropout,
                    optimizer=optimizer, lr=lr, use_horovod=use_horovod, device=device, l2=l2,
                    metrics=metrics, weighted_metrics=weighted_metrics,
-                   activation=activation, batch_norm=batch_norm, pool=pool, global_pool=global_pool)
+                   activation=activation, batch_norm=batch_norm, pool=pool, global_pool=global_pool, loss=loss)
 
 
 def train_model(model, train_input, train_labels, valid_input, valid_labels, batch_size, n_epochs,

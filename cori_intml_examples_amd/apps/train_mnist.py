@@ -29,6 +29,9 @@ def build_parser():
     p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
     p.add_argument("--global-pool", choices=["avg", "max"], default=None,
                    help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
+    p.add_argument("--loss", default=None, metavar="NAME",
+                   help="a Keras loss name in categorical_crossentropy's place (mse, mae, msle, logcosh, hinge, "
+                        "squared_hinge, categorical_hinge, kld, poisson)")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--valid-frac", type=float, default=0.17)
@@ -54,7 +57,7 @@ def main(argv=None):
     model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout,
                       optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
                       use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm,
-                      pool=a.pool, global_pool=a.global_pool, metrics=parse_metric_list(a.metrics),
+                      pool=a.pool, global_pool=a.global_pool, loss=a.loss, metrics=parse_metric_list(a.metrics),
                       weighted_metrics=parse_metric_list(a.weighted_metrics))
     cbs = []
     if hvd.size() > 1:

@@ -50,6 +50,9 @@ def build_parser():
     p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
     p.add_argument("--global-pool", choices=["avg", "max"], default=None,
                    help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
+    p.add_argument("--loss", default=None, metavar="NAME",
+                   help="a Keras loss name in binary_crossentropy's place (mse, mae, msle, logcosh, hinge, "
+                        "squared_hinge, categorical_hinge, kld, poisson)")
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--n-epochs", type=int, default=4)
     p.add_argument("--fom", choices=["best", "last"])
@@ -106,7 +109,7 @@ def main(argv=None):
                         dropout=args.dropout,
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
                         use_horovod=True, l2=args.l2, activation=args.activation,
-                        batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool,
+                        batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool, loss=args.loss,
                         metrics=parse_metric_list(args.metrics),
                         weighted_metrics=parse_metric_list(args.weighted_metrics))
     if hvd.rank() == 0:

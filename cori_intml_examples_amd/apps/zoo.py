@@ -98,13 +98,14 @@ def fom_from_history(history, name: str, mode: str) -> float:
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
               n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu",
-              batch_norm=False, pool="max", global_pool=None, metrics=None, weighted_metrics=None, l2=0.0):
+              batch_norm=False, pool="max", global_pool=None, metrics=None, weighted_metrics=None, loss=None, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer.  ``global_pool``: None |
     "avg" | "max", a global pooling layer in the Flatten's place (behind the Dropout: the plan wants
-    the conv stage's dropout ahead of it)."""
+    the conv stage's dropout ahead of it).  ``loss``: a Keras loss name of the README's "Losses"
+    table in categorical_crossentropy's place (None: the reference's loss)."""
     reg = _kernel_l2(l2)
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     m = Sequential(device=device)
@@ -117,18 +118,21 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
         m.add(layer)
     m.add(Dropout(dropout if dropout2 is None else dropout2))
     m.add(Dense(n_classes, activation="softmax", **reg))
-    m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="categorical_crossentropy", **_metric_lists(metrics, weighted_metrics))
+    m.compile(optimizer=_opt(optimizer, lr, use_horovod), loss=loss or "categorical_crossentropy", **_metric_lists(metrics, weighted_metrics))
     return m
 
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
             use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max", global_pool=None,
-            metrics=None, weighted_metrics=None, l2=0.0):
+            metrics=None, weighted_metrics=None, loss=None, outputs=1, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer of every conv block.
-    ``global_pool``: None | "avg" | "max", a global pooling layer in the Flatten's place."""
+    ``global_pool``: None | "avg" | "max", a global pooling layer in the Flatten's place.
+    ``loss``: a Keras loss name of the README's "Losses" table in binary_crossentropy's place
+    (None: the reference's loss).  ``outputs``: the sigmoid output's columns (1: the reference's
+    model; more: a multi-label head)."""
     reg = _kernel_l2(l2)
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     inputs = Input(shape=input_shape)
@@ -141,22 +145,23 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
     for f in fc_sizes:
         h = _chain(h, _hidden(Dense, f, **hid))
         h = Dropout(dropout)(h)
-    outputs = Dense(1, activation="sigmoid", **reg)(h)
+    outputs = Dense(outputs, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
-    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy",
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss=loss or "binary_crossentropy",
                   **_metric_lists(metrics, weighted_metrics))
     return model
 
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
                    use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max",
-                   global_pool=None, metrics=None, weighted_metrics=None):
+                   global_pool=None, metrics=None, weighted_metrics=None, loss=None):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: accepted for symmetry with the other builders (this model's
     convs are strided, it has no 2x2 pooling layer).  ``global_pool``: None | "avg" | "max", a
-    global pooling layer in the Flatten's place: "avg" removes the 65,536-row Dense kernel."""
+    global pooling layer in the Flatten's place: "avg" removes the 65,536-row Dense kernel.
+    ``loss``: a Keras loss name in binary_crossentropy's place (None: the reference's loss)."""
     _pool(pool)
     hid = dict(activation=activation, batch_norm=batch_norm)
     h = inputs = Input(shape=input_shape)
@@ -166,6 +171,6 @@ def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2
     h = _chain(h, _hidden(Dense, h5, **hid))
     outputs = Dense(1, activation="sigmoid")(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVClassifier", device=device)
-    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy",
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss=loss or "binary_crossentropy",
                   **_metric_lists(metrics, weighted_metrics))
     return model

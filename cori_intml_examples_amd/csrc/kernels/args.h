@@ -398,6 +398,16 @@ struct HeadArgs {
   // wb != null: the weighted loss (head_kernel<.., true>).  Row m's sample weight is wb[m] (the
   // batch gathered by the prologue) or, with yidx, dataset row yidx[m] of st->data_w
   const float* wb = nullptr;
+  // loss_head_kernel only (loss_head.hip): the row loss, a LOSS_* code; head_kernel ignores it
+  // (its loss follows from act)
+  int loss = 0;
+};
+
+// Loss codes of loss_head_kernel (HeadArgs::loss); every one goes with act 0 / 1 / 2 except
+// LOSS_BCE (the multi-label binary_crossentropy), which is a sigmoid head's
+enum HeadLoss : int {
+  LOSS_MSE = 0, LOSS_MAE = 1, LOSS_MSLE = 2, LOSS_LOGCOSH = 3, LOSS_HINGE = 4, LOSS_SQ_HINGE = 5,
+  LOSS_CAT_HINGE = 6, LOSS_KLD = 7, LOSS_POISSON = 8, LOSS_BCE = 9, LOSS_COUNT = 10
 };
 
 struct GatherArgs {

@@ -35,6 +35,7 @@ void launch_dense_epi(const DenseEpiArgs& a, hipStream_t s);
 int dense_groups(int M, int NT, int KS);
 bool dense_big(int NT, int KS);
 void launch_head(const HeadArgs& a, hipStream_t s);
+void launch_loss_head(const HeadArgs& a, hipStream_t s);
 bool launch_dual_halo(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, int splits,
                       const DualExtra& x, hipStream_t s);
 bool launch_dense_bwd_dual(const WgradArgs& wa, int ktw, int ntt, int splits, const DenseFwdArgs& da,
@@ -187,7 +188,19 @@ PYBIND11_MODULE(_kernels, m) {
       RW(HeadArgs, flat_C) RW(HeadArgs, flat_Cs) PTR(HeadArgs, w) PTR(HeadArgs, bias) PTR(HeadArgs, y)
       RW(HeadArgs, act) RW(HeadArgs, training) RW(HeadArgs, inv_bs) PTR(HeadArgs, st) PTR(HeadArgs, probs)
       PTR(HeadArgs, wslab) PTR(HeadArgs, bslab) RW(HeadArgs, bt) RW(HeadArgs, epi) PTR(HeadArgs, ts)
-      PTR(HeadArgs, yidx) RW(HeadArgs, generic) PTR(HeadArgs, wb);
+      PTR(HeadArgs, yidx) RW(HeadArgs, generic) PTR(HeadArgs, wb) RW(HeadArgs, loss);
+  // loss codes of loss_head (HeadArgs.loss)
+  m.attr("LOSS_MSE") = (int)LOSS_MSE;
+  m.attr("LOSS_MAE") = (int)LOSS_MAE;
+  m.attr("LOSS_MSLE") = (int)LOSS_MSLE;
+  m.attr("LOSS_LOGCOSH") = (int)LOSS_LOGCOSH;
+  m.attr("LOSS_HINGE") = (int)LOSS_HINGE;
+  m.attr("LOSS_SQ_HINGE") = (int)LOSS_SQ_HINGE;
+  m.attr("LOSS_CAT_HINGE") = (int)LOSS_CAT_HINGE;
+  m.attr("LOSS_KLD") = (int)LOSS_KLD;
+  m.attr("LOSS_POISSON") = (int)LOSS_POISSON;
+  m.attr("LOSS_BCE") = (int)LOSS_BCE;
+  m.attr("LOSS_COUNT") = (int)LOSS_COUNT;
 
 
   py::class_<GatherArgs>(m, "GatherArgs")
@@ -419,6 +432,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("dense_big", &dense_big, "dense_fwd uses the large-weight LDS path for (NT, KS)");
   m.def("dense_epi", [](const DenseEpiArgs& a, uintptr_t s) { launch_dense_epi(a, S(s)); check_last("dense_epi"); });
   m.def("head", [](const HeadArgs& a, uintptr_t s) { launch_head(a, S(s)); check_last("head"); });
+  m.def("loss_head", [](const HeadArgs& a, uintptr_t s) { launch_loss_head(a, S(s)); check_last("loss_head"); });
   m.def("prologue", [](const PrologueArgs& a, const PackTable& t, uintptr_t s) {
     launch_prologue(a, t, S(s)); check_last("prologue"); });
   m.def("gather_gx", &gather_gx);

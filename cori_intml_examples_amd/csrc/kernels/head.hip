@@ -9,17 +9,9 @@
 //   dropout / ReLU masks (bwd_through_store: dense dH, or the flattened conv's pooled dP).
 // N (classes) <= 16, so the head is a handful of dot products per row: one wave per row,
 // K split across the 64 lanes, cross-lane shuffle reductions.
-#include "bwd_through.h"
+#include "head_common.h"
 
-// Keras' probability clip (tf.clip_by_value) propagates a NaN; fminf/fmaxf would replace it
-// by a bound and turn a diverged model's loss into a finite value
-__device__ __forceinline__ float clip_nan(float q, float lo, float hi) {
-  return q != q ? q : fminf(fmaxf(q, lo), hi);
-}
-
-#define HEAD_RB 4
 #define HEAD_EPI_MAX 1024   // widest previous dense whose epilogue the head absorbs
-#define HEAD_W_LDS 2048     // head weights staged in LDS up to this many floats
 
 // dense_epilogue_kernel's value for (m, n): the same 4-way interleaved split order
 // (bit-identical), then bias, ReLU, dropout.
@@ -72,22 +64,6 @@ __device__ __forceinline__ float dense_epi_group(const DenseEpiArgs& e, int m, i
   for (int jj = 0; jj < 16; ++jj)
     if (jj >= jn && sg + 4 * jj < e.splits) a0 += v[jj];
   return a0 + a1;
-}
-
-// 16-lane group reductions (lanes 0..15 of a wave; xor offsets < 16 stay inside the group)
-__device__ __forceinline__ float grp16_sum(float v) {
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-// max value and its lowest index (the serial loop's strict '>' keeps the first maximum)
-__device__ __forceinline__ void grp16_argmax(float& v, int& i) {
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off);
-    const int oi = __shfl_xor(i, off);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
 }
 
 // Softmax + Keras categorical_crossentropy (clip of the renormalised probabilities) and its
@@ -177,33 +153,11 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
   const bool fused = a.epi.part != nullptr;
   // the rows' targets and the bias too (read by the serial loss code below)
   __shared__ float ysh[RB][16], bsh[16];
-  if (tid < 16) bsh[tid] = (a.bias && tid < a.N) ? a.bias[tid] : 0.f;
-  if (tid >= 64 && tid < 64 + RB * 16) {
-    const int rl = (tid - 64) >> 4, n = (tid - 64) & 15;
-    const int m = row0 + rl;
-    const bool ok = a.y && n < a.N && m < a.M;
-    // (prologue-free step: the targets' dataset row, recorded by the conv stack)
-    const float* yr = a.yidx ? reinterpret_cast<const float*>(a.st->data_y) + (size_t)a.yidx[ok ? m : 0] * a.st->data_C
-                             : a.y + (size_t)m * a.N;
-    ysh[rl][n] = ok ? yr[n] : 0.f;
-  }
-  // the rows' weights, and nnz counted by every workgroup itself over all M weights (ballot +
-  // popcount: an exact integer, the same in every workgroup; no float atomics, no
-  // cross-workgroup wait).  Read after the barriers below.
+  HEAD_STAGE_TARGETS(RB);
+  // the rows' weights and the batch's nnz (head_common.h).  Read after the barriers below.
   __shared__ float wrow[RB];
   __shared__ int nnz_s[4];
-  if constexpr (WT) {
-    const float* dw = a.yidx ? reinterpret_cast<const float*>(a.st->data_w) : a.wb;
-    int cnt = 0;
-    for (int m0 = 0; m0 < a.M; m0 += 256) {
-      const int m = m0 + tid;
-      float wv = 0.f;
-      if (m < a.M) wv = !dw ? 1.f : (a.yidx ? dw[a.yidx[m]] : dw[m]);
-      cnt += __popcll(__ballot(wv != 0.f));
-      if (m >= row0 && m < row0 + RB) wrow[m - row0] = wv;   // (rows >= M: 0)
-    }
-    if (lane == 0) nnz_s[wave] = cnt;
-  }
+  if constexpr (WT) head_stage_weights<RB>(a, row0, tid, wrow, nnz_s);
   bool done_epi = false;
   if constexpr (RB == 1) {
    if (fused && !a.generic && a.epi.splits <= 32 && a.epi.Ns <= 128) {
@@ -298,42 +252,14 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     __threadfence_block();
     __syncthreads();
   }
-  if (a.st && blockIdx.x == 0 && tid == 0) {
-    // advance the data cursor the step prologue gathered from (it must not move while
-    // prologue workgroups read it) and mark the weight packs fresh (this step's prologue
-    // re-packed them if an optimizer ran; the next optimizer marks them stale again)
-    if (a.training) a.st->pos += a.M;
-    else a.st->eval_pos += a.M;
-    a.st->packs_stale = 0;
-  }
+  HEAD_ADVANCE_CURSOR();
 
   HEAD_STAMP(1);
   if (!fused) __syncthreads();   // (the fused path's barriers already cover wsh / ysh / bsh)
   float wf = 1.f;                // this wave's row factor w_i * (M / nnz)
-  if constexpr (WT) {
-    const int nnz = max((nnz_s[0] + nnz_s[1]) + (nnz_s[2] + nnz_s[3]), 1);
-    wf = wrow[rw] * ((float)a.M / (float)nnz);
-  }
+  if constexpr (WT) wf = head_weight_factor<RB>(a, rw, wrow, nnz_s);
   float z[NM];
-#pragma unroll
-  for (int n = 0; n < NM; ++n) z[n] = 0.f;
-  if (row < a.M && row_wave) {
-    const bf16* hr = a.h + (size_t)row * a.Ks;
-    for (int k = lane; k < a.K; k += 64) {
-      const int kp = a.flat_C ? flat_keras_to_padded(k, a.flat_C, a.flat_Cs) : k;
-      const float hv = fused ? bf2f(hs[rw][kp]) : bf2f(hr[kp]);
-#pragma unroll
-      for (int n = 0; n < NM; ++n)
-        if (n < N) z[n] += hv * (wlds ? wsh[k * N + n] : a.w[(size_t)k * N + n]);
-    }
-  }
-  // the NM chains unconditionally (z[n >= N] is 0) and interleaved: 6 dependent cross-lane
-  // rounds instead of N guarded chains of 6 (each chain's order is unchanged)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int n = 0; n < NM; ++n) z[n] += __shfl_xor(z[n], off);
-  }
+  HEAD_LOGITS(row < a.M && row_wave, fused ? bf2f(hs[rw][kp]) : bf2f(hr[kp]));
   HEAD_STAMP(7);
   if constexpr (RB == 1 && NM == 1) {
     // Binary head of a fused hidden dense layer (the RPV step): only dz gates the backward,
@@ -369,12 +295,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
           float ls = fmaxf(lg, 0.f) - lg * yv + log1pf(expf(-fabsf(lg)));
           if constexpr (WT) ls *= wf;
           const float cs = (rintf(p) == yv) ? 1.f : 0.f;
-          long long* slot = a.st->metric_slots[blockIdx.x & 15];
-          const bool loss_ok = isfinite(ls) && fabsf(ls) < 1073741824.f;
-          if (loss_ok) atomicAdd((unsigned long long*)&slot[0], (unsigned long long)llrint((double)ls * 4294967296.0));
-          else atomicAdd((unsigned long long*)&slot[3], 1ull);
-          atomicAdd((unsigned long long*)&slot[1], (unsigned long long)llrintf(cs));
-          atomicAdd((unsigned long long*)&slot[2], 1ull);
+          head_metric_commit(a, ls, cs, 1);
         }
         HEAD_STAMP(4);
         return;
@@ -491,53 +412,18 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
   if (tid == 0 && a.y && a.st) {
     float ls = 0.f, cs = 0.f;
     for (int r = 0; r < rows_here; ++r) { ls += met[r][0]; cs += met[r][1]; }
-    // per-workgroup sums in a fixed row order, then order-independent integer atomics
-    // spread over 16 slots: 128 workgroups on one address serialise at the L2 (~2 us)
-    long long* slot = a.st->metric_slots[blockIdx.x & 15];
-    // a non-finite loss (diverged trial) or one beyond the fixed-point range (|sum| >= 2^30
-    // per workgroup) cannot be converted: count it in the slot's spare word instead, and the
-    // host reports the loss as NaN (llrint of NaN/inf is undefined and would read as finite)
-    const bool loss_ok = isfinite(ls) && fabsf(ls) < 1073741824.f;
-    if (loss_ok) atomicAdd((unsigned long long*)&slot[0], (unsigned long long)llrint((double)ls * 4294967296.0));
-    else atomicAdd((unsigned long long*)&slot[3], 1ull);
-    atomicAdd((unsigned long long*)&slot[1], (unsigned long long)llrintf(cs));
-    atomicAdd((unsigned long long*)&slot[2], (unsigned long long)rows_here);
+    // per-workgroup sums in a fixed row order, then the integer atomics
+    head_metric_commit(a, ls, cs, rows_here);
   }
   HEAD_STAMP(4);
   if (!a.training) return;
 
-  float* ws = a.wslab + (size_t)blockIdx.x * a.K * N;
-  for (int idx = tid; idx < a.K * N; idx += 256) {
-    const int k = idx / N, n = idx - (idx / N) * N;
-    const int kp = a.flat_C ? flat_keras_to_padded(k, a.flat_C, a.flat_Cs) : k;
-    float s = 0.f;
-    for (int rl = 0; rl < rows_here; ++rl)
-      s += (fused ? bf2f(hs[rl][kp]) : bf2f(a.h[(size_t)(row0 + rl) * a.Ks + kp])) * dz_s[rl][n];
-    ws[idx] = s;
-  }
-  if (tid < N && a.bslab) {
-    float s = 0.f;
-    for (int rl = 0; rl < rows_here; ++rl) s += dz_s[rl][tid];
-    a.bslab[(size_t)blockIdx.x * N + tid] = s;
-  }
+  HEAD_STORE_SLABS(fused ? bf2f(hs[rl][kp]) : bf2f(a.h[(size_t)(row0 + rl) * a.Ks + kp]));
   HEAD_STAMP(5);
   const BwdThrough& t = a.bt;
-  if (t.dy) {
-    const int width = t.pH * t.pW * t.pCs;
-    for (int idx = tid; idx < rows_here * width; idx += 256) {
-      const int rl = idx / width;
-      const int kp = idx - rl * width;
-      const int y = kp / (t.pW * t.pCs);
-      const int rem = kp - y * t.pW * t.pCs;
-      const int x = rem / t.pCs;
-      const int c = rem - x * t.pCs;
-      float gs = 0.f;
-      if (c < t.pC) {
-        const int k = (y * t.pW + x) * t.pC + c;
-        for (int n = 0; n < N; ++n) gs += dz_s[rl][n] * (wlds ? wsh[k * N + n] : a.w[(size_t)k * N + n]);
-      }
+  // (the previous stage IS the fused dense layer: its saved output row is in LDS)
+  HEAD_STORE_DH(
       if (fused && t.prev_out == a.epi.out && t.pH == 1 && t.pW == 1) {
-        // the previous stage IS the fused dense layer: its saved output row is in LDS
         if (c >= t.pCs) continue;
         if (c >= t.pC) {
           gs = 0.f;
@@ -551,9 +437,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
         t.dy[(size_t)(row0 + rl) * t.pCs + c] = f2bf(gs);
         continue;
       }
-      bwd_through_store(t, row0 + rl, y, x, c, gs, step);
-    }
-  }
+  );
   HEAD_STAMP(6);
 }
 

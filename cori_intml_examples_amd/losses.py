@@ -45,7 +45,50 @@ def sparse_categorical_crossentropy(y_true, y_pred):
     return categorical_crossentropy(onehot, yp)
 
 
+def mean_absolute_error(y_true, y_pred):
+    return np.abs(_np(y_pred) - _np(y_true)).mean(axis=-1)
+
+
+def mean_squared_logarithmic_error(y_true, y_pred):
+    a = np.log(np.maximum(_np(y_pred), EPSILON) + 1.0)
+    b = np.log(np.maximum(_np(y_true), EPSILON) + 1.0)
+    return ((a - b) ** 2).mean(axis=-1)
+
+
+def logcosh(y_true, y_pred):
+    x = np.abs(_np(y_pred) - _np(y_true))
+    return (x + np.log1p(np.exp(-2.0 * x)) - np.log(2.0)).mean(axis=-1)
+
+
+def hinge(y_true, y_pred):
+    return np.maximum(1.0 - _np(y_true) * _np(y_pred), 0.0).mean(axis=-1)
+
+
+def squared_hinge(y_true, y_pred):
+    return (np.maximum(1.0 - _np(y_true) * _np(y_pred), 0.0) ** 2).mean(axis=-1)
+
+
+def categorical_hinge(y_true, y_pred):
+    yt, yp = _np(y_true), _np(y_pred)
+    pos = (yt * yp).sum(axis=-1)
+    neg = ((1.0 - yt) * yp).max(axis=-1)
+    return np.maximum(0.0, neg - pos + 1.0)
+
+
+def kullback_leibler_divergence(y_true, y_pred):
+    yt, yp = np.clip(_np(y_true), EPSILON, 1), np.clip(_np(y_pred), EPSILON, 1)
+    return (yt * np.log(yt / yp)).sum(axis=-1)
+
+
+def poisson(y_true, y_pred):
+    yt, yp = _np(y_true), _np(y_pred)
+    return (yp - yt * np.log(yp + EPSILON)).mean(axis=-1)
+
+
 mse = MSE = mean_squared_error
+mae = MAE = mean_absolute_error
+msle = MSLE = mean_squared_logarithmic_error
+kld = KLD = kullback_leibler_divergence
 
 
 def get(identifier):

@@ -41,10 +41,15 @@ from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin
-from .plan import Plan
+from .plan import Plan, binary_accuracy_head, classic_head
 from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
                            cdiv, check_bucket_cover, defer_after_readers, dropout_pair, gpool_geometry,
                            splice_bucket_launches, stage_geometry, stream_program)
+
+# canonical loss name -> the loss-code constant of the kernels module (HeadArgs.loss, loss_head.hip)
+LOSS_CODES = {"mse": "LOSS_MSE", "mae": "LOSS_MAE", "msle": "LOSS_MSLE", "logcosh": "LOSS_LOGCOSH",
+              "hinge": "LOSS_HINGE", "squared_hinge": "LOSS_SQ_HINGE", "categorical_hinge": "LOSS_CAT_HINGE",
+              "kld": "LOSS_KLD", "poisson": "LOSS_POISSON", "binary_crossentropy": "LOSS_BCE"}
 
 BF16 = torch.bfloat16
 # views of the optimizer-kind table (optim/optimizers.py KINDS); STANDALONE_KINDS: see
@@ -194,6 +199,11 @@ class HipExecutor(Executor):
     # ------------------------------------------------------------------ geometry
     def _build_geometry(self):
         inp, self.convs, self.denses, self.head_src, self.head_act = stage_geometry(self.plan)
+        hd = self.plan.head
+        # the second head kernel (loss_head.hip) runs every pair the first one does not; it reads
+        # the last hidden stage's stored output, never a split-K epilogue
+        self.loss_head = not classic_head(hd.activation, hd.loss, hd.N)
+        self.acc_div = float(hd.N) if self.loss_head and hd.N > 1 and binary_accuracy_head(hd.loss, hd.N) else 1.0
         self.in_C, self.in_Cs, self.in_H, self.in_W = inp.C, inp.Cs, inp.H, inp.W
         # the global pooling stage behind the last conv stage (None: the model has none)
         self.gpool = gpool_geometry(self.plan, self.convs[-1].out_src) if self.convs else None
@@ -493,7 +503,9 @@ class HipExecutor(Executor):
         v = self.state.view(torch.int64)[o:o + 4 * self.K.STEP_STATE_METRIC_SLOTS].view(-1, 4).sum(0).tolist()
         # v[3] counts head workgroups whose loss was non-finite or out of fixed-point range:
         # the loss is then NaN (sticky until reset_metrics), never a finite garbage value
-        return [v[0] / 4294967296.0 if v[3] == 0 else float("nan"), float(v[1]), float(v[2])]
+        # (v[1]: correct rows, or correct ELEMENTS of a multi-column binary_accuracy head -- the
+        # loss head's integer count -- divided by the columns here so that cs / rows is the accuracy)
+        return [v[0] / 4294967296.0 if v[3] == 0 else float("nan"), float(v[1]) / self.acc_div, float(v[2])]
 
     def reset_metrics(self):
         o = self.K.STEP_STATE_METRICS_OFFSET // 8
@@ -1004,7 +1016,7 @@ class BatchPlan(GeometryMixin):
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head") and g.plain):
+                    and tune("fuse_head") and g.plain and not ex.loss_head):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
@@ -1049,7 +1061,11 @@ class BatchPlan(GeometryMixin):
         # (a fused dense layer + head launch -- 16-wave K-slice tiles, the last arriving workgroup
         # of each row group running the head -- measured 15.6 us against 13.3 us for the split-K
         # dense launch + this head launch at RPV B=128, and was removed in round 5)
-        self._add("head", lambda s, a=h: K.head(a, s), head=h)
+        if ex.loss_head:
+            h.loss = getattr(K, LOSS_CODES[hd.loss])
+            self._add("loss_head", lambda s, a=h: K.loss_head(a, s), head=h)
+        else:
+            self._add("head", lambda s, a=h: K.head(a, s), head=h)
         if self.roc:
             # directly behind the head, on the main stream, inside the captured step
             r = ex._roc_args()

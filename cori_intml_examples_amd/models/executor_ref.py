@@ -28,7 +28,7 @@ from ..ops.rng import dropout_keep
 from ..optim.optimizers import clip_pair
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
-from .plan import Plan
+from .plan import Plan, binary_accuracy_head, classic_head
 
 
 class RefExecutor(Executor):
@@ -39,6 +39,10 @@ class RefExecutor(Executor):
         self.slots: List[torch.Tensor] = [torch.zeros(store.capacity) for _ in range(n_slots)]
         self.m_schedule = 1.0
         self._acc = torch.zeros(3, dtype=torch.float64)
+        # binary_accuracy of a multi-column output counts correct ELEMENTS: the divisor per row
+        hd = plan.head
+        self._acc_div = float(hd.N) if (hd.N > 1 and binary_accuracy_head(hd.loss, hd.N)
+                                        and not classic_head(hd.activation, hd.loss, hd.N)) else 1.0
         self._last = (0.0, 0.0)
         self.emulate_bf16 = bool(tune("ref_bf16"))
         # Keras weight regularizers [(lo, hi, l1, l2)], read here (at compile) like the clip values
@@ -200,7 +204,13 @@ class RefExecutor(Executor):
         """Per-row (loss, dlogits, correct); with weights w [M], loss and dlogits carry the row
         factor w_i * M / nnz (R.weight_factor), the accuracy stays unweighted."""
         hd = self.plan.head
-        if hd.activation == "softmax":
+        if not classic_head(hd.activation, hd.loss, hd.N):
+            # the loss table, or the multi-label binary_crossentropy (corr: correct ELEMENTS per row)
+            if hd.loss == "binary_crossentropy":
+                loss, dz, corr = R.sigmoid_bce(z, y)
+            else:
+                loss, dz, corr = R.table_loss(hd.activation, hd.loss, z, y)
+        elif hd.activation == "softmax":
             loss, dz, corr = R.softmax_cce(z, y)
         elif hd.activation == "sigmoid":
             loss, dz, corr = R.sigmoid_bce(z.reshape(-1), y.reshape(-1))
@@ -358,7 +368,7 @@ class RefExecutor(Executor):
 
     def _accumulate(self, loss, corr, bs, penalty=0.0):
         # (a batch of bs rows reports L_data + P: it adds bs * P to the epoch's loss sum)
-        ls, cs = float(loss.sum()) + bs * penalty, float(corr.sum())
+        ls, cs = float(loss.sum()) + bs * penalty, float(corr.sum()) / self._acc_div
         self._acc += torch.tensor([ls, cs, bs], dtype=torch.float64)
         self._last = (ls / bs, cs / bs)
 

@@ -133,15 +133,46 @@ class Plan:
                 + ([self.head] if self.head else []))
 
 
+# every Keras name (and alias) of a loss -> its canonical name
+LOSS_ALIASES = {"categorical_crossentropy": "categorical_crossentropy",
+                "binary_crossentropy": "binary_crossentropy",
+                "mse": "mse", "MSE": "mse", "mean_squared_error": "mse",
+                "sparse_categorical_crossentropy": "sparse_categorical_crossentropy",
+                "mae": "mae", "MAE": "mae", "mean_absolute_error": "mae",
+                "msle": "msle", "MSLE": "msle", "mean_squared_logarithmic_error": "msle",
+                "logcosh": "logcosh", "hinge": "hinge", "squared_hinge": "squared_hinge",
+                "categorical_hinge": "categorical_hinge",
+                "kld": "kld", "KLD": "kld", "kullback_leibler_divergence": "kld",
+                "poisson": "poisson"}
+# the losses that go with every output activation (README, "Losses"); the crossentropies keep
+# their own activation
+TABLE_LOSSES = ("mse", "mae", "msle", "logcosh", "hinge", "squared_hinge", "categorical_hinge", "kld", "poisson")
+
+
 def canonical_loss(loss) -> str:
+    """The canonical name of a Keras loss name, alias, or loss function (by its ``__name__``)."""
     name = loss if isinstance(loss, str) else getattr(loss, "__name__", str(loss))
-    aliases = {"categorical_crossentropy": "categorical_crossentropy",
-               "binary_crossentropy": "binary_crossentropy",
-               "mse": "mse", "mean_squared_error": "mse",
-               "sparse_categorical_crossentropy": "sparse_categorical_crossentropy"}
-    if name not in aliases:
+    if name not in LOSS_ALIASES:
         raise NotImplementedError("loss %r is not implemented" % (name,))
-    return aliases[name]
+    return LOSS_ALIASES[name]
+
+
+def classic_head(activation, loss: str, N: int) -> bool:
+    """True for the three (activation, loss) pairs of the first head kernel at the widths it
+    supports: softmax + (sparse_)categorical_crossentropy, sigmoid + binary_crossentropy
+    at N == 1, linear + mse (a linear output with a crossentropy name has always run as mse).
+    Every other pair runs the loss head."""
+    if activation == "softmax":
+        return loss in ("categorical_crossentropy", "sparse_categorical_crossentropy")
+    if activation == "sigmoid":
+        return loss == "binary_crossentropy" and N == 1
+    return loss not in TABLE_LOSSES or loss == "mse"
+
+
+def binary_accuracy_head(loss: str, N: int) -> bool:
+    """Keras' ``compile`` rule for 'acc': binary_accuracy (mean over the columns of
+    [rint(p) == y]) for a one-column output or binary_crossentropy, else categorical_accuracy."""
+    return N == 1 or loss == "binary_crossentropy"
 
 
 ACT_LAYERS = (Activation, LeakyReLU, ELU)
@@ -299,8 +330,8 @@ def build_plan(layers: List[Layer], loss) -> Plan:
     if plan.head is None:
         raise NotImplementedError("the model must end with a Dense layer")
     if plan.head.activation == "softmax" and loss not in ("categorical_crossentropy",
-                                                          "sparse_categorical_crossentropy"):
+                                                          "sparse_categorical_crossentropy") + TABLE_LOSSES:
         raise NotImplementedError("softmax output with loss %s" % loss)
-    if plan.head.activation == "sigmoid" and loss != "binary_crossentropy":
+    if plan.head.activation == "sigmoid" and loss not in ("binary_crossentropy",) + TABLE_LOSSES:
         raise NotImplementedError("sigmoid output with loss %s" % loss)
     return plan

@@ -219,7 +219,11 @@ def softmax_cce(logits: torch.Tensor, y: torch.Tensor):
 def sigmoid_bce(z: torch.Tensor, y: torch.Tensor):
     """Keras binary_crossentropy on a sigmoid output: clip p to [eps, 1-eps], go back
     to logits, sigmoid-CE-with-logits.  z, y: [B] (or [B,1]).  Returns per-row
-    (loss, dz, correct)."""
+    (loss, dz, correct).
+
+    z, y of shape [B, N] with N > 1 (a multi-label head): the loss is the mean over the columns
+    of the per-element formula, dz [B, N] carries the 1/N, and correct is the row's COUNT of
+    correct elements (binary_accuracy is its sum over rows * N)."""
     p = torch.sigmoid(z)
     inr = (p >= EPS) & (p <= 1.0 - EPS)
     pc = p.clamp(EPS, 1.0 - EPS)
@@ -227,7 +231,106 @@ def sigmoid_bce(z: torch.Tensor, y: torch.Tensor):
     loss = torch.clamp(lg, min=0) - lg * y + torch.log1p(torch.exp(-lg.abs()))
     dz = torch.where(inr, pc - y, torch.zeros_like(p))
     correct = (torch.round(p) == y).to(torch.float32)   # round-half-even like TF
+    if z.dim() == 2 and z.shape[1] > 1:
+        return loss.mean(-1), dz / z.shape[1], correct.sum(-1)
     return loss, dz, correct
+
+
+# The loss table (README, "Losses"): per-row loss l(p, y) [B] and g = dl/dp [B, N] of an output
+# p = A(z) [B, N].  Keras 2.2.4 / TF subgradients: a maximum's tie gives the first argument the
+# gradient, clips pass it on the closed interval, the FIRST row maximum takes the whole gradient.
+def _first_argmax(v: torch.Tensor) -> torch.Tensor:
+    mx = v.max(dim=-1, keepdim=True).values
+    idx = torch.arange(v.shape[-1], device=v.device).expand_as(v)
+    # (a row of NaNs has no maximum: index 0)
+    return torch.where(v == mx, idx, torch.full_like(idx, v.shape[-1])).min(dim=-1).values % v.shape[-1]
+
+
+def loss_mse(p, y):
+    d = p - y
+    return (d * d).mean(-1), 2.0 * d / p.shape[-1]
+
+
+def loss_mae(p, y):
+    d = p - y
+    return d.abs().mean(-1), torch.sign(d) / p.shape[-1]
+
+
+def loss_msle(p, y):
+    pm, ym = p.clamp(min=EPS), y.clamp(min=EPS)
+    d = torch.log(pm + 1.0) - torch.log(ym + 1.0)
+    g = torch.where(p >= EPS, 2.0 * d / (pm + 1.0), torch.zeros_like(p))
+    return (d * d).mean(-1), g / p.shape[-1]
+
+
+def loss_logcosh(p, y):
+    d = p - y
+    ad = d.abs()
+    return (ad + torch.log1p(torch.exp(-2.0 * ad)) - math.log(2.0)).mean(-1), torch.tanh(d) / p.shape[-1]
+
+
+def loss_hinge(p, y):
+    m = 1.0 - y * p
+    return m.clamp(min=0).mean(-1), torch.where(m >= 0, -y, torch.zeros_like(p)) / p.shape[-1]
+
+
+def loss_squared_hinge(p, y):
+    h = (1.0 - y * p).clamp(min=0)
+    return (h * h).mean(-1), -2.0 * y * h / p.shape[-1]
+
+
+def loss_categorical_hinge(p, y):
+    pos = (y * p).sum(-1)
+    negs = (1.0 - y) * p
+    neg = negs.max(dim=-1).values
+    v = neg - pos + 1.0
+    first = torch.nn.functional.one_hot(_first_argmax(negs), p.shape[-1]).to(p.dtype)
+    g = torch.where((v > 0).unsqueeze(-1), -y + first * (1.0 - y), torch.zeros_like(p))
+    return v.clamp(min=0), g
+
+
+def loss_kld(p, y):
+    yc, pc = y.clamp(EPS, 1.0), p.clamp(EPS, 1.0)
+    g = torch.where((p >= EPS) & (p <= 1.0), -yc / pc, torch.zeros_like(p))
+    return (yc * torch.log(yc / pc)).sum(-1), g
+
+
+def loss_poisson(p, y):
+    q = p + EPS
+    return (p - y * torch.log(q)).mean(-1), (1.0 - y / q) / p.shape[-1]
+
+
+TABLE_LOSSES = {"mse": loss_mse, "mae": loss_mae, "msle": loss_msle, "logcosh": loss_logcosh, "hinge": loss_hinge,
+                "squared_hinge": loss_squared_hinge, "categorical_hinge": loss_categorical_hinge, "kld": loss_kld,
+                "poisson": loss_poisson}
+
+
+def head_probs(activation, z: torch.Tensor) -> torch.Tensor:
+    if activation == "softmax":
+        return torch.softmax(z, dim=-1)
+    if activation == "sigmoid":
+        return torch.sigmoid(z)
+    return z
+
+
+def table_loss(activation, loss: str, z: torch.Tensor, y: torch.Tensor):
+    """A loss of the table on the output A(z), z and y [B, N].  Returns per-row
+    (loss [B], dlogits [B, N] (not /B), correct [B]); correct is the row's count of correct
+    elements under Keras' binary_accuracy (N == 1) and 0 / 1 under categorical_accuracy (first
+    argmax of the output against first argmax of the targets)."""
+    p = head_probs(activation, z)
+    l, g = TABLE_LOSSES[loss](p, y)
+    if activation == "sigmoid":
+        dz = g * p * (1.0 - p)
+    elif activation == "softmax":
+        dz = p * (g - (p * g).sum(-1, keepdim=True))
+    else:
+        dz = g
+    if z.shape[-1] == 1:
+        correct = (torch.round(p) == y).to(torch.float32).sum(-1)
+    else:
+        correct = (_first_argmax(p) == _first_argmax(y)).to(torch.float32)
+    return l, dz, correct
 
 
 def mse(out: torch.Tensor, y: torch.Tensor):
