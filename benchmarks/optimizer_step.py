@@ -44,7 +44,9 @@ inputs instead of 4096).
 ``INTML_TUNE=fuse_head=0``: ``dense_epi`` as a launch of its own, then the first head kernel) and one
 ``<name>/loss-<NAME>`` model per name (that structure with the ``loss_head`` launch in the head's
 place; ``NAME@N`` puts the loss on a sigmoid output of N columns, ``binary_crossentropy@8`` being the
-multi-label head).  The difference between those is the cost of the second head kernel.
+multi-label head).  The difference between those is the cost of the second head kernel.  With N > 16
+(``binary_crossentropy@100``) the row is the wide head's: the same structure with ``wide_head`` in the
+head's place, and the end-of-step slab reduction of its K x N gradient.
 
 ``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
 them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
@@ -120,7 +122,7 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
         for ls in losses:
             # NAME@N: the loss on a sigmoid output of N columns (binary_crossentropy@8: the multi-label head)
             name, _, cols = ls.partition("@")
-            out.append((nm + "/loss-" + ls, nm, {}, None, 0.0, "relu",
+            out.append((nm + "/loss-" + ls, nm, {}, "wide_head=1" if cols and int(cols) > 16 else None, 0.0, "relu",
                         dict({"loss": name}, **({"outputs": int(cols)} if cols else {}))))
     return out
 

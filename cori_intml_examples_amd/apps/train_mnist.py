@@ -9,6 +9,8 @@ from __future__ import annotations
 import argparse
 import sys
 
+import numpy as np
+
 
 def build_parser():
     p = argparse.ArgumentParser(description="MNIST CNN training (FoM protocol)")
@@ -32,6 +34,9 @@ def build_parser():
     p.add_argument("--loss", default=None, metavar="NAME",
                    help="a Keras loss name in categorical_crossentropy's place (mse, mae, msle, logcosh, hinge, "
                         "squared_hinge, categorical_hinge, kld, poisson)")
+    p.add_argument("--classes", type=int, default=10, metavar="N",
+                   help="output columns (>= 10; the labels keep their 10 classes, further columns are never hot; "
+                        "more than 16: the wide head kernel, with INTML_TUNE=wide_head=1)")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--valid-frac", type=float, default=0.17)
@@ -54,7 +59,10 @@ def main(argv=None):
     hvd.init()
     x, y, _, _ = load_data(n_train=a.n_train)
     x, y = x[:a.n_train], y[:a.n_train]
-    model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout,
+    if a.classes < y.shape[1]:
+        raise SystemExit("--classes must be at least %d" % y.shape[1])
+    y = np.pad(y, ((0, 0), (0, a.classes - y.shape[1])))
+    model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout, n_classes=a.classes,
                       optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
                       use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm,
                       pool=a.pool, global_pool=a.global_pool, loss=a.loss, metrics=parse_metric_list(a.metrics),

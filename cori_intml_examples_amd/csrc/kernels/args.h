@@ -407,7 +407,10 @@ struct HeadArgs {
 // LOSS_BCE (the multi-label binary_crossentropy), which is a sigmoid head's
 enum HeadLoss : int {
   LOSS_MSE = 0, LOSS_MAE = 1, LOSS_MSLE = 2, LOSS_LOGCOSH = 3, LOSS_HINGE = 4, LOSS_SQ_HINGE = 5,
-  LOSS_CAT_HINGE = 6, LOSS_KLD = 7, LOSS_POISSON = 8, LOSS_BCE = 9, LOSS_COUNT = 10
+  LOSS_CAT_HINGE = 6, LOSS_KLD = 7, LOSS_POISSON = 8, LOSS_BCE = 9, LOSS_COUNT = 10,
+  // wide_head_kernel only (wide_head.hip): (sparse_)categorical_crossentropy on a softmax output.
+  // No code of loss_head_kernel's: far past LOSS_COUNT, so no loss added to that table reaches it
+  LOSS_CCE = 100
 };
 
 struct GatherArgs {

@@ -36,6 +36,9 @@ int dense_groups(int M, int NT, int KS);
 bool dense_big(int NT, int KS);
 void launch_head(const HeadArgs& a, hipStream_t s);
 void launch_loss_head(const HeadArgs& a, hipStream_t s);
+void launch_wide_head(const HeadArgs& a, hipStream_t s);
+int wide_head_slabs(int M);
+int wide_head_max_n();
 bool launch_dual_halo(const ConvMMArgs& ca, int ntc, const WgradArgs& wa, int MT, int NTT, int splits,
                       const DualExtra& x, hipStream_t s);
 bool launch_dense_bwd_dual(const WgradArgs& wa, int ktw, int ntt, int splits, const DenseFwdArgs& da,
@@ -201,6 +204,7 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("LOSS_POISSON") = (int)LOSS_POISSON;
   m.attr("LOSS_BCE") = (int)LOSS_BCE;
   m.attr("LOSS_COUNT") = (int)LOSS_COUNT;
+  m.attr("LOSS_CCE") = (int)LOSS_CCE;      // wide_head only
 
 
   py::class_<GatherArgs>(m, "GatherArgs")
@@ -433,6 +437,11 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("dense_epi", [](const DenseEpiArgs& a, uintptr_t s) { launch_dense_epi(a, S(s)); check_last("dense_epi"); });
   m.def("head", [](const HeadArgs& a, uintptr_t s) { launch_head(a, S(s)); check_last("head"); });
   m.def("loss_head", [](const HeadArgs& a, uintptr_t s) { launch_loss_head(a, S(s)); check_last("loss_head"); });
+  // the wide head (wide_head.hip): 17..WIDE_HEAD_MAX_N columns; its launch has wide_head_slabs(M)
+  // workgroups, each the owner of one dW / db slab
+  m.def("wide_head", [](const HeadArgs& a, uintptr_t s) { launch_wide_head(a, S(s)); check_last("wide_head"); });
+  m.def("wide_head_slabs", &wide_head_slabs);
+  m.attr("WIDE_HEAD_MAX_N") = wide_head_max_n();
   m.def("prologue", [](const PrologueArgs& a, const PackTable& t, uintptr_t s) {
     launch_prologue(a, t, S(s)); check_last("prologue"); });
   m.def("gather_gx", &gather_gx);

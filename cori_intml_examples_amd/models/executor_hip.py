@@ -50,6 +50,10 @@ from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDes
 LOSS_CODES = {"mse": "LOSS_MSE", "mae": "LOSS_MAE", "msle": "LOSS_MSLE", "logcosh": "LOSS_LOGCOSH",
               "hinge": "LOSS_HINGE", "squared_hinge": "LOSS_SQ_HINGE", "categorical_hinge": "LOSS_CAT_HINGE",
               "kld": "LOSS_KLD", "poisson": "LOSS_POISSON", "binary_crossentropy": "LOSS_BCE"}
+# the wide head's three pairs (wide_head.hip): (output activation, canonical loss) -> its loss code
+WIDE_HEAD_PAIRS = {("softmax", "categorical_crossentropy"): "LOSS_CCE",
+                   ("softmax", "sparse_categorical_crossentropy"): "LOSS_CCE",
+                   ("sigmoid", "binary_crossentropy"): "LOSS_BCE", (None, "mse"): "LOSS_MSE"}
 
 BF16 = torch.bfloat16
 # views of the optimizer-kind table (optim/optimizers.py KINDS); STANDALONE_KINDS: see
@@ -198,12 +202,26 @@ class HipExecutor(Executor):
 
     # ------------------------------------------------------------------ geometry
     def _build_geometry(self):
-        inp, self.convs, self.denses, self.head_src, self.head_act = stage_geometry(self.plan)
         hd = self.plan.head
+        # opt-in (INTML_TUNE=wide_head=1): without it a head wider than 16 units is refused as ever
+        if hd.N > 16 and not tune("wide_head"):
+            raise NotImplementedError("output layers wider than 16 units need INTML_TUNE=wide_head=1 (the wide head "
+                                      "kernel: up to %d units)" % self.K.WIDE_HEAD_MAX_N)
+        inp, self.convs, self.denses, self.head_src, self.head_act = stage_geometry(
+            self.plan, head_max=self.K.WIDE_HEAD_MAX_N if tune("wide_head") else 16)
+        # more than 16 columns: the wide head kernel (wide_head.hip), three pairs.  Its model takes the
+        # fuse_head=0 structure like a loss_head model, and the end-of-step / per-bucket slab
+        # reduction (BatchPlan._early_groups)
+        self.wide_head = hd.N > 16
+        if self.wide_head and (hd.activation, hd.loss) not in WIDE_HEAD_PAIRS:
+            raise NotImplementedError("loss %s on a %s output layer of %d units: output layers wider than 16 units "
+                                      "run softmax + (sparse_)categorical_crossentropy, sigmoid + "
+                                      "binary_crossentropy or linear + mse" % (hd.loss, hd.activation or "linear", hd.N))
         # the second head kernel (loss_head.hip) runs every pair the first one does not; it reads
         # the last hidden stage's stored output, never a split-K epilogue
-        self.loss_head = not classic_head(hd.activation, hd.loss, hd.N)
-        self.acc_div = float(hd.N) if self.loss_head and hd.N > 1 and binary_accuracy_head(hd.loss, hd.N) else 1.0
+        self.loss_head = not self.wide_head and not classic_head(hd.activation, hd.loss, hd.N)
+        self.acc_div = (float(hd.N) if (self.loss_head or self.wide_head) and hd.N > 1
+                        and binary_accuracy_head(hd.loss, hd.N) else 1.0)
         self.in_C, self.in_Cs, self.in_H, self.in_W = inp.C, inp.Cs, inp.H, inp.W
         # the global pooling stage behind the last conv stage (None: the model has none)
         self.gpool = gpool_geometry(self.plan, self.convs[-1].out_src) if self.convs else None
@@ -639,6 +657,8 @@ class BatchPlan(GeometryMixin):
         hd = ex.plan.head
         self.head_blocks = cdiv(bs, K.head_rows_per_block(False))   # re-set below if the head fuses the epilogue
         head_slab_blocks = cdiv(bs, K.head_rows_per_block(True))
+        if ex.wide_head:      # one slab per workgroup of the wide head's launch
+            self.head_blocks = head_slab_blocks = K.wide_head_slabs(bs)
         # (a plan with a ROC metric: roc_accum reads the head's probabilities in train and eval mode too)
         self.roc = ex.roc_on and mode != "predict"
         self.probs = z(bs, hd.N, dt=torch.float32) if mode == "predict" or self.roc else None
@@ -1016,7 +1036,7 @@ class BatchPlan(GeometryMixin):
                 e.drop_thr, e.drop_scale = dropout_pair(g.rate)
             e.seed, e.stream_id, e.st = ex.seed, g.stream, ex.state.data_ptr()
             if (g.j == len(ex.denses) - 1 and ex.head_src.kind == "dense" and g.Ns <= K.head_epi_max()
-                    and tune("fuse_head") and g.plain and not ex.loss_head):
+                    and tune("fuse_head") and g.plain and not ex.loss_head and not ex.wide_head):
                 # the head launch (one row per workgroup, the row's split groups in parallel)
                 # reduces this layer's partials itself: one kernel boundary fewer
                 head_epi = e
@@ -1061,7 +1081,10 @@ class BatchPlan(GeometryMixin):
         # (a fused dense layer + head launch -- 16-wave K-slice tiles, the last arriving workgroup
         # of each row group running the head -- measured 15.6 us against 13.3 us for the split-K
         # dense launch + this head launch at RPV B=128, and was removed in round 5)
-        if ex.loss_head:
+        if ex.wide_head:
+            h.loss = getattr(K, WIDE_HEAD_PAIRS[hd.activation, hd.loss])
+            self._add("wide_head", lambda s, a=h: K.wide_head(a, s), head=h)
+        elif ex.loss_head:
             h.loss = getattr(K, LOSS_CODES[hd.loss])
             self._add("loss_head", lambda s, a=h: K.loss_head(a, s), head=h)
         else:
@@ -1566,7 +1589,9 @@ class BatchPlan(GeometryMixin):
         self.early_red = {}
         # (not inline_update_ok: the head and dense groups stay in the end-of-step / per-bucket
         # reduce_optim_kernel<KIND> launch)
-        if not tune("early_reduce") or not self.ex.inline_update_ok:
+        # (a wide head: its K x N group is far larger than anything the dual launch's extra workgroups
+        # were sized and measured for -- it stays in the end-of-step / per-bucket reduction too)
+        if not tune("early_reduce") or not self.ex.inline_update_ok or self.ex.wide_head:
             return []
         names = [it[0] for it in self.launches]
         # only the FIRST dual launch carries a bucket: every dual launch carrying the previous

@@ -192,7 +192,8 @@ class Model:
         if getattr(self.optimizer, "distributed", False):
             from ..parallel import dist
             dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda",
-                                       tuple(self.store.regularized_layers()), dist.bn_layer_names(self._plan))
+                                       tuple(self.store.regularized_layers()), dist.bn_layer_names(self._plan),
+                                       dist.wide_head_names(self._plan))
         if self._device.type == "cuda":
             from .executor_hip import HipExecutor
             self._executor = HipExecutor(self._plan, self.store, base, self._seed)

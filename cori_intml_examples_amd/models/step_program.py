@@ -162,8 +162,10 @@ def gpool_geometry(plan, src):
     return GPoolGeo.of(plan.gpool, src, plan.gpool.mode) if getattr(plan, "gpool", None) is not None else None
 
 
-def stage_geometry(plan):
-    """(input Src, [ConvGeo], [DenseGeo], head Src, head activation code) of a models.plan.Plan."""
+def stage_geometry(plan, head_max=16):
+    """(input Src, [ConvGeo], [DenseGeo], head Src, head activation code) of a models.plan.Plan.
+    ``head_max``: the widest output layer the caller has a kernel for (16: the two narrow head
+    kernels; HipExecutor passes the wide head kernel's limit)."""
     shape = plan.input_shape
     H, W, Cin = shape if len(shape) == 3 else (1, 1, shape[0])
     Cs_in = 4 if Cin <= 4 else r8(Cin)
@@ -201,8 +203,8 @@ def stage_geometry(plan):
     hd = plan.head
     if hd.K != src.H * src.W * src.C:
         raise ValueError("head input width mismatch")
-    if hd.N > 16:
-        raise NotImplementedError("output layers wider than 16 units")
+    if hd.N > head_max:
+        raise NotImplementedError("output layers wider than %d units" % head_max)
     return inp, convs, denses, src, {None: 0, "sigmoid": 1, "softmax": 2}[hd.activation]
 
 

@@ -533,19 +533,24 @@ def auto_plane(grad_bytes: Optional[int] = None) -> str:
 RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-switch instance)
 
 
-def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=(), bn_layers=()) -> str:
+def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=(), bn_layers=(), wide_head=()) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
     for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``), and for a
     model with weight regularizers (``needs_local_gradient``: the names of its regularized
     layers) -- when it was merely chosen (auto / a recorded verdict), and is a ValueError when it
     was forced (INTML_XGMI, or a job without an RCCL communicator).  A model with
     BatchNormalization layers (``bn_layers``: their names) is gated the same way: its step is
-    exercised on the RCCL plane only."""
+    exercised on the RCCL plane only.  So is a model whose output layer is wider than 16 units
+    (``wide_head``: that layer's name): the xGMI tables were sized for heads of up to 16 columns."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
     clips = bool(getattr(base, "clips", False))
     if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips
-                                               or needs_local_gradient or bn_layers):
+                                               or needs_local_gradient or bn_layers or wide_head):
         return plane
+    if forced and wide_head:
+        raise ValueError("output layer %s is wider than 16 units: the wide head has no kernels for the %r data "
+                         "plane (its gradient is all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
+                         % (", ".join(wide_head), plane))
     if forced and bn_layers:
         raise ValueError("BatchNormalization layers (%s) have no kernels for the %r data plane (their gamma / beta "
                          "gradients are all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
@@ -588,8 +593,9 @@ class NativeGradReducer:
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
                  rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None,
-                 needs_local_gradient=(), bn_layers=()):
+                 needs_local_gradient=(), bn_layers=(), wide_head=()):
         self.store, self.comm = store, comm
+        self.wide_head = wide_head      # (an output layer wider than 16 units: the same)
         self.bn_layers = bn_layers      # (a model with BatchNormalization layers: RCCL plane only)
         self.optimizer = optimizer      # (plane_for_optimizer: kinds that stay off the xGMI planes)
         self.needs_local_gradient = needs_local_gradient   # (a regularized model's layer names: the same)
@@ -620,7 +626,8 @@ class NativeGradReducer:
         local = getattr(self, "needs_local_gradient", ())
         self.plane = plane_for_optimizer(self.plane, getattr(self, "optimizer", None),
                                          forced=self.comm is None or forced_plane() is not None,
-                                         needs_local_gradient=local, bn_layers=getattr(self, "bn_layers", ()))
+                                         needs_local_gradient=local, bn_layers=getattr(self, "bn_layers", ()),
+                                         wide_head=getattr(self, "wide_head", ()))
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
@@ -780,7 +787,7 @@ class NativeGradReducer:
             grad[: self.store.numel].div_(self.size)
 
 
-def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_layers=()) -> None:
+def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_layers=(), wide_head=()) -> None:
     """ValueError when the job pins a data plane ``optimizer`` -- or a model with weight
     regularizers (``needs_local_gradient``: its regularized layers' names) -- has no kernels for
     (INTML_XGMI = xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds
@@ -790,15 +797,21 @@ def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_l
     st = _st()
     if on_gpu and st.comm is not None:
         plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
-                            bn_layers=bn_layers)
+                            bn_layers=bn_layers, wide_head=wide_head)
     elif on_gpu and st.xgmi_only and st.size > 1:
         plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
-                            bn_layers=bn_layers)
+                            bn_layers=bn_layers, wide_head=wide_head)
 
 
 def bn_layer_names(plan) -> tuple:
     """Names of a plan's BatchNormalization layers, in stage order."""
     return tuple(s.bn.name for s in list(plan.convs) + list(plan.denses) if getattr(s, "bn", None) is not None)
+
+
+def wide_head_names(plan) -> tuple:
+    """(name,) of a plan's output layer when it is wider than 16 units (the wide head kernel), else ()."""
+    hd = getattr(plan, "head", None)
+    return (hd.dense.name,) if hd is not None and hd.N > 16 else ()
 
 
 def make_reducer(executor, optimizer):
@@ -812,12 +825,13 @@ def make_reducer(executor, optimizer):
     # all-reduce, as a clipping optimizer does: ONE bucket, RCCL plane (the layers' names, for errors)
     local = tuple(executor.store.regularized_layers()) if getattr(executor, "regs", None) else ()
     bn = bn_layer_names(executor.plan)
-    check_optimizer_plane(optimizer, on_gpu, local, bn)
+    wide = wide_head_names(executor.plan)
+    check_optimizer_plane(optimizer, on_gpu, local, bn, wide)
     if on_gpu and st.comm is not None:
         return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn)
+                                 bn_layers=bn, wide_head=wide)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
                                  device=executor.store.device, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn)
+                                 bn_layers=bn, wide_head=wide)
     return GradReducer(executor.store, comp, bb, optimizer=optimizer, needs_local_gradient=local)

@@ -158,6 +158,9 @@ KNOBS: Tuple[Knob, ...] = (
     # ---------------------------------------------------------------- head
     Knob("fuse_head", True, PATH, "the head launch runs the last dense layer's split-K epilogue; same "
          "activations, the loss metric differs in fp32 rounding (tests/test_head_edges.py)"),
+    Knob("wide_head", False, PATH, "1: output layers of 17..1024 units run the wide head kernel "
+         "(wide_head.hip) instead of raising NotImplementedError; opt-in, so every model that built "
+         "before builds as before (tests/test_wide_head_gpu.py)"),
     Knob("head_generic", False, EXACT, "1: the head kernel without its fast paths "
          "(test_head_fast_paths_bit_identical)"),
     # ---------------------------------------------------------------- reduction / optimizer

@@ -20,6 +20,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KDIR = os.path.join(ROOT, "cori_intml_examples_amd", "csrc", "kernels")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + KDIR, "-munsafe-fp-atomics",
          "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
+
+
+def _build_file_flags():
+    """The build's per-file flags (cori_intml_examples_amd/_build.py FILE_FLAGS), loaded by path: the
+    package itself is not imported."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_intml_build", os.path.join(ROOT, "cori_intml_examples_amd", "_build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.FILE_FLAGS
+
+
+FILE_FLAGS = _build_file_flags()
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "ScratchSize [bytes/lane]": "scratch", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occ"}
 
@@ -54,7 +67,7 @@ def report(src, insts=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as tmp:
         out = ["-S", "-x", "hip", src, "-o", os.path.join(tmp, "k.s")] if insts else ["-c", src, "-o", os.devnull]
-        r = subprocess.run([hipcc] + FLAGS + out, capture_output=True, text=True, timeout=1800)
+        r = subprocess.run([hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + out, capture_output=True, text=True, timeout=1800)
         counts = count_instructions(os.path.join(tmp, "k.s")) if insts and r.returncode == 0 else {}
     rows, cur = [], None
     for line in r.stderr.splitlines():
