@@ -4,7 +4,7 @@
                                         [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
                                         [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
-                                        [--loss NAME[,NAME..]]
+                                        [--loss NAME[,NAME..]] [--separable]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -48,6 +48,10 @@ multi-label head).  The difference between those is the cost of the second head 
 (``binary_crossentropy@100``) the row is the wide head's: the same structure with ``wide_head`` in the
 head's place, and the end-of-step slab reduction of its K x N gradient.
 
+``--separable`` adds ``<name>/unstacked`` likewise and ``<name>/separable`` (``rpv_cnn(separable=True)``: every
+Conv2D except the first is a SeparableConv2D -- per conv layer behind the first ``dw_fwd`` and a 1x1
+``conv_fwd`` in the 3x3 conv's place, ``dw_wgrad`` / ``dw_dgrad`` and the 1x1 stage's backward).
+
 ``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
 them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
 ``<name>/weighted-data`` (the default model on sample-weighted data: the weighted head instances, no new
@@ -84,7 +88,7 @@ def make_opt(name, **kw):
 
 
 def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
-             metrics=None, weighted_metrics=None, losses=()):
+             metrics=None, weighted_metrics=None, losses=(), separable=False):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
     "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
@@ -106,12 +110,14 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/l2", nm, {}, None, l2, "relu"))
         if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
-        if pool != "max" or global_pool:
+        if pool != "max" or global_pool or separable:
             out.append((nm + "/unstacked", nm, {}, UNSTACKED, 0.0, "relu"))
         if pool != "max":
             out.append((nm + "/pool-" + pool, nm, {}, None, 0.0, "relu+pool=" + pool))
         if global_pool:
             out.append((nm + "/gpool-" + global_pool, nm, {}, None, 0.0, "relu+gpool=" + global_pool))
+        if separable:
+            out.append((nm + "/separable", nm, {}, None, 0.0, "relu+separable"))
         if batch_norm:
             out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
@@ -159,6 +165,7 @@ def main():
     ap.add_argument("--pool", choices=["max", "avg"], default="max", help="time the model with AveragePooling2D layers")
     ap.add_argument("--global-pool", choices=["avg", "max"], default=None,
                     help="time the model with a global pooling layer in the Flatten's place")
+    ap.add_argument("--separable", action="store_true", help="time rpv_cnn(separable=True)")
     ap.add_argument("--loss", default="", metavar="NAME[,NAME]",
                     help="time the model with these Keras losses in binary_crossentropy's place (the loss head), "
                          "and the default model under fuse_head=0 (the same structure with the first head kernel)")
@@ -169,7 +176,7 @@ def main():
     split = lambda t: [n for n in t.split(",") if n]
     var = [v if len(v) == 7 else v + ({},) for v in
            variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
-                    split(a.metrics), split(a.weighted_metrics), split(a.loss))]
+                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable)]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -184,6 +191,7 @@ def main():
             m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
                             optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
                             **({"batch_norm": True} if act == "relu+bn" else {}),
+                            **({"separable": True} if act == "relu+separable" else {}),
                             **({"pool": act.split("=")[1]} if act.startswith("relu+pool=") else {}),
                             **({"global_pool": act.split("=")[1]} if act.startswith("relu+gpool=") else {}),
                             **({"activation": act} if not act.startswith("relu") else {}),

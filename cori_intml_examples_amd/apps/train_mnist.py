@@ -28,6 +28,8 @@ def build_parser():
                         "softplus, softsign")
     p.add_argument("--batch-norm", action="store_true",
                    help="a BatchNormalization between every hidden Conv2D / Dense and its activation")
+    p.add_argument("--separable", action="store_true",
+                   help="every Conv2D except the first becomes a SeparableConv2D with the same arguments")
     p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
     p.add_argument("--global-pool", choices=["avg", "max"], default=None,
                    help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
@@ -65,7 +67,8 @@ def main(argv=None):
     model = mnist_cnn(h1=a.h1, h2=a.h2, h3=a.h3, dropout=a.dropout, n_classes=a.classes,
                       optimizer=clipped_optimizer(a.optimizer, a.lr, a.clipnorm, a.clipvalue), lr=a.lr,
                       use_horovod=hvd.size() > 1, l2=a.l2, activation=a.activation, batch_norm=a.batch_norm,
-                      pool=a.pool, global_pool=a.global_pool, loss=a.loss, metrics=parse_metric_list(a.metrics),
+                      pool=a.pool, global_pool=a.global_pool, loss=a.loss, separable=a.separable,
+                      metrics=parse_metric_list(a.metrics),
                       weighted_metrics=parse_metric_list(a.weighted_metrics))
     cbs = []
     if hvd.size() > 1:

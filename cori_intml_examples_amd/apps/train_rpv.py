@@ -47,6 +47,8 @@ def build_parser():
                         "softplus, softsign")
     p.add_argument("--batch-norm", action="store_true",
                    help="a BatchNormalization between every hidden Conv2D / Dense and its activation")
+    p.add_argument("--separable", action="store_true",
+                   help="every Conv2D except the first becomes a SeparableConv2D with the same arguments")
     p.add_argument("--pool", choices=["max", "avg"], default="max", help="the 2x2 pooling layers: MaxPooling2D or AveragePooling2D")
     p.add_argument("--global-pool", choices=["avg", "max"], default=None,
                    help="a GlobalAveragePooling2D / GlobalMaxPooling2D in the Flatten's place")
@@ -110,7 +112,7 @@ def main(argv=None):
                         optimizer=clipped_optimizer(args.optimizer, lr, args.clipnorm, args.clipvalue), lr=lr,
                         use_horovod=True, l2=args.l2, activation=args.activation,
                         batch_norm=args.batch_norm, pool=args.pool, global_pool=args.global_pool, loss=args.loss,
-                        metrics=parse_metric_list(args.metrics),
+                        separable=args.separable, metrics=parse_metric_list(args.metrics),
                         weighted_metrics=parse_metric_list(args.weighted_metrics))
     if hvd.rank() == 0:
         model.summary()

@@ -9,7 +9,7 @@
 from __future__ import annotations
 
 from ..models import (Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
-                      GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, Sequential)
+                      GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, SeparableConv2D, Sequential)
 from .. import optim as optimizers
 from .. import regularizers
 
@@ -26,6 +26,20 @@ def _hidden(layer_cls, *args, activation="relu", batch_norm=False, **kw):
     if not batch_norm:
         return [layer_cls(*args, activation=activation, **kw)]
     return [layer_cls(*args, **kw), BatchNormalization(), Activation(activation)]
+
+
+def _conv_cls(separable, first=False):
+    """The builders' ``separable=``: Conv2D, or -- for every conv layer but the model's first -- a
+    SeparableConv2D with the same arguments (a kernel regularizer goes on both of its kernels)."""
+    if not separable or first:
+        return Conv2D
+
+    def make(*args, **kw):
+        reg = kw.pop("kernel_regularizer", None)
+        if reg is not None:
+            kw.update(depthwise_regularizer=reg, pointwise_regularizer=reg)
+        return SeparableConv2D(*args, **kw)
+    return make
 
 
 def _pool(pool):
@@ -98,8 +112,10 @@ def fom_from_history(history, name: str, mode: str) -> float:
 
 def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta", lr=None,
               n_classes=10, input_shape=(28, 28, 1), use_horovod=False, device=None, activation="relu",
-              batch_norm=False, pool="max", global_pool=None, metrics=None, weighted_metrics=None, loss=None, l2=0.0):
+              batch_norm=False, pool="max", global_pool=None, metrics=None, weighted_metrics=None, loss=None,
+              separable=False, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``separable``: every Conv2D except the first becomes a SeparableConv2D with the same arguments.
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer.  ``global_pool``: None |
@@ -109,7 +125,7 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
     reg = _kernel_l2(l2)
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     m = Sequential(device=device)
-    for layer in (_hidden(Conv2D, h1, (3, 3), input_shape=input_shape, **hid) + _hidden(Conv2D, h2, (3, 3), **hid)):
+    for layer in (_hidden(Conv2D, h1, (3, 3), input_shape=input_shape, **hid) + _hidden(_conv_cls(separable), h2, (3, 3), **hid)):
         m.add(layer)
     m.add(_pool(pool))
     m.add(Dropout(dropout))
@@ -124,8 +140,9 @@ def mnist_cnn(h1=4, h2=8, h3=32, dropout=0.5, dropout2=None, optimizer="Adadelta
 
 def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, optimizer="Adam", lr=0.001,
             use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max", global_pool=None,
-            metrics=None, weighted_metrics=None, loss=None, outputs=1, l2=0.0):
+            metrics=None, weighted_metrics=None, loss=None, outputs=1, separable=False, l2=0.0):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``separable``: every Conv2D except the first becomes a SeparableConv2D with the same arguments.
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: "max" | "avg", the 2x2 pooling layer of every conv block.
@@ -137,8 +154,8 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
     hid = dict(activation=activation, batch_norm=batch_norm, **reg)
     inputs = Input(shape=input_shape)
     h = inputs
-    for c in conv_sizes:
-        h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), padding="same", **hid))
+    for i, c in enumerate(conv_sizes):
+        h = _chain(h, _hidden(_conv_cls(separable, i == 0), c, kernel_size=(3, 3), padding="same", **hid))
         h = _pool(pool)(h)
     h = Dropout(dropout)(h)
     h = _bridge(global_pool)(h)
@@ -154,8 +171,9 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
 
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
                    use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max",
-                   global_pool=None, metrics=None, weighted_metrics=None, loss=None):
+                   global_pool=None, metrics=None, weighted_metrics=None, loss=None, separable=False):
     """``activation``: the hidden activation of every Conv2D / Dense ("relu": the reference's model).
+    ``separable``: every Conv2D except the first becomes a SeparableConv2D with the same arguments.
     ``metrics`` / ``weighted_metrics``: Model.compile's lists (None: ["accuracy"] and none).
     ``batch_norm``: every hidden Conv2D / Dense becomes layer(linear) -> BatchNormalization ->
     Activation(activation).  ``pool``: accepted for symmetry with the other builders (this model's
@@ -165,8 +183,8 @@ def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2
     _pool(pool)
     hid = dict(activation=activation, batch_norm=batch_norm)
     h = inputs = Input(shape=input_shape)
-    for c, st in ((h1, 1), (h2, 2), (h3, 1), (h4, 2)):
-        h = _chain(h, _hidden(Conv2D, c, kernel_size=(3, 3), strides=st, padding="same", **hid))
+    for i, (c, st) in enumerate(((h1, 1), (h2, 2), (h3, 1), (h4, 2))):
+        h = _chain(h, _hidden(_conv_cls(separable, i == 0), c, kernel_size=(3, 3), strides=st, padding="same", **hid))
     h = _bridge(global_pool)(h)
     h = _chain(h, _hidden(Dense, h5, **hid))
     outputs = Dense(1, activation="sigmoid")(h)

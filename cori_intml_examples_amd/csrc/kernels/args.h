@@ -723,3 +723,36 @@ struct RocArgs {
   long long* state = nullptr;    // ROC_HDR + 2 * N * ROC_BLOCK words
   long long* res = nullptr;      // roc_finish: 2 * N * ROC_RES_WORDS words
 };
+
+// Depthwise convolution (depthwise.hip): Keras DepthwiseConv2D and the depthwise half of a
+// SeparableConv2D, depth_multiplier 1.  bf16 channels-last activations [B, H, W, Cs] (Cs == 4 with
+// C <= 4, else a multiple of 8); the weights are the fp32 master ``depthwise_kernel`` [KH][KW][C],
+// rounded to bf16 on load.  One struct for the stage's three launches:
+//   dw_fwd    x -> out = bf16(A(conv + bias)), A relu or linear; blocks of R OUTPUT rows
+//   dw_dgrad  dt (the gradient wrt the depthwise output) -> dx through ``bt``, the feeding stage's
+//             BwdThrough, at that stage's output resolution; blocks of R INPUT rows
+//   dw_wgrad  x, dt -> S slab rows [KH*KW][C] (+ [C], the bias gradient) of ``slab_ld`` floats; slab g
+//             sums the (image, block of R output rows) pairs [g * pairs_per_slab, (g + 1) * pairs_per_slab)
+#define DW_FWD 0
+#define DW_DGRAD 1
+#define DW_WGRAD 2
+#define DW_THREADS 256
+#define DW_PX 4                    // consecutive output pixels a thread of dw_fwd / dw_dgrad keeps in registers
+#define DW_LDS_BUDGET (64 * 1024)
+struct DwArgs {
+  const bf16* x = nullptr;         // [B, H, W, Cs] the stage input (fwd, wgrad)
+  const float* w = nullptr;        // fp32 [KH][KW][C]
+  const float* bias = nullptr;     // fp32 [C] (fwd; null: none)
+  bf16* out = nullptr;             // [B, Ho, Wo, Cs] (fwd)
+  const bf16* dt = nullptr;        // [B, Ho, Wo, Cs] (dgrad, wgrad)
+  int B = 0, H = 0, W = 0, C = 0, Cs = 0, Ho = 0, Wo = 0;
+  int Cs_out = 0;                  // the channel stride of out / dt: 0 = Cs; 8 behind a model input with Cs == 4
+  int KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0;
+  int depth_multiplier = 1;        // only 1 is implemented (the launchers refuse anything else)
+  int relu = 0;
+  int R = 0;                       // rows per block (dw_rows)
+  BwdThrough bt;                   // dgrad
+  const StepState* st = nullptr;   // dgrad: the dropout counter's step (null: 0)
+  float* slab = nullptr;           // wgrad
+  int slab_ld = 0, S = 0, pairs_per_slab = 0, has_bias = 0;
+};

@@ -74,6 +74,11 @@ void launch_act_fwd(const ActArgs& a, hipStream_t s);
 void launch_act_bwd(const ActArgs& a, hipStream_t s);
 void launch_pool_fwd(const PoolArgs& a, hipStream_t s);
 void launch_pool_bwd(const PoolArgs& a, hipStream_t s);
+void launch_dw_fwd(const DwArgs& a, hipStream_t s);
+void launch_dw_dgrad(const DwArgs& a, hipStream_t s);
+void launch_dw_wgrad(const DwArgs& a, hipStream_t s);
+int dw_rows(const DwArgs& a, int kind, int want);
+size_t dw_lds_bytes(const DwArgs& a, int kind, int R);
 void launch_roc_accum(const RocArgs& a, hipStream_t s);
 void launch_roc_finish(const RocArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
@@ -586,6 +591,23 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("POOL_GMAX") = POOL_GMAX;
   m.def("pool_fwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_fwd(a, S(s)); check_last("pool_fwd"); });
   m.def("pool_bwd", [](const PoolArgs& a, uintptr_t s) { launch_pool_bwd(a, S(s)); check_last("pool_bwd"); });
+  // depthwise convolution (depthwise.hip): forward, input gradient, weight gradient slabs
+  py::class_<DwArgs>(m, "DwArgs")
+      .def(py::init<>())
+      PTR(DwArgs, x) PTR(DwArgs, w) PTR(DwArgs, bias) PTR(DwArgs, out) PTR(DwArgs, dt) RW(DwArgs, B) RW(DwArgs, H)
+      RW(DwArgs, W) RW(DwArgs, C) RW(DwArgs, Cs) RW(DwArgs, Cs_out) RW(DwArgs, Ho) RW(DwArgs, Wo) RW(DwArgs, KH) RW(DwArgs, KW)
+      RW(DwArgs, stride) RW(DwArgs, pad_t) RW(DwArgs, pad_l) RW(DwArgs, depth_multiplier) RW(DwArgs, relu)
+      RW(DwArgs, R) RW(DwArgs, bt) PTR(DwArgs, st) PTR(DwArgs, slab) RW(DwArgs, slab_ld) RW(DwArgs, S)
+      RW(DwArgs, pairs_per_slab) RW(DwArgs, has_bias);
+  m.attr("DW_FWD") = DW_FWD;
+  m.attr("DW_DGRAD") = DW_DGRAD;
+  m.attr("DW_WGRAD") = DW_WGRAD;
+  m.attr("DW_LDS_BUDGET") = DW_LDS_BUDGET;
+  m.def("dw_rows", &dw_rows);
+  m.def("dw_lds_bytes", &dw_lds_bytes);
+  m.def("dw_fwd", [](const DwArgs& a, uintptr_t s) { launch_dw_fwd(a, S(s)); check_last("dw_fwd"); });
+  m.def("dw_dgrad", [](const DwArgs& a, uintptr_t s) { launch_dw_dgrad(a, S(s)); check_last("dw_dgrad"); });
+  m.def("dw_wgrad", [](const DwArgs& a, uintptr_t s) { launch_dw_wgrad(a, S(s)); check_last("dw_wgrad"); });
   // ROC / AUC, purity, efficiency and weighted metrics (roc.hip): roc_accum behind the head in a step,
   // roc_finish once when the metrics are read
   py::class_<RocArgs>(m, "RocArgs")

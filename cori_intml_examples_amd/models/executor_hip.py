@@ -253,7 +253,9 @@ class HipExecutor(Executor):
             return o
 
         for g, cs in zip(self.convs, self.plan.convs):
-            sp = st.spec(cs.conv, "kernel")
+            if g.depthwise:         # (depthwise.hip reads the fp32 master: no pack, no route)
+                continue
+            sp = st.spec(cs.conv, cs.wname)
             g.pack_fwd = alloc(g.KS, g.NT)
             tab.add(sp.offset, sp.numel, PACK_CONV_FWD, g.KH, g.KW, g.Cin, g.Cout, g.Cs_in, g.NT, g.pack_fwd)
             if g.i > 0:
@@ -273,7 +275,9 @@ class HipExecutor(Executor):
         # copies into these packs itself, so a training step needs no re-pack pass
         routes = []
         for g, cs in zip(self.convs, self.plan.convs):
-            sp = st.spec(cs.conv, "kernel")
+            if g.depthwise:
+                continue
+            sp = st.spec(cs.conv, cs.wname)
             bwd = g.pack_dgrad if g.i > 0 and g.Cs_out % 4 == 0 else -1
             routes.append((sp.offset, sp.offset + sp.numel, 1, g.KH * g.KW, g.Cin, g.Cout, g.Cs_in,
                            g.Cs_out if g.i > 0 else 0, g.NT, g.NTd if g.i > 0 else 0, g.pack_fwd, bwd))
@@ -984,6 +988,12 @@ class BatchPlan(GeometryMixin):
             return
         x_buf = self.xb
         for g, cs in zip(ex.convs, ex.plan.convs):
+            if g.depthwise:
+                da = self._dw_args(g, cs, x_buf)
+                self._add("dw_fwd%d" % g.i, lambda s, a=da: K.dw_fwd(a, s), dw=da)
+                self._add_stage_tail_fwd(g)
+                x_buf = self.stage_bufs(g).out
+                continue
             a = K.ConvMMArgs()
             a.x = x_buf.data_ptr()
             a.B, a.H, a.W, a.Cs_in = self.bs, g.H, g.W, g.Cs_in
@@ -992,7 +1002,7 @@ class BatchPlan(GeometryMixin):
             a.KS = g.KS
             a.wpk = ex.arena.data_ptr() + 2 * g.pack_fwd
             a.NT = g.NT
-            a.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
+            a.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
             a.N = g.Cout
             a.mode = 0
             # (a BatchNormalization stage in its linear, un-pooled form: z for the bn.hip launches)
@@ -1286,14 +1296,16 @@ class BatchPlan(GeometryMixin):
         one dual launch where both take the halo kernels -- and the layer's reduction group."""
         ex, K, store = self.ex, self.ex.K, self.ex.store
         xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
+        if g.depthwise:
+            return self._build_dw_bwd(g, cs, xin)
         # (a BatchNormalization stage: conv_dy holds the dense un-pooled dz of bn_bwd_apply)
         g_stage, g = g, g.linear
         wide = self._wide(g.Cs_in, g.KS, g.NT)
         if wide:
-            w = self._wgrad_tile_args(xin, g, cs.conv.use_bias)
+            w = self._wgrad_tile_args(xin, g, cs.use_bias)
             wl = lambda s, a=w.a, c=w.cfg: K.wgrad_tile(a, c[0], s)
         else:
-            w = self._wgrad_halo_args(xin, g, cs.conv.use_bias)
+            w = self._wgrad_halo_args(xin, g, cs.use_bias)
             if g.i == 0 and self.pro_free:      # the images the stack read from the dataset
                 w.a.xidx, w.a.xst = self.srcidx.data_ptr(), ex.state.data_ptr()
             wl = lambda s, a=w.a, c=w.cfg: K.wgrad_halo(a, *c, s)
@@ -1310,8 +1322,8 @@ class BatchPlan(GeometryMixin):
             self._add(dname, fn, "main", ca=ca, ntc=ntc, wa=w.a, cfg=w.cfg)
         else:
             self._add("wgrad_conv%d" % g.i, wl, "side", wa=w.a, cfg=w.cfg)
-        sp = store.spec(cs.conv, "kernel")
-        bsp = store.spec(cs.conv, "bias") if cs.conv.use_bias else None
+        sp = store.spec(cs.conv, cs.wname)
+        bsp = store.spec(cs.conv, "bias") if cs.use_bias else None
         ld = g.NT * 16
         descs = [RedDesc(w.slab.data_ptr(), w.a.Ktiles * 16 * ld, w.splits, ld, sp.offset, sp.numel, RED_CONVW,
                          g.KH, g.KW, g.Cin, g.Cout, g.Cs_in)]
@@ -1323,6 +1335,73 @@ class BatchPlan(GeometryMixin):
             if not dual:
                 self._add(dname, self._conv_launch(ca, g.NTd, False), ca=ca)
             self.pack_readers.append((dname, sp.offset, sp.offset + sp.numel))
+            self._add_stage_tail_bwd(ex.convs[g.i - 1])
+
+    def _dw_args(self, g, cs, x_buf):
+        """The DwArgs of depthwise stage g's forward launch (depthwise.hip), reading ``x_buf``."""
+        ex, K = self.ex, self.ex.K
+        a = K.DwArgs()
+        a.x = x_buf.data_ptr()
+        a.w = ex.store.view(cs.conv, cs.wname).data_ptr()
+        a.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
+        a.out = self.stage_bufs(g).lin_out.data_ptr()
+        a.B, a.H, a.W, a.C, a.Cs, a.Cs_out = self.bs, g.H, g.W, g.Cin, g.Cs_in, g.Cs_out
+        a.Ho, a.Wo = g.Ho, g.Wo
+        a.KH, a.KW, a.stride, a.pad_t, a.pad_l = g.KH, g.KW, g.stride, g.pad_t, g.pad_l
+        a.relu = int(g.relu)
+        a.R = self._dw_rows(a, K.DW_FWD, "%s (dw_fwd%d)" % (cs.conv.name, g.i))
+        return a
+
+    def _dw_rows(self, a, kind, what):
+        R = self.ex.K.dw_rows(a, kind, int(tune("halo_min_wgs")))
+        if R <= 0:
+            raise NotImplementedError("layer %s: one row of its halo over all %d channels exceeds the depthwise "
+                                      "kernels' %d bytes of LDS" % (what, a.C, self.ex.K.DW_LDS_BUDGET))
+        return R
+
+    def _build_dw_bwd(self, g, cs, xin):
+        """A depthwise stage's backward: dw_wgrad into one slab row per workgroup (its reduction group:
+        the kernel, and the bias of a DepthwiseConv2D, as bias-like descriptors) and, unless it is the
+        first stage, dw_dgrad through the feeding stage's BwdThrough."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        bufs = self.stage_bufs(g)
+
+        def base(kind, name):
+            a = K.DwArgs()
+            a.w = store.view(cs.conv, cs.wname).data_ptr()
+            a.dt = bufs.dz.data_ptr()
+            a.B, a.H, a.W, a.C, a.Cs, a.Cs_out = self.bs, g.H, g.W, g.Cin, g.Cs_in, g.Cs_out
+            a.Ho, a.Wo = g.Ho, g.Wo
+            a.KH, a.KW, a.stride, a.pad_t, a.pad_l = g.KH, g.KW, g.stride, g.pad_t, g.pad_l
+            a.R = self._dw_rows(a, kind, "%s (%s%d)" % (cs.conv.name, name, g.i))
+            return a
+
+        wa = base(K.DW_WGRAD, "dw_wgrad")
+        wa.x, wa.has_bias = xin.data_ptr(), int(cs.use_bias)
+        ntaps = g.KH * g.KW
+        bias_off = (ntaps * g.Cin + 3) // 4 * 4
+        wa.slab_ld = bias_off + (cdiv(g.Cin, 4) * 4 if cs.use_bias else 0)
+        # one resident round of workgroups (two per CU at the kernels' 64 KB of LDS)
+        npairs = self.bs * cdiv(g.Ho, wa.R)
+        S = max(1, min(npairs, 2 * self._cu_count()))
+        wa.pairs_per_slab = cdiv(npairs, S)
+        wa.S = S = cdiv(npairs, wa.pairs_per_slab)
+        slab = torch.zeros(S, wa.slab_ld, dtype=torch.float32, device=ex.device)
+        wa.slab = slab.data_ptr()
+        self.wgrad_slabs.append((slab, None))
+        self._add("dw_wgrad%d" % g.i, lambda s, a=wa: K.dw_wgrad(a, s), "side", dw=wa)
+        sp = store.spec(cs.conv, cs.wname)
+        bsp = store.spec(cs.conv, "bias") if cs.use_bias else None
+        descs = [RedDesc(slab.data_ptr(), wa.slab_ld, S, g.Cin, sp.offset, sp.numel, RED_BIAS)]
+        if bsp is not None:
+            descs.append(RedDesc(slab.data_ptr() + 4 * bias_off, wa.slab_ld, S, g.Cin, bsp.offset, bsp.numel,
+                                 RED_BIAS))
+        self._add_group(sp, descs, bsp)
+        if g.i > 0:
+            da = base(K.DW_DGRAD, "dw_dgrad")
+            da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
+            da.st = ex.state.data_ptr()
+            self._add("dw_dgrad%d" % g.i, lambda s, a=da: K.dw_dgrad(a, s), dw=da)
             self._add_stage_tail_bwd(ex.convs[g.i - 1])
 
     # ---------------------------------------------------------------- step program: reductions

@@ -132,9 +132,10 @@ class RefExecutor(Executor):
         self._bn_ctx = {}
         a = x
         for cs in self.plan.convs:
-            w = self._q(st.view(cs.conv, "kernel"))
-            b = st.view(cs.conv, "bias") if cs.conv.use_bias else None
-            z = R.conv2d(a, w, b, cs.stride, cs.conv.padding)
+            # (a SeparableConv2D is two stages: its bias-free depthwise half, then its 1x1 conv)
+            w = self._q(st.view(cs.conv, cs.wname))
+            b = st.view(cs.conv, "bias") if cs.use_bias else None
+            z = (R.depthwise_conv2d if cs.depthwise else R.conv2d)(a, w, b, cs.stride, cs.padding)
             z_code = z
             if cs.bn is not None:
                 # z is stored (bf16) before the statistics; everything behind it acts on u = BN(z),
@@ -286,10 +287,10 @@ class RefExecutor(Executor):
                 da = da * (r > 0).to(da.dtype)
             if cs.bn is not None:
                 da = self._bn_backward(cs.bn, da, self._bn_ctx[id(cs)])
-            dx, dw, db = R.conv2d_backward(a_in, self._q(st.view(cs.conv, "kernel")), da, cs.stride,
-                                           cs.conv.padding, need_dx=i > 0)
-            st.view(cs.conv, "kernel", grad=True).copy_(dw)
-            if cs.conv.use_bias:
+            bwd = R.depthwise_conv2d_backward if cs.depthwise else R.conv2d_backward
+            dx, dw, db = bwd(a_in, self._q(st.view(cs.conv, cs.wname)), da, cs.stride, cs.padding, need_dx=i > 0)
+            st.view(cs.conv, cs.wname, grad=True).copy_(dw)
+            if cs.use_bias:
                 st.view(cs.conv, "bias", grad=True).copy_(db)
             da = dx
 

@@ -101,7 +101,7 @@ class GeometryMixin:
                 L.drop_thr, L.drop_scale = dropout_pair(g.rate)
             L.stream_id = g.stream
             L.wpk = ex.arena.data_ptr() + 2 * g.pack_fwd
-            L.bias = store.view(cs.conv, "bias").data_ptr() if cs.conv.use_bias else 0
+            L.bias = store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
             L.out = self.conv_out[i].data_ptr()
             if g.pool:
                 L.code = self.conv_code[i].data_ptr()

@@ -274,6 +274,160 @@ class Conv2D(_Regularized, Layer):
         return super().from_config(cfg)
 
 
+_GLOROT_CFG = {"class_name": "VarianceScaling", "config": {"scale": 1.0, "mode": "fan_avg", "distribution": "uniform",
+                                                           "seed": None}}
+
+
+class _DepthwiseBase(Layer):
+    """What DepthwiseConv2D and SeparableConv2D share (Keras 2.2.4): a depthwise convolution with
+    depth_multiplier 1, channels_last, isotropic strides, no dilation; the regularizers of the weights
+    in ``_REG_KEYS`` go through ``weight_regularizers()`` under the weights' short names."""
+    _REG_KEYS = ()          # (keyword prefix, weight short name)
+
+    def _set_conv(self, kernel_size, strides, padding, data_format, dilation_rate, depth_multiplier, activation,
+                  use_bias, regs, activity_regularizer, constraints):
+        what = "layer %s (%s)" % (self.name, type(self).__name__)
+        if int(depth_multiplier) != 1:
+            raise NotImplementedError("%s: depth_multiplier = %r; only depth_multiplier=1 is implemented"
+                                      % (what, depth_multiplier))
+        self.depth_multiplier = 1
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        if self.strides[0] != self.strides[1]:
+            raise NotImplementedError("%s: anisotropic strides %r are not implemented" % (what, tuple(self.strides)))
+        if _pair(dilation_rate) != (1, 1):
+            raise NotImplementedError("%s: dilation_rate = %r; dilated convolutions are not implemented"
+                                      % (what, tuple(_pair(dilation_rate))))
+        if data_format not in (None, "channels_last"):
+            raise NotImplementedError("%s: data_format = %r; only channels_last is implemented" % (what, data_format))
+        if activity_regularizer is not None:
+            raise NotImplementedError("%s: activity_regularizer is not implemented (the weight regularizers are)" % what)
+        for key, v in constraints.items():
+            if v is not None:
+                raise NotImplementedError("%s: %s is not implemented" % (what, key))
+        padding = padding.lower()
+        if padding not in ("valid", "same"):
+            raise ValueError(padding)
+        self.padding = padding
+        self.activation = _check_act(activation)
+        if self.activation == "softmax":
+            raise NotImplementedError("%s: softmax on a conv output" % what)
+        self.use_bias = bool(use_bias)
+        self._regs = {short: regularizers.get(regs.get(prefix + "_regularizer")) or None
+                      for prefix, short in self._REG_KEYS}
+
+    def weight_regularizers(self):
+        """{weight short name: L1L2} of this layer's regularized tensors."""
+        return {short: r for short, r in self._regs.items()
+                if r is not None and (short != "bias" or self.use_bias)}
+
+    def _out_hw(self, s):
+        if len(s) != 3:
+            raise ValueError("%s expects (H, W, C) inputs, got %s" % (type(self).__name__, s))
+        kh, kw = self.kernel_size
+        st = self.strides[0]
+        return conv_out_size(s[0], kh, st, self.padding), conv_out_size(s[1], kw, st, self.padding)
+
+    def _conv_config(self):
+        cfg = Layer.get_config(self)
+        cfg.update({"kernel_size": list(self.kernel_size), "strides": list(self.strides), "padding": self.padding,
+                    "data_format": "channels_last", "dilation_rate": [1, 1], "depth_multiplier": 1,
+                    "activation": self.activation or "linear", "use_bias": self.use_bias,
+                    "bias_initializer": {"class_name": "Zeros", "config": {}}, "activity_regularizer": None})
+        for prefix, short in self._REG_KEYS:
+            cfg[prefix + "_regularizer"] = regularizers.serialize(self._regs[short])
+            cfg[prefix + "_constraint"] = None
+            if prefix != "bias":
+                cfg[prefix + "_initializer"] = dict(_GLOROT_CFG)
+        return cfg
+
+    _CONFIG_KEYS = ("name", "trainable", "kernel_size", "strides", "padding", "depth_multiplier", "activation",
+                    "use_bias", "batch_input_shape", "activity_regularizer", "data_format", "dilation_rate")
+
+    @classmethod
+    def from_config(cls, cfg):
+        keys = cls._CONFIG_KEYS + tuple(p + s for p, _ in cls._REG_KEYS for s in ("_regularizer", "_constraint"))
+        cfg = {k: v for k, v in cfg.items() if k in keys}
+        if "dilation_rate" in cfg:
+            cfg["dilation_rate"] = tuple(cfg["dilation_rate"])
+        return super().from_config(cfg)
+
+
+class DepthwiseConv2D(_DepthwiseBase):
+    """``keras.layers.DepthwiseConv2D`` (depth_multiplier 1): every channel convolved with its own
+    kh x kw kernel.  Weights: ``depthwise_kernel`` (kh, kw, C, 1), ``bias`` (C,)."""
+    _REG_KEYS = (("depthwise", "depthwise_kernel"), ("bias", "bias"))
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, data_format=None,
+                 activation=None, use_bias=True, depthwise_initializer="glorot_uniform", bias_initializer="zeros",
+                 depthwise_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 depthwise_constraint=None, bias_constraint=None, dilation_rate=(1, 1), **kw):
+        super().__init__(**kw)
+        self._set_conv(kernel_size, strides, padding, data_format, dilation_rate, depth_multiplier, activation,
+                       use_bias, {"depthwise_regularizer": depthwise_regularizer, "bias_regularizer": bias_regularizer},
+                       activity_regularizer,
+                       {"depthwise_constraint": depthwise_constraint, "bias_constraint": bias_constraint})
+        self.depthwise_initializer = depthwise_initializer
+        self.bias_initializer = bias_initializer
+
+    def compute_output_shape(self, s):
+        return self._out_hw(s) + (s[2],)
+
+    def weight_specs(self):
+        kh, kw = self.kernel_size
+        c = self.input_shape[-1]
+        specs = [("depthwise_kernel", (kh, kw, c, 1), self.depthwise_initializer)]
+        if self.use_bias:
+            specs.append(("bias", (c,), self.bias_initializer))
+        return specs
+
+    def get_config(self):
+        return self._conv_config()
+
+
+class SeparableConv2D(_DepthwiseBase):
+    """``keras.layers.SeparableConv2D`` (depth_multiplier 1): y = A(pointwise(depthwise(x)) + bias);
+    strides and padding belong to the depthwise part, which has no bias and no activation.  Weights:
+    ``depthwise_kernel`` (kh, kw, C, 1), ``pointwise_kernel`` (1, 1, C, filters), ``bias`` (filters,)."""
+    _REG_KEYS = (("depthwise", "depthwise_kernel"), ("pointwise", "pointwise_kernel"), ("bias", "bias"))
+    _CONFIG_KEYS = _DepthwiseBase._CONFIG_KEYS + ("filters",)
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None,
+                 dilation_rate=(1, 1), depth_multiplier=1, activation=None, use_bias=True,
+                 depthwise_initializer="glorot_uniform", pointwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, pointwise_regularizer=None,
+                 bias_regularizer=None, activity_regularizer=None, depthwise_constraint=None,
+                 pointwise_constraint=None, bias_constraint=None, **kw):
+        super().__init__(**kw)
+        self._set_conv(kernel_size, strides, padding, data_format, dilation_rate, depth_multiplier, activation,
+                       use_bias, {"depthwise_regularizer": depthwise_regularizer,
+                                  "pointwise_regularizer": pointwise_regularizer, "bias_regularizer": bias_regularizer},
+                       activity_regularizer,
+                       {"depthwise_constraint": depthwise_constraint, "pointwise_constraint": pointwise_constraint,
+                        "bias_constraint": bias_constraint})
+        self.filters = int(filters)
+        self.depthwise_initializer = depthwise_initializer
+        self.pointwise_initializer = pointwise_initializer
+        self.bias_initializer = bias_initializer
+
+    def compute_output_shape(self, s):
+        return self._out_hw(s) + (self.filters,)
+
+    def weight_specs(self):
+        kh, kw = self.kernel_size
+        c = self.input_shape[-1]
+        specs = [("depthwise_kernel", (kh, kw, c, 1), self.depthwise_initializer),
+                 ("pointwise_kernel", (1, 1, c, self.filters), self.pointwise_initializer)]
+        if self.use_bias:
+            specs.append(("bias", (self.filters,), self.bias_initializer))
+        return specs
+
+    def get_config(self):
+        cfg = self._conv_config()
+        cfg["filters"] = self.filters
+        return cfg
+
+
 class MaxPooling2D(Layer):
     def __init__(self, pool_size=(2, 2), strides=None, padding="valid", data_format=None, **kw):
         super().__init__(**kw)
@@ -547,4 +701,5 @@ def activation_of(layer):
 
 LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
                                          LeakyReLU, ELU, BatchNormalization, AveragePooling2D,
-                                         GlobalAveragePooling2D, GlobalMaxPooling2D)}
+                                         GlobalAveragePooling2D, GlobalMaxPooling2D, DepthwiseConv2D,
+                                         SeparableConv2D)}

@@ -25,6 +25,11 @@ kernel (with its relu) and the activation launch run un-pooled, and the pool.hip
 and drop.  A GlobalAveragePooling2D / GlobalMaxPooling2D in Flatten's place is a stage of its own
 without weights (``Plan.gpool``), with the Dropout behind it.
 
+A DepthwiseConv2D is a conv stage of its own (``depthwise``: Cout == Cin, never pooled, no dropout;
+depthwise.hip), and a SeparableConv2D expands into two stages: its linear, bias-free depthwise half and
+a 1x1 conv stage (``pointwise``) that owns the layer's pointwise_kernel / bias, its activation and
+whatever follows it by the rules above.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -33,8 +38,9 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
-                     GlobalAveragePooling2D, GlobalMaxPooling2D, InputLayer, Layer, LeakyReLU, MaxPooling2D, activation_of)
+from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, DepthwiseConv2D, Dropout,
+                     Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, InputLayer, Layer, LeakyReLU, MaxPooling2D,
+                     SeparableConv2D, activation_of)
 from ..ops.reference import conv_pads
 
 
@@ -51,6 +57,28 @@ class ConvStage:
     act: Optional[str] = None               # hidden activation other than relu / linear (None for those)
     act_alpha: float = 0.0
     bn: Optional[BatchNormalization] = None  # dropout(maxpool(A(BN(conv)))): the pool is NOT taken before BN
+    # a depthwise convolution (a DepthwiseConv2D layer, or the linear, bias-free first half of a
+    # SeparableConv2D): Cout == Cin, never pooled, no dropout.  ``pointwise``: the 1x1 second half of a
+    # SeparableConv2D, an ordinary conv stage over that layer's pointwise_kernel / bias
+    depthwise: bool = False
+    pointwise: bool = False
+
+    @property
+    def wname(self) -> str:
+        """The short name of the stage's kernel among ``conv``'s weights."""
+        return "depthwise_kernel" if self.depthwise else "pointwise_kernel" if self.pointwise else "kernel"
+
+    @property
+    def use_bias(self) -> bool:
+        return self.conv.use_bias and not (self.depthwise and isinstance(self.conv, SeparableConv2D))
+
+    @property
+    def kernel_size(self):
+        return (1, 1) if self.pointwise else tuple(self.conv.kernel_size)
+
+    @property
+    def padding(self) -> str:
+        return "valid" if self.pointwise else self.conv.padding
 
     @property
     def pool_kind(self) -> Optional[str]:
@@ -63,13 +91,13 @@ class ConvStage:
 
     @property
     def stride(self) -> int:
-        return self.conv.strides[0]
+        return 1 if self.pointwise else self.conv.strides[0]
 
     @property
     def pads(self):
         H, W, _ = self.in_shape
-        kh, kw = self.conv.kernel_size
-        return conv_pads(H, W, kh, kw, self.stride, self.conv.padding)
+        kh, kw = self.kernel_size
+        return conv_pads(H, W, kh, kw, self.stride, self.padding)
 
 
 @dataclass
@@ -176,6 +204,15 @@ def binary_accuracy_head(loss: str, N: int) -> bool:
 
 
 ACT_LAYERS = (Activation, LeakyReLU, ELU)
+CONV_LAYERS = (Conv2D, DepthwiseConv2D, SeparableConv2D)
+
+
+def _behind_depthwise(layer, stage):
+    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D: not implemented."""
+    if stage is not None and stage.depthwise:
+        raise NotImplementedError("layer %s follows %s: %s directly behind a DepthwiseConv2D is not implemented "
+                                  "(a Conv2D, SeparableConv2D, Flatten or global pooling layer may follow it)"
+                                  % (layer.name, stage.conv.name, type(layer).__name__))
 
 
 def _stage_act(layer, name, alpha, what):
@@ -209,7 +246,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
         if skip:                # the output Activation layer, taken by the head Dense before it
             skip = False
             continue
-        if not isinstance(layer, ACT_LAYERS + (Conv2D, Dense, BatchNormalization)):
+        if not isinstance(layer, ACT_LAYERS + CONV_LAYERS + (Dense, BatchNormalization)):
             open_stage = None
         if isinstance(layer, BatchNormalization):
             if isinstance(before, BatchNormalization):
@@ -219,7 +256,8 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 raise NotImplementedError("layer %s follows %s, the output Dense: BatchNormalization behind the "
                                           "output layer is not implemented"
                                           % (layer.name, (plan.head.dense if plan.head is not None else before).name))
-            if isinstance(before, (Conv2D, Dense)) and before.activation is not None:
+            _behind_depthwise(layer, cur_conv if isinstance(before, DepthwiseConv2D) else None)
+            if isinstance(before, CONV_LAYERS + (Dense,)) and before.activation is not None:
                 raise NotImplementedError("layer %s follows %s, which already has the activation %s: "
                                           "BatchNormalization must follow a linear Conv2D or Dense (put the "
                                           "activation behind it as a layer)"
@@ -232,7 +270,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
         elif isinstance(layer, ACT_LAYERS):
             name, alpha = activation_of(layer)
             if open_stage is None:
-                owner = before if isinstance(before, (Conv2D, Dense)) else None
+                owner = before if isinstance(before, CONV_LAYERS + (Dense,)) else None
                 if owner is not None and owner.activation is not None:
                     raise NotImplementedError("layer %s follows %s, which already has the activation %s: two "
                                               "activations on one stage" % (layer.name, owner.name, owner.activation))
@@ -246,22 +284,31 @@ def build_plan(layers: List[Layer], loss) -> Plan:
             stage.relu, stage.act, stage.act_alpha = _stage_act(layer, name, alpha, "hidden")
             if name is not None:
                 open_stage = None
-        elif isinstance(layer, Conv2D):
+        elif isinstance(layer, CONV_LAYERS):
             if plan.gpool is not None:
-                raise NotImplementedError("layer %s follows %s: Conv2D after a global pooling layer"
-                                          % (layer.name, plan.gpool.layer.name))
+                raise NotImplementedError("layer %s follows %s: %s after a global pooling layer"
+                                          % (layer.name, plan.gpool.layer.name, type(layer).__name__))
             if plan.denses or flat_from is not None:
-                raise NotImplementedError("Conv2D after Flatten/Dense")
+                raise NotImplementedError("%s after Flatten/Dense" % type(layer).__name__)
             relu, act, alpha = _stage_act(layer, layer.activation, 1.0 if layer.activation == "elu" else 0.0, "conv")
-            cur_conv = ConvStage(conv=layer, in_shape=tuple(layer.input_shape),
-                                 conv_shape=tuple(layer.output_shape_),
-                                 out_shape=tuple(layer.output_shape_), relu=relu, act=act, act_alpha=alpha)
+            in_shape, out_shape = tuple(layer.input_shape), tuple(layer.output_shape_)
+            if isinstance(layer, SeparableConv2D):
+                # two stages: the linear, bias-free depthwise half, then the 1x1 conv that owns the
+                # layer's activation and whatever follows it
+                mid = out_shape[:2] + in_shape[2:]
+                plan.convs.append(ConvStage(conv=layer, in_shape=in_shape, conv_shape=mid, out_shape=mid, relu=False,
+                                            depthwise=True))
+                in_shape = mid
+            cur_conv = ConvStage(conv=layer, in_shape=in_shape, conv_shape=out_shape, out_shape=out_shape, relu=relu,
+                                 act=act, act_alpha=alpha, depthwise=isinstance(layer, DepthwiseConv2D),
+                                 pointwise=isinstance(layer, SeparableConv2D))
             plan.convs.append(cur_conv)
             cur_dense = None
             open_stage = (cur_conv, layer) if layer.activation is None else None
         elif isinstance(layer, MaxPooling2D):       # (AveragePooling2D too)
             if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None or plan.gpool is not None:
                 raise NotImplementedError("%s must directly follow a Conv2D" % type(layer).__name__)
+            _behind_depthwise(layer, cur_conv)
             if isinstance(layer, AveragePooling2D) and cur_conv.bn is not None:
                 raise NotImplementedError("layer %s follows %s on the stage of %s: AveragePooling2D on a "
                                           "BatchNormalization stage is not implemented"
@@ -288,6 +335,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 tgt = plan.gpool
             if tgt is None:
                 raise NotImplementedError("Dropout directly on the model input")
+            _behind_depthwise(layer, tgt if tgt is cur_conv else None)
             if tgt.dropout is not None:
                 raise NotImplementedError("two consecutive Dropout layers")
             tgt.dropout = layer

@@ -47,13 +47,14 @@ class Stage:
     act_alpha: float = 0.0
     bn: Optional[object] = None    # the stage's BatchNormalization layer
     avg: bool = False              # a conv stage with an AveragePooling2D: dropout(avgpool(A(conv)))
+    depthwise: bool = False        # a depthwise conv stage (depthwise.hip): no pack, never pooled, no dropout
     lin_grid = out_grid = (1, 1)
 
     @classmethod
     def of(cls, st, *geo):
         """The record of plan stage ``st`` with the positional geometry ``geo``."""
         return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn,
-                   avg=getattr(st, "pool_kind", None) == "avg")
+                   avg=getattr(st, "pool_kind", None) == "avg", depthwise=getattr(st, "depthwise", False))
 
     @property
     def tag(self):
@@ -69,7 +70,7 @@ class Stage:
         """Neither a table activation nor a BatchNormalization nor an average pool: the linear kernels
         are the whole stage (the condition for the conv stack and for the head launch running the
         epilogue)."""
-        return self.act is None and self.bn is None and not self.avg
+        return self.act is None and self.bn is None and not self.avg and not self.depthwise
 
     @property
     def dropout_in(self):
@@ -175,12 +176,13 @@ def stage_geometry(plan, head_max=16):
         Ho, Wo, Cout = cs.conv_shape
         Hp, Wp, _ = cs.out_shape
         pt, _, pl, _ = cs.pads
-        kh, kw = cs.conv.kernel_size
+        kh, kw = cs.kernel_size
+        # (a depthwise stage: Cs_out == Cs_in, except behind a model input of <= 4 channels, 4 -> 8)
         g = ConvGeo.of(cs, i, H, W, Cin, Cs_in, Ho, Wo, Cout, r8(Cout), Hp, Wp, kh, kw, cs.stride, pt, pl,
                        cs.pool is not None and getattr(cs, "pool_kind", "max") == "max")
         g.KS = cdiv(kh * kw * Cs_in, 32)
         g.NT = cdiv(Cout, 16)
-        if i > 0:
+        if i > 0 and not g.depthwise:
             g.KSd = cdiv(kh * kw * g.Cs_out, 32)
             g.NTd = cdiv(Cin, 16)
         convs.append(g)

@@ -67,6 +67,30 @@ def conv2d_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: 
     return (xr.grad if need_dx else None), wr.grad, db
 
 
+def depthwise_conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int = 1,
+                     padding: str = "valid") -> torch.Tensor:
+    """x [B,H,W,C], w [KH,KW,C,1] (depth_multiplier 1) -> y [B,Ho,Wo,C] (no activation)."""
+    kh, kw, c = w.shape[0], w.shape[1], w.shape[2]
+    pt, pb, pl, pr = conv_pads(x.shape[1], x.shape[2], kh, kw, stride, padding)
+    xn = x.permute(0, 3, 1, 2)
+    if pt or pb or pl or pr:
+        xn = F.pad(xn, (pl, pr, pt, pb))
+    y = F.conv2d(xn, w.permute(2, 3, 0, 1), b, stride=stride, groups=c)
+    return y.permute(0, 2, 3, 1)
+
+
+def depthwise_conv2d_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: int,
+                              padding: str, need_dx: bool = True):
+    """Returns (dx or None, dw [KH,KW,C,1], db [C])."""
+    with torch.enable_grad():
+        xr = x.detach().clone().requires_grad_(need_dx)
+        wr = w.detach().clone().requires_grad_(True)
+        y = depthwise_conv2d(xr, wr, None, stride, padding)
+        y.backward(dy)
+    db = dy.sum(dim=(0, 1, 2))
+    return (xr.grad if need_dx else None), wr.grad, db
+
+
 # --------------------------------------------------------------------------- pool
 def maxpool2x2(x: torch.Tensor):
     """2x2/2 valid max-pool on NHWC.  Returns (y, code) where code in {0..3} is the
