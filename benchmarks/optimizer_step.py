@@ -4,7 +4,7 @@
                                         [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
                                         [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
-                                        [--loss NAME[,NAME..]] [--separable]
+                                        [--loss NAME[,NAME..]] [--separable] [--dilated]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -52,6 +52,10 @@ head's place, and the end-of-step slab reduction of its K x N gradient.
 Conv2D except the first is a SeparableConv2D -- per conv layer behind the first ``dw_fwd`` and a 1x1
 ``conv_fwd`` in the 3x3 conv's place, ``dw_wgrad`` / ``dw_dgrad`` and the 1x1 stage's backward).
 
+``--dilated`` adds ``<name>/unstacked`` likewise and ``<name>/dilated`` (``zoo.rpv_context_cnn``: 3x3 convs
+at dilations 1, 2, 4 over the full 64x64 grid and a global average pool -- ``dil_fwd`` / ``dil_wgrad`` /
+``dil_dgrad`` for the two dilated layers).
+
 ``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
 them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
 ``<name>/weighted-data`` (the default model on sample-weighted data: the weighted head instances, no new
@@ -88,7 +92,7 @@ def make_opt(name, **kw):
 
 
 def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
-             metrics=None, weighted_metrics=None, losses=(), separable=False):
+             metrics=None, weighted_metrics=None, losses=(), separable=False, dilated=False):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
     "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
@@ -110,7 +114,7 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/l2", nm, {}, None, l2, "relu"))
         if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
-        if pool != "max" or global_pool or separable:
+        if pool != "max" or global_pool or separable or dilated:
             out.append((nm + "/unstacked", nm, {}, UNSTACKED, 0.0, "relu"))
         if pool != "max":
             out.append((nm + "/pool-" + pool, nm, {}, None, 0.0, "relu+pool=" + pool))
@@ -118,6 +122,8 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/gpool-" + global_pool, nm, {}, None, 0.0, "relu+gpool=" + global_pool))
         if separable:
             out.append((nm + "/separable", nm, {}, None, 0.0, "relu+separable"))
+        if dilated:
+            out.append((nm + "/dilated", nm, {}, None, 0.0, "relu+dilated"))
         if batch_norm:
             out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
@@ -166,6 +172,7 @@ def main():
     ap.add_argument("--global-pool", choices=["avg", "max"], default=None,
                     help="time the model with a global pooling layer in the Flatten's place")
     ap.add_argument("--separable", action="store_true", help="time rpv_cnn(separable=True)")
+    ap.add_argument("--dilated", action="store_true", help="time zoo.rpv_context_cnn (dilations 1, 2, 4)")
     ap.add_argument("--loss", default="", metavar="NAME[,NAME]",
                     help="time the model with these Keras losses in binary_crossentropy's place (the loss head), "
                          "and the default model under fuse_head=0 (the same structure with the first head kernel)")
@@ -176,7 +183,7 @@ def main():
     split = lambda t: [n for n in t.split(",") if n]
     var = [v if len(v) == 7 else v + ({},) for v in
            variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
-                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable)]
+                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable, a.dilated)]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -188,14 +195,16 @@ def main():
     for nm, oname, kw, tv, l2, act, extra in var:
         set_random_seed(1)
         with tuned(tv):
-            m = zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
+            m = (zoo.rpv_context_cnn((64, 64, 3), dropout=0.2, optimizer=make_opt(oname, **kw), lr=None, device="cuda:0")
+                 if act == "relu+dilated" else
+                 zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
                             optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
                             **({"batch_norm": True} if act == "relu+bn" else {}),
                             **({"separable": True} if act == "relu+separable" else {}),
                             **({"pool": act.split("=")[1]} if act.startswith("relu+pool=") else {}),
                             **({"global_pool": act.split("=")[1]} if act.startswith("relu+gpool=") else {}),
                             **({"activation": act} if not act.startswith("relu") else {}),
-                            **{k: v for k, v in extra.items() if k != "weighted_data"})
+                            **{k: v for k, v in extra.items() if k != "weighted_data"}))
         ex = m._executor
         yv = y if extra.get("outputs", 1) == 1 else (rs.rand(bs * REPLAY, extra["outputs"]) > 0.5).astype(np.float32)
         d = ex.upload(x, yv, w) if extra.get("weighted_data") else ex.upload(x, yv)

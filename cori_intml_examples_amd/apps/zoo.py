@@ -169,6 +169,29 @@ def rpv_cnn(input_shape, conv_sizes=(8, 16, 32), fc_sizes=(64,), dropout=0.5, op
     return model
 
 
+def rpv_context_cnn(input_shape, dilations=(1, 2, 4), filters=(16, 32, 64), dense=(128,), dropout=0.5, optimizer="Adam",
+                    lr=0.001, use_horovod=False, device=None, activation="relu", l2=0.0):
+    """A context-aggregation classifier for the RPV images: one same-padded 3x3 Conv2D per entry of
+    ``dilations`` (its dilation_rate; 1 is an ordinary Conv2D) with ``filters`` channels -- the receptive
+    field grows without pooling resolution away -- then GlobalAveragePooling2D, ``[Dense, Dropout]`` per
+    entry of ``dense`` and the sigmoid output; BCE + accuracy.  ``activation`` / ``l2`` / ``lr`` /
+    ``optimizer``: as in the other builders."""
+    if len(dilations) != len(filters):
+        raise ValueError("dilations %r and filters %r differ in length" % (tuple(dilations), tuple(filters)))
+    reg = _kernel_l2(l2)
+    h = inputs = Input(shape=input_shape)
+    for d, c in zip(dilations, filters):
+        h = Conv2D(c, kernel_size=(3, 3), padding="same", dilation_rate=d, activation=activation, **reg)(h)
+    h = GlobalAveragePooling2D()(h)
+    for f in dense:
+        h = Dense(f, activation=activation, **reg)(h)
+        h = Dropout(dropout)(h)
+    outputs = Dense(1, activation="sigmoid", **reg)(h)
+    model = Model(inputs=inputs, outputs=outputs, name="RPVContextClassifier", device=device)
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
+    return model
+
+
 def rpv_legacy_cnn(input_shape=(64, 64, 1), optimizer="Adam", lr=None, h1=64, h2=128, h3=256, h4=256, h5=512,
                    use_horovod=False, device=None, activation="relu", batch_norm=False, pool="max",
                    global_pool=None, metrics=None, weighted_metrics=None, loss=None, separable=False):

@@ -79,6 +79,12 @@ void launch_dw_dgrad(const DwArgs& a, hipStream_t s);
 void launch_dw_wgrad(const DwArgs& a, hipStream_t s);
 int dw_rows(const DwArgs& a, int kind, int want);
 size_t dw_lds_bytes(const DwArgs& a, int kind, int R);
+void launch_dil_fwd(const DilArgs& a, hipStream_t s);
+void launch_dil_dgrad(const DilArgs& a, hipStream_t s);
+void launch_dil_wgrad(const DilArgs& a, hipStream_t s);
+std::tuple<int, int> dil_cfg(const DilArgs& a, int kind, int want);
+size_t dil_lds_bytes(const DilArgs& a, int kind, int R, int kc);
+int dil_ntw(int n, int kind);
 void launch_roc_accum(const RocArgs& a, hipStream_t s);
 void launch_roc_finish(const RocArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
@@ -608,6 +614,25 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("dw_fwd", [](const DwArgs& a, uintptr_t s) { launch_dw_fwd(a, S(s)); check_last("dw_fwd"); });
   m.def("dw_dgrad", [](const DwArgs& a, uintptr_t s) { launch_dw_dgrad(a, S(s)); check_last("dw_dgrad"); });
   m.def("dw_wgrad", [](const DwArgs& a, uintptr_t s) { launch_dw_wgrad(a, S(s)); check_last("dw_wgrad"); });
+  // dilated convolution (dilated.hip): forward, input gradient, weight gradient slabs
+  py::class_<DilArgs>(m, "DilArgs")
+      .def(py::init<>())
+      PTR(DilArgs, x) PTR(DilArgs, w) PTR(DilArgs, bias) PTR(DilArgs, out) PTR(DilArgs, dt) RW(DilArgs, B) RW(DilArgs, H)
+      RW(DilArgs, W) RW(DilArgs, Cin) RW(DilArgs, Cs_in) RW(DilArgs, Ho) RW(DilArgs, Wo) RW(DilArgs, Cout) RW(DilArgs, Cs_out)
+      RW(DilArgs, KH) RW(DilArgs, KW) RW(DilArgs, dil) RW(DilArgs, stride) RW(DilArgs, pad_t) RW(DilArgs, pad_l)
+      RW(DilArgs, relu) RW(DilArgs, R) RW(DilArgs, ntw) RW(DilArgs, kc) RW(DilArgs, xpix) RW(DilArgs, bt) PTR(DilArgs, st)
+      PTR(DilArgs, slab) RW(DilArgs, slab_ld) RW(DilArgs, S) RW(DilArgs, pairs_per_slab) RW(DilArgs, has_bias);
+  m.attr("DIL_FWD") = DIL_FWD;
+  m.attr("DIL_DGRAD") = DIL_DGRAD;
+  m.attr("DIL_WGRAD") = DIL_WGRAD;
+  m.attr("DIL_MTW") = DIL_MTW;
+  m.attr("DIL_LDS_BUDGET") = DIL_LDS_BUDGET;
+  m.def("dil_cfg", &dil_cfg);
+  m.def("dil_lds_bytes", &dil_lds_bytes);
+  m.def("dil_ntw", &dil_ntw);
+  m.def("dil_fwd", [](const DilArgs& a, uintptr_t s) { launch_dil_fwd(a, S(s)); check_last("dil_fwd"); });
+  m.def("dil_dgrad", [](const DilArgs& a, uintptr_t s) { launch_dil_dgrad(a, S(s)); check_last("dil_dgrad"); });
+  m.def("dil_wgrad", [](const DilArgs& a, uintptr_t s) { launch_dil_wgrad(a, S(s)); check_last("dil_wgrad"); });
   // ROC / AUC, purity, efficiency and weighted metrics (roc.hip): roc_accum behind the head in a step,
   // roc_finish once when the metrics are read
   py::class_<RocArgs>(m, "RocArgs")

@@ -41,6 +41,7 @@ from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin
+from .lds_layout import conv_layout
 from .plan import Plan, binary_accuracy_head, classic_head
 from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
                            cdiv, check_bucket_cover, defer_after_readers, dropout_pair, gpool_geometry,
@@ -253,7 +254,7 @@ class HipExecutor(Executor):
             return o
 
         for g, cs in zip(self.convs, self.plan.convs):
-            if g.depthwise:         # (depthwise.hip reads the fp32 master: no pack, no route)
+            if g.unpacked:          # (depthwise.hip / dilated.hip read the fp32 master: no pack, no route)
                 continue
             sp = st.spec(cs.conv, cs.wname)
             g.pack_fwd = alloc(g.KS, g.NT)
@@ -275,7 +276,7 @@ class HipExecutor(Executor):
         # copies into these packs itself, so a training step needs no re-pack pass
         routes = []
         for g, cs in zip(self.convs, self.plan.convs):
-            if g.depthwise:
+            if g.unpacked:
                 continue
             sp = st.spec(cs.conv, cs.wname)
             bwd = g.pack_dgrad if g.i > 0 and g.Cs_out % 4 == 0 else -1
@@ -988,6 +989,15 @@ class BatchPlan(GeometryMixin):
             return
         x_buf = self.xb
         for g, cs in zip(ex.convs, ex.plan.convs):
+            if g.dilated:
+                da = self._dil_args(g, cs, ex.K.DIL_FWD, "dil_fwd")
+                da.x = x_buf.data_ptr()
+                da.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
+                da.out, da.relu = self.stage_bufs(g).lin_out.data_ptr(), int(g.relu)
+                self._add("dil_fwd%d" % g.i, lambda s, a=da: K.dil_fwd(a, s), dil=da)
+                self._add_stage_tail_fwd(g)
+                x_buf = self.stage_bufs(g).out
+                continue
             if g.depthwise:
                 da = self._dw_args(g, cs, x_buf)
                 self._add("dw_fwd%d" % g.i, lambda s, a=da: K.dw_fwd(a, s), dw=da)
@@ -1298,6 +1308,8 @@ class BatchPlan(GeometryMixin):
         xin = self.xb if g.i == 0 else self.conv_out[g.i - 1]
         if g.depthwise:
             return self._build_dw_bwd(g, cs, xin)
+        if g.dilated:
+            return self._build_dil_bwd(g, cs, xin)
         # (a BatchNormalization stage: conv_dy holds the dense un-pooled dz of bn_bwd_apply)
         g_stage, g = g, g.linear
         wide = self._wide(g.Cs_in, g.KS, g.NT)
@@ -1402,6 +1414,71 @@ class BatchPlan(GeometryMixin):
             da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
             da.st = ex.state.data_ptr()
             self._add("dw_dgrad%d" % g.i, lambda s, a=da: K.dw_dgrad(a, s), dw=da)
+            self._add_stage_tail_bwd(ex.convs[g.i - 1])
+
+    def _dil_args(self, g, cs, kind, name):
+        """The DilArgs of one of dilated stage g's launches (dilated.hip): its geometry, the fp32 master
+        kernel, and the launch's configuration -- n-tiles per workgroup, the halo's pixel stride
+        (lds_layout.conv_layout where it fits: the A-fragment reads are conv_halo_body's, tap-shifted), rows per block
+        and the weight chunk (dil_cfg, under the LDS budget and the minimum-workgroup tune)."""
+        ex, K = self.ex, self.ex.K
+        a = K.DilArgs()
+        a.w = ex.store.view(cs.conv, cs.wname).data_ptr()
+        a.B, a.H, a.W, a.Cin, a.Cs_in = self.bs, g.H, g.W, g.Cin, g.Cs_in
+        a.Ho, a.Wo, a.Cout, a.Cs_out = g.Ho, g.Wo, g.Cout, g.Cs_out
+        a.KH, a.KW, a.dil, a.stride, a.pad_t, a.pad_l = g.KH, g.KW, g.dilation, g.stride, g.pad_t, g.pad_l
+        dgrad = kind == K.DIL_DGRAD
+        ck, wr = (g.Cs_out, g.W) if dgrad else (g.Cs_in, g.Wo)
+        a.ntw = K.dil_ntw(g.Cin if dgrad else g.Cout, kind)
+        # (the conflict-free stride where it costs no rows per block, else the dense one: at large dilations
+        # the halo's ke_h - 1 extra rows are re-staged by every block, which outweighs bank conflicts)
+        best = None
+        for xpix in (conv_layout(ck, wr + (g.KW - 1) * g.dilation, wr, False, g.KH, g.KW), ck):
+            a.xpix = xpix
+            R, kc = K.dil_cfg(a, kind, int(tune("halo_min_wgs")))
+            if best is None or R > best[0]:
+                best = (R, kc, xpix)
+        a.R, a.kc, a.xpix = best
+        if a.R <= 0:
+            raise NotImplementedError("layer %s (%s%d): one row of its halo over all %d channels, %d bytes, exceeds the "
+                                      "dilated kernels' %d bytes of LDS (no channel chunking)"
+                                      % (cs.conv.name, name, g.i, ck, K.dil_lds_bytes(a, kind, 1, 0 if kind == K.DIL_WGRAD else min(2, cdiv(g.KH * g.KW * ck, 32))),
+                                         K.DIL_LDS_BUDGET))
+        return a
+
+    def _build_dil_bwd(self, g, cs, xin):
+        """A dilated stage's backward: dil_wgrad into one slab row per workgroup (its reduction group: the
+        kernel in Keras order and the bias, as identity descriptors) and, unless it is the first stage,
+        dil_dgrad through the feeding stage's BwdThrough."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        bufs = self.stage_bufs(g)
+        wa = self._dil_args(g, cs, K.DIL_WGRAD, "dil_wgrad")
+        wa.x, wa.dt, wa.has_bias = xin.data_ptr(), bufs.dz.data_ptr(), int(cs.use_bias)
+        sp = store.spec(cs.conv, cs.wname)
+        bsp = store.spec(cs.conv, "bias") if cs.use_bias else None
+        bias_off = cdiv(sp.numel, 4) * 4
+        wa.slab_ld = bias_off + (cdiv(g.Cout, 4) * 4 if cs.use_bias else 0)
+        # about one resident round of workgroups, over the launch's (m group, n group) grid
+        npairs = self.bs * cdiv(g.Ho, wa.R)
+        per = cdiv(cdiv(g.KH * g.KW * g.Cs_in, 16), 4 * K.DIL_MTW) * cdiv(cdiv(g.Cout, 16), wa.ntw)
+        S = max(1, min(npairs, cdiv(2 * self._cu_count(), per)))
+        wa.pairs_per_slab = cdiv(npairs, S)
+        wa.S = S = cdiv(npairs, wa.pairs_per_slab)
+        slab = torch.zeros(S, wa.slab_ld, dtype=torch.float32, device=ex.device)
+        wa.slab = slab.data_ptr()
+        self.wgrad_slabs.append((slab, None))
+        self._add("dil_wgrad%d" % g.i, lambda s, a=wa: K.dil_wgrad(a, s), "side", dil=wa)
+        descs = [RedDesc(slab.data_ptr(), wa.slab_ld, S, g.Cout, sp.offset, sp.numel, RED_BIAS)]
+        if bsp is not None:
+            descs.append(RedDesc(slab.data_ptr() + 4 * bias_off, wa.slab_ld, S, g.Cout, bsp.offset, bsp.numel,
+                                 RED_BIAS))
+        self._add_group(sp, descs, bsp)
+        if g.i > 0:
+            da = self._dil_args(g, cs, K.DIL_DGRAD, "dil_dgrad")
+            da.dt = bufs.dz.data_ptr()
+            da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
+            da.st = ex.state.data_ptr()
+            self._add("dil_dgrad%d" % g.i, lambda s, a=da: K.dil_dgrad(a, s), dil=da)
             self._add_stage_tail_bwd(ex.convs[g.i - 1])
 
     # ---------------------------------------------------------------- step program: reductions

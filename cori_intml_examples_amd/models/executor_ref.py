@@ -135,7 +135,8 @@ class RefExecutor(Executor):
             # (a SeparableConv2D is two stages: its bias-free depthwise half, then its 1x1 conv)
             w = self._q(st.view(cs.conv, cs.wname))
             b = st.view(cs.conv, "bias") if cs.use_bias else None
-            z = (R.depthwise_conv2d if cs.depthwise else R.conv2d)(a, w, b, cs.stride, cs.padding)
+            z = (R.depthwise_conv2d(a, w, b, cs.stride, cs.padding) if cs.depthwise
+                 else R.conv2d(a, w, b, cs.stride, cs.padding, cs.dilation))
             z_code = z
             if cs.bn is not None:
                 # z is stored (bf16) before the statistics; everything behind it acts on u = BN(z),
@@ -288,7 +289,8 @@ class RefExecutor(Executor):
             if cs.bn is not None:
                 da = self._bn_backward(cs.bn, da, self._bn_ctx[id(cs)])
             bwd = R.depthwise_conv2d_backward if cs.depthwise else R.conv2d_backward
-            dx, dw, db = bwd(a_in, self._q(st.view(cs.conv, cs.wname)), da, cs.stride, cs.padding, need_dx=i > 0)
+            dx, dw, db = bwd(a_in, self._q(st.view(cs.conv, cs.wname)), da, cs.stride, cs.padding, need_dx=i > 0,
+                             **({} if cs.depthwise else {"dilation": cs.dilation}))
             st.view(cs.conv, cs.wname, grad=True).copy_(dw)
             if cs.use_bias:
                 st.view(cs.conv, "bias", grad=True).copy_(db)

@@ -221,8 +221,16 @@ class Conv2D(_Regularized, Layer):
         self.strides = _pair(strides)
         if self.strides[0] != self.strides[1]:
             raise NotImplementedError("anisotropic strides")
-        if _pair(dilation_rate) != (1, 1):
-            raise NotImplementedError("dilated convolutions")
+        self.dilation_rate = _pair(dilation_rate)
+        if self.dilation_rate[0] != self.dilation_rate[1]:
+            raise NotImplementedError("layer %s (Conv2D): anisotropic dilation_rate = %r is not implemented"
+                                      % (self.name, tuple(self.dilation_rate)))
+        if self.dilation_rate[0] < 1:
+            raise ValueError("layer %s (Conv2D): dilation_rate = %r" % (self.name, tuple(self.dilation_rate)))
+        if self.dilation_rate[0] > 1 and self.strides[0] > 1:       # (Keras' own rule)
+            raise ValueError("layer %s (Conv2D): strides = %r with dilation_rate = %r: specifying any stride value != 1 "
+                             "is incompatible with specifying any dilation_rate value != 1"
+                             % (self.name, tuple(self.strides), tuple(self.dilation_rate)))
         if data_format not in (None, "channels_last"):
             raise NotImplementedError("only channels_last (reference forces it, mnist.py:30)")
         padding = padding.lower()
@@ -240,9 +248,13 @@ class Conv2D(_Regularized, Layer):
         if len(s) != 3:
             raise ValueError("Conv2D expects (H, W, C) inputs, got %s" % (s,))
         kh, kw = self.kernel_size
-        st = self.strides[0]
-        return (conv_out_size(s[0], kh, st, self.padding), conv_out_size(s[1], kw, st, self.padding),
-                self.filters)
+        st, d = self.strides[0], self.dilation_rate[0]
+        out = (conv_out_size(s[0], kh, st, self.padding, d), conv_out_size(s[1], kw, st, self.padding, d), self.filters)
+        if d > 1 and min(out[:2]) <= 0:
+            raise ValueError("layer %s (Conv2D): a %dx%d kernel at dilation_rate %d spans %dx%d pixels, more than its "
+                             "valid-padded %dx%d input" % (self.name, kh, kw, d, (kh - 1) * d + 1, (kw - 1) * d + 1,
+                                                           s[0], s[1]))
+        return out
 
     def weight_specs(self):
         kh, kw = self.kernel_size
@@ -256,7 +268,7 @@ class Conv2D(_Regularized, Layer):
         cfg = super().get_config()
         cfg.update({"filters": self.filters, "kernel_size": list(self.kernel_size),
                     "strides": list(self.strides), "padding": self.padding,
-                    "data_format": "channels_last", "dilation_rate": [1, 1],
+                    "data_format": "channels_last", "dilation_rate": list(self.dilation_rate),
                     "activation": self.activation or "linear", "use_bias": self.use_bias,
                     "kernel_initializer": {"class_name": "VarianceScaling", "config": {
                         "scale": 1.0, "mode": "fan_avg", "distribution": "uniform", "seed": None}},
@@ -270,7 +282,10 @@ class Conv2D(_Regularized, Layer):
     def from_config(cls, cfg):
         cfg = {k: v for k, v in cfg.items() if k in (
             "name", "trainable", "filters", "kernel_size", "strides", "padding", "activation",
-            "use_bias", "batch_input_shape", "kernel_regularizer", "bias_regularizer", "activity_regularizer")}
+            "use_bias", "batch_input_shape", "kernel_regularizer", "bias_regularizer", "activity_regularizer",
+            "dilation_rate")}
+        if "dilation_rate" in cfg:
+            cfg["dilation_rate"] = tuple(_pair(cfg["dilation_rate"]))
         return super().from_config(cfg)
 
 

@@ -30,6 +30,9 @@ depthwise.hip), and a SeparableConv2D expands into two stages: its linear, bias-
 a 1x1 conv stage (``pointwise``) that owns the layer's pointwise_kernel / bias, its activation and
 whatever follows it by the rules above.
 
+A Conv2D with dilation_rate > 1 is a conv stage of its own kind too (``dilated``: never pooled, no
+dropout, out of the conv stack; dilated.hip), with the same rules for what may follow it.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -62,6 +65,21 @@ class ConvStage:
     # SeparableConv2D, an ordinary conv stage over that layer's pointwise_kernel / bias
     depthwise: bool = False
     pointwise: bool = False
+
+    @property
+    def dilation(self) -> int:
+        """The stage's dilation rate (1: none; only a Conv2D has one)."""
+        return 1 if self.depthwise or self.pointwise else getattr(self.conv, "dilation_rate", (1, 1))[0]
+
+    @property
+    def dilated(self) -> bool:
+        """A Conv2D with dilation_rate > 1: a stage of the dilated.hip kernels."""
+        return self.dilation > 1
+
+    @property
+    def unfused(self) -> Optional[str]:
+        """What kind of stage has no fused pool / BatchNormalization / Dropout behind it, or None."""
+        return "DepthwiseConv2D" if self.depthwise else "dilated Conv2D" if self.dilated else None
 
     @property
     def wname(self) -> str:
@@ -97,7 +115,7 @@ class ConvStage:
     def pads(self):
         H, W, _ = self.in_shape
         kh, kw = self.kernel_size
-        return conv_pads(H, W, kh, kw, self.stride, self.padding)
+        return conv_pads(H, W, kh, kw, self.stride, self.padding, self.dilation)
 
 
 @dataclass
@@ -207,12 +225,13 @@ ACT_LAYERS = (Activation, LeakyReLU, ELU)
 CONV_LAYERS = (Conv2D, DepthwiseConv2D, SeparableConv2D)
 
 
-def _behind_depthwise(layer, stage):
-    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D: not implemented."""
-    if stage is not None and stage.depthwise:
-        raise NotImplementedError("layer %s follows %s: %s directly behind a DepthwiseConv2D is not implemented "
+def _behind_unfused(layer, stage):
+    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D or a dilated Conv2D:
+    not implemented (their kernels have no such epilogues)."""
+    if stage is not None and stage.unfused:
+        raise NotImplementedError("layer %s follows %s: %s directly behind a %s is not implemented "
                                   "(a Conv2D, SeparableConv2D, Flatten or global pooling layer may follow it)"
-                                  % (layer.name, stage.conv.name, type(layer).__name__))
+                                  % (layer.name, stage.conv.name, type(layer).__name__, stage.unfused))
 
 
 def _stage_act(layer, name, alpha, what):
@@ -256,7 +275,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 raise NotImplementedError("layer %s follows %s, the output Dense: BatchNormalization behind the "
                                           "output layer is not implemented"
                                           % (layer.name, (plan.head.dense if plan.head is not None else before).name))
-            _behind_depthwise(layer, cur_conv if isinstance(before, DepthwiseConv2D) else None)
+            _behind_unfused(layer, cur_conv if before is getattr(cur_conv, "conv", None) else None)
             if isinstance(before, CONV_LAYERS + (Dense,)) and before.activation is not None:
                 raise NotImplementedError("layer %s follows %s, which already has the activation %s: "
                                           "BatchNormalization must follow a linear Conv2D or Dense (put the "
@@ -308,7 +327,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
         elif isinstance(layer, MaxPooling2D):       # (AveragePooling2D too)
             if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None or plan.gpool is not None:
                 raise NotImplementedError("%s must directly follow a Conv2D" % type(layer).__name__)
-            _behind_depthwise(layer, cur_conv)
+            _behind_unfused(layer, cur_conv)
             if isinstance(layer, AveragePooling2D) and cur_conv.bn is not None:
                 raise NotImplementedError("layer %s follows %s on the stage of %s: AveragePooling2D on a "
                                           "BatchNormalization stage is not implemented"
@@ -335,7 +354,7 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 tgt = plan.gpool
             if tgt is None:
                 raise NotImplementedError("Dropout directly on the model input")
-            _behind_depthwise(layer, tgt if tgt is cur_conv else None)
+            _behind_unfused(layer, tgt if tgt is cur_conv else None)
             if tgt.dropout is not None:
                 raise NotImplementedError("two consecutive Dropout layers")
             tgt.dropout = layer

@@ -48,13 +48,15 @@ class Stage:
     bn: Optional[object] = None    # the stage's BatchNormalization layer
     avg: bool = False              # a conv stage with an AveragePooling2D: dropout(avgpool(A(conv)))
     depthwise: bool = False        # a depthwise conv stage (depthwise.hip): no pack, never pooled, no dropout
+    dilation: int = 1              # > 1: a dilated conv stage (dilated.hip): no pack, never pooled, no dropout
     lin_grid = out_grid = (1, 1)
 
     @classmethod
     def of(cls, st, *geo):
         """The record of plan stage ``st`` with the positional geometry ``geo``."""
         return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn,
-                   avg=getattr(st, "pool_kind", None) == "avg", depthwise=getattr(st, "depthwise", False))
+                   avg=getattr(st, "pool_kind", None) == "avg", depthwise=getattr(st, "depthwise", False),
+                   dilation=getattr(st, "dilation", 1))
 
     @property
     def tag(self):
@@ -66,11 +68,21 @@ class Stage:
         return Src(self.kind, self.idx, self.C, self.Cs, *self.out_grid)
 
     @property
+    def dilated(self):
+        return self.dilation > 1
+
+    @property
+    def unpacked(self):
+        """A stage whose kernels read the fp32 master weights themselves (depthwise.hip, dilated.hip): no
+        bf16 weight pack, no pack route."""
+        return self.depthwise or self.dilated
+
+    @property
     def plain(self):
         """Neither a table activation nor a BatchNormalization nor an average pool: the linear kernels
         are the whole stage (the condition for the conv stack and for the head launch running the
         epilogue)."""
-        return self.act is None and self.bn is None and not self.avg and not self.depthwise
+        return self.act is None and self.bn is None and not self.avg and not self.unpacked
 
     @property
     def dropout_in(self):
@@ -182,7 +194,7 @@ def stage_geometry(plan, head_max=16):
                        cs.pool is not None and getattr(cs, "pool_kind", "max") == "max")
         g.KS = cdiv(kh * kw * Cs_in, 32)
         g.NT = cdiv(Cout, 16)
-        if i > 0 and not g.depthwise:
+        if i > 0 and not g.unpacked:
             g.KSd = cdiv(kh * kw * g.Cs_out, 32)
             g.NTd = cdiv(Cin, 16)
         convs.append(g)

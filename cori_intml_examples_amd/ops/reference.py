@@ -21,7 +21,9 @@ EPS = 1e-7  # keras.backend.epsilon()
 
 
 # --------------------------------------------------------------------------- conv geometry
-def conv_out_size(n: int, k: int, s: int, padding: str) -> int:
+def conv_out_size(n: int, k: int, s: int, padding: str, dilation: int = 1) -> int:
+    """``dilation``: the taps lie ``dilation`` apart, the effective extent is (k - 1) * dilation + 1."""
+    k = (k - 1) * dilation + 1
     if padding == "same":
         return -(-n // s)
     return (n - k) // s + 1
@@ -34,7 +36,8 @@ def same_pad(n: int, k: int, s: int) -> Tuple[int, int]:
     return total // 2, total - total // 2
 
 
-def conv_pads(h: int, w: int, kh: int, kw: int, s: int, padding: str):
+def conv_pads(h: int, w: int, kh: int, kw: int, s: int, padding: str, dilation: int = 1):
+    kh, kw = (kh - 1) * dilation + 1, (kw - 1) * dilation + 1
     if padding == "same":
         pt, pb = same_pad(h, kh, s)
         pl, pr = same_pad(w, kw, s)
@@ -44,24 +47,24 @@ def conv_pads(h: int, w: int, kh: int, kw: int, s: int, padding: str):
 
 # --------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int = 1,
-           padding: str = "valid") -> torch.Tensor:
-    """x [B,H,W,C], w [KH,KW,C,Co] -> y [B,Ho,Wo,Co] (no activation)."""
+           padding: str = "valid", dilation: int = 1) -> torch.Tensor:
+    """x [B,H,W,C], w [KH,KW,C,Co] -> y [B,Ho,Wo,Co] (no activation); ``dilation``: Keras' dilation_rate."""
     kh, kw = w.shape[0], w.shape[1]
-    pt, pb, pl, pr = conv_pads(x.shape[1], x.shape[2], kh, kw, stride, padding)
+    pt, pb, pl, pr = conv_pads(x.shape[1], x.shape[2], kh, kw, stride, padding, dilation)
     xn = x.permute(0, 3, 1, 2)
     if pt or pb or pl or pr:
         xn = F.pad(xn, (pl, pr, pt, pb))
-    y = F.conv2d(xn, w.permute(3, 2, 0, 1), b, stride=stride)
+    y = F.conv2d(xn, w.permute(3, 2, 0, 1), b, stride=stride, dilation=dilation)
     return y.permute(0, 2, 3, 1)
 
 
 def conv2d_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: int,
-                    padding: str, need_dx: bool = True):
+                    padding: str, need_dx: bool = True, dilation: int = 1):
     """Returns (dx or None, dw [KH,KW,C,Co], db [Co])."""
     with torch.enable_grad():
         xr = x.detach().clone().requires_grad_(need_dx)
         wr = w.detach().clone().requires_grad_(True)
-        y = conv2d(xr, wr, None, stride, padding)
+        y = conv2d(xr, wr, None, stride, padding, dilation)
         y.backward(dy)
     db = dy.sum(dim=(0, 1, 2))
     return (xr.grad if need_dx else None), wr.grad, db
