@@ -1,7 +1,7 @@
 """Step time of the RPV CNN ([16,32,64]/[128], 64x64x3, B=128) per optimizer on one GPU.
 
     python benchmarks/optimizer_step.py [--opts Adam,Adagrad,Adamax,AMSGrad] [--rounds 6] [--steps 256]
-                                        [--clipnorm C] [--l2 X] [--activation NAME[,NAME..]] [--batch-norm]
+                                        [--clipnorm C] [--l2 X] [--max-norm X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
                                         [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
                                         [--loss NAME[,NAME..]] [--separable] [--dilated]
@@ -20,6 +20,11 @@ of gradient clipping.
 ``--l2 X`` likewise adds ``<name>/unfused`` and ``<name>/l2`` (an l2 kernel regularizer ``X`` on
 every Conv2D / Dense: that structure plus the one ``weight_reg`` launch).  The difference between
 the two is the cost of the weight regularizers.
+
+``--max-norm X`` adds ``<name>/max-norm``: the default model, same step structure, with ``MaxNorm(X, axis=[0, 1, 2])``
+on every Conv2D kernel and ``MaxNorm(X, axis=0)`` on every Dense kernel -- the ``constraint_norms`` and
+``constraint_apply`` launches at the end of the step (``end_launches`` in the output).  The difference to
+``<name>`` is the cost of the weight constraints.
 
 ``--activation NAME[,NAME..]`` adds ``<name>/perlayer`` (the relu model built under
 ``INTML_TUNE=conv_stack=0,fuse_head=0``: the per-layer structure a model with hidden activations
@@ -74,8 +79,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from cori_intml_examples_amd import optim  # noqa: E402
+from cori_intml_examples_amd import constraints, optim  # noqa: E402
 from cori_intml_examples_amd.apps import zoo  # noqa: E402
+from cori_intml_examples_amd.models.layers import Conv2D, Dense  # noqa: E402
 from cori_intml_examples_amd.utils import set_random_seed  # noqa: E402
 
 REPLAY = 32
@@ -92,11 +98,12 @@ def make_opt(name, **kw):
 
 
 def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
-             metrics=None, weighted_metrics=None, losses=(), separable=False, dilated=False):
+             metrics=None, weighted_metrics=None, losses=(), separable=False, dilated=False, max_norm=None):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
     "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
-    metric keywords, "weighted_data": True for sample-weighted data)]"""
+    metric keywords, "weighted_data": True for sample-weighted data, "max_norm": X for MaxNorm kernel
+    constraints)]"""
     out = []
     for nm in names:
         out.append((nm, nm, {}, None, 0.0, "relu"))
@@ -112,6 +119,8 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/clipnorm", nm, {"clipnorm": clipnorm}, None, 0.0, "relu"))
         if l2:
             out.append((nm + "/l2", nm, {}, None, l2, "relu"))
+        if max_norm:
+            out.append((nm + "/max-norm", nm, {}, None, 0.0, "relu", {"max_norm": max_norm}))
         if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
         if pool != "max" or global_pool or separable or dilated:
@@ -166,6 +175,8 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--clipnorm", type=float, default=None)
     ap.add_argument("--l2", type=float, default=None)
+    ap.add_argument("--max-norm", type=float, default=None,
+                    help="time the model with MaxNorm(X) kernel constraints on every Conv2D / Dense")
     ap.add_argument("--activation", default="", help="comma-separated hidden activations to time")
     ap.add_argument("--batch-norm", action="store_true", help="time the model with BatchNormalization layers")
     ap.add_argument("--pool", choices=["max", "avg"], default="max", help="time the model with AveragePooling2D layers")
@@ -183,7 +194,7 @@ def main():
     split = lambda t: [n for n in t.split(",") if n]
     var = [v if len(v) == 7 else v + ({},) for v in
            variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
-                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable, a.dilated)]
+                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable, a.dilated, a.max_norm)]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -204,7 +215,14 @@ def main():
                             **({"pool": act.split("=")[1]} if act.startswith("relu+pool=") else {}),
                             **({"global_pool": act.split("=")[1]} if act.startswith("relu+gpool=") else {}),
                             **({"activation": act} if not act.startswith("relu") else {}),
-                            **{k: v for k, v in extra.items() if k != "weighted_data"}))
+                            **{k: v for k, v in extra.items() if k not in ("weighted_data", "max_norm")}))
+            if extra.get("max_norm"):
+                # the builders take no constraint keyword: set the layers' and compile again
+                for layer in m.layers:
+                    if isinstance(layer, (Conv2D, Dense)):
+                        layer.kernel_constraint = constraints.MaxNorm(
+                            extra["max_norm"], axis=[0, 1, 2] if isinstance(layer, Conv2D) else 0)
+                m.compile(optimizer=make_opt(oname, **kw), loss="binary_crossentropy", metrics=["accuracy"])
         ex = m._executor
         yv = y if extra.get("outputs", 1) == 1 else (rs.rand(bs * REPLAY, extra["outputs"]) > 0.5).astype(np.float32)
         d = ex.upload(x, yv, w) if extra.get("weighted_data") else ex.upload(x, yv)
@@ -258,6 +276,7 @@ def main():
            "us_per_step_runs": {nm: [round(t, 2) for t in v] for nm, v in us.items()},
            "optim_fused": {nm: bool(runs[nm][1]._plans[keys[nm]].optim_fused) for nm in names},
            "launches": {nm: [it[0] for it in runs[nm][1]._plans[keys[nm]].launches] for nm in names},
+           "end_launches": {nm: [it[0] for it in runs[nm][1]._plans[keys[nm]].end_launches] for nm in names},
            "finite": {nm: bool(np.isfinite(runs[nm][0].store.master[:runs[nm][0].store.numel].sum().item()))
                       for nm in names}}
     if ev:

@@ -32,7 +32,8 @@ HDF5_ROOT = os.environ.get("INTML_HDF5_ROOT", "/opt/conda")
 # known are pinned to their object code and stay as built, new files are compiled without those forms
 # (for wide_head.hip: 79 instead of 80 / 92 VGPRs, no other difference in the resource report).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FILE_FLAGS = {"wide_head.hip": _NO_PK_F32, "depthwise.hip": _NO_PK_F32, "dilated.hip": _NO_PK_F32}
+FILE_FLAGS = {"wide_head.hip": _NO_PK_F32, "depthwise.hip": _NO_PK_F32, "dilated.hip": _NO_PK_F32,
+              "constraint.hip": _NO_PK_F32}
 
 
 def _py_includes():

@@ -5,7 +5,7 @@ names (``mnist.py:15-21``, ``rpv.py:15-16,64``, ``train_rpv.py:10``, ``mlextras.
 ``hpo_widgets.py:9``, ``CrayHPO_rpv.ipynb:44-45``).  ``install()`` registers this
 framework's implementations under those names *when the real package is absent*:
 
-    keras, keras.{layers,models,optimizers,regularizers,activations,callbacks,losses,utils,backend,datasets.mnist,
+    keras, keras.{layers,models,optimizers,regularizers,constraints,activations,callbacks,losses,utils,backend,datasets.mnist,
                   wrappers.scikit_learn}
     horovod, horovod.keras, horovod.keras.callbacks      -> parallel.hvd (RCCL data parallelism)
     ipyparallel, ipyparallel.datapub, ipyparallel.error  -> farm (one-node task farm)
@@ -33,6 +33,7 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
     from .. import models as _models
     from .. import activations as _act
     from .. import regularizers as _reg
+    from .. import constraints as _con
     from ..hpo import sklearn as _skl
     from ..models import layers as _layers
     from ..optim import optimizers as _opt
@@ -72,9 +73,10 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
                   KerasRegressor=_skl.KerasRegressor)
     wrappers = _mod("keras.wrappers", scikit_learn=scikit)
     keras = _mod("keras", "MI355X-native Keras-2.2-shaped API", __version__="2.2.4", layers=layers,
-                 models=models, optimizers=_opt, regularizers=_reg, activations=_act, callbacks=_cb, losses=_losses, utils=utils, backend=backend,
+                 models=models, optimizers=_opt, regularizers=_reg, constraints=_con, activations=_act, callbacks=_cb, losses=_losses, utils=utils, backend=backend,
                  datasets=datasets, wrappers=wrappers, Sequential=_models.Sequential, Model=_models.Model)
     return {"keras": keras, "keras.layers": layers, "keras.models": models, "keras.optimizers": _opt, "keras.regularizers": _reg,
+            "keras.constraints": _con,
             "keras.activations": _act,
             "keras.callbacks": _cb, "keras.losses": _losses, "keras.utils": utils, "keras.backend": backend,
             "keras.datasets": datasets, "keras.datasets.mnist": mnist, "keras.wrappers": wrappers,

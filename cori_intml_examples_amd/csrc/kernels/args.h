@@ -135,6 +135,49 @@ struct RegArgs {
   float* state = nullptr;        // REG_STATE_WORDS words
 };
 
+// Keras weight constraints (constraint.hip): MaxNorm / NonNeg / UnitNorm / MinMaxNorm of the flat
+// master weights behind the step's update.  One descriptor per constrained tensor: the row-major
+// [R, M] fp32 matrix at element off, one group per column.  con_plan derives every descriptor's
+// work split from its shape: 1 << cg_log2 threads of a workgroup lie across the columns (4 columns
+// each where vec), the other CON_THREADS >> cg_log2 are row lanes; the rows are cut into nchunk
+// chunks of rchunk rows and the columns into ntile tiles, one workgroup per (chunk, tile).  A tensor
+// of more than one chunk (but NonNeg, which needs no sum) takes two launches: constraint_norms_kernel
+// writes partials[part0 + chunk * M + column], constraint_apply_kernel adds a column's chunks in
+// ascending order; a tensor of one chunk is summed inside the apply launch.
+#define MAX_CON 16
+#define CON_THREADS 256
+#define CON_MIN_CHUNK_ROWS 128   // rows per chunk: max(CON_MIN_CHUNK_ROWS, ceil(R / CON_MAX_CHUNKS))
+#define CON_MAX_CHUNKS 256
+#define CON_MAX_NORM 0
+#define CON_NON_NEG 1
+#define CON_UNIT_NORM 2
+#define CON_MIN_MAX_NORM 3
+struct ConDesc {
+  int off, R, M, kind;
+  float p0, p1, p2;              // min_value, max_value, rate (MaxNorm: 0, max_value, 1)
+  int vec;                       // 1: M % 4 == 0 and the tensor starts on a 16-byte line -> float4 columns
+  int cg_log2;                   // column groups (threads across the columns) per workgroup, log2
+  int rchunk, nchunk, ntile;
+  int b0;                        // its first workgroup in the apply launch
+  int nb0;                       // ... in the norms launch (-1: not in it)
+  int part0;                     // its first word of partials (-1: none)
+};
+struct ConArgs {
+  float* p = nullptr;            // master weights, elements [0, n)
+  int n = 0;
+  int ndesc = 0;                 // ascending, disjoint (set_tensors)
+  ConDesc d[MAX_CON];
+  int norm_blocks = 0, apply_blocks = 0;   // (con_plan)
+  float* partials = nullptr;     // sums of squares per (chunk, column) of the two-launch tensors
+  int npartials = 0;             // capacity of partials (host check)
+  // the bf16 packs of the rescaled weights, as the optimizer writes them (pack_write): nroutes > 0 ->
+  // through the routes; else the packs are marked stale for the next prologue (st may be null: no packs)
+  bf16* arena = nullptr;
+  const PackRoute* routes = nullptr;
+  int nroutes = 0;
+  StepState* st = nullptr;
+};
+
 // Implicit-GEMM convolution / 1x1 "dense as conv" (fwd, dgrad, dense-dX).
 struct ConvMMArgs {
   const bf16* x = nullptr;       // input activations [B, H, W, Cs_in]

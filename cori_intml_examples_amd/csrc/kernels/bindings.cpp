@@ -70,6 +70,11 @@ int clip_blocks(const ClipArgs& a);
 void launch_weight_reg(const RegArgs& a, hipStream_t s);
 int reg_blocks(const RegArgs& a);
 void reg_set_ranges(RegArgs& a, const int* lo, const int* hi, const float* l1, const float* l2, int count);
+void launch_constraint_norms(const ConArgs& a, hipStream_t s);
+void launch_constraint_apply(const ConArgs& a, hipStream_t s);
+int con_plan(ConArgs& a);
+void con_set_tensors(ConArgs& a, const int* off, const int* R, const int* M, const int* kind, const float* p0,
+                     const float* p1, const float* p2, int count);
 void launch_act_fwd(const ActArgs& a, hipStream_t s);
 void launch_act_bwd(const ActArgs& a, hipStream_t s);
 void launch_pool_fwd(const PoolArgs& a, hipStream_t s);
@@ -568,6 +573,38 @@ PYBIND11_MODULE(_kernels, m) {
   m.attr("REG_TICKET") = REG_TICKET;
   m.def("reg_blocks", &reg_blocks);
   m.def("weight_reg", [](const RegArgs& a, uintptr_t s) { launch_weight_reg(a, S(s)); check_last("weight_reg"); });
+  // Keras weight constraints (constraint.hip): the column-norm launches behind the step's update
+  py::class_<ConArgs>(m, "ConArgs")
+      .def(py::init<>())
+      PTR(ConArgs, p) RW(ConArgs, n) PTR(ConArgs, partials) RW(ConArgs, npartials) PTR(ConArgs, arena)
+      PTR(ConArgs, routes) RW(ConArgs, nroutes) PTR(ConArgs, st)
+      .def_readonly("ndesc", &ConArgs::ndesc)
+      // [(offset, R, M, kind, p0, p1, p2)] ascending and disjoint
+      .def("set_tensors", [](ConArgs& a, const std::vector<std::tuple<int, int, int, int, float, float, float>>& ts) {
+        std::vector<int> off, R, M, kind;
+        std::vector<float> p0, p1, p2;
+        for (const auto& t : ts) {
+          off.push_back(std::get<0>(t)); R.push_back(std::get<1>(t)); M.push_back(std::get<2>(t));
+          kind.push_back(std::get<3>(t)); p0.push_back(std::get<4>(t)); p1.push_back(std::get<5>(t));
+          p2.push_back(std::get<6>(t));
+        }
+        con_set_tensors(a, off.data(), R.data(), M.data(), kind.data(), p0.data(), p1.data(), p2.data(), (int)ts.size());
+      })
+      // the work split for the args' weight pointer: (partials words, norms workgroups, apply workgroups,
+      // [(vec, column groups, rows per chunk, chunks, column tiles) per tensor])
+      .def("plan", [](const ConArgs& in) {
+        ConArgs a = in;
+        const int words = con_plan(a);
+        std::vector<std::tuple<int, int, int, int, int>> geo;
+        for (int i = 0; i < a.ndesc; ++i)
+          geo.emplace_back(a.d[i].vec, 1 << a.d[i].cg_log2, a.d[i].rchunk, a.d[i].nchunk, a.d[i].ntile);
+        return std::make_tuple(words, a.norm_blocks, a.apply_blocks, geo);
+      });
+  m.attr("MAX_CON") = MAX_CON;
+  m.attr("CON_MIN_CHUNK_ROWS") = CON_MIN_CHUNK_ROWS;
+  m.attr("CON_MAX_CHUNKS") = CON_MAX_CHUNKS;
+  m.def("constraint_norms", [](const ConArgs& a, uintptr_t s) { launch_constraint_norms(a, S(s)); check_last("constraint_norms"); });
+  m.def("constraint_apply", [](const ConArgs& a, uintptr_t s) { launch_constraint_apply(a, S(s)); check_last("constraint_apply"); });
   // element-wise hidden activations (act.hip): one launch per direction behind a stage's linear kernels
   py::class_<ActArgs>(m, "ActArgs")
       .def(py::init<>())

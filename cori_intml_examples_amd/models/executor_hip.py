@@ -140,6 +140,15 @@ class HipExecutor(Executor):
                                             device=self.device)
         self._build_geometry()
         self._build_packs()
+        # Keras weight constraints [(offset, R, M, kind, params)] over the flat store, read HERE like the
+        # clip values (they go into kernel arguments of the captured step): ONE descriptor table for all
+        # tensors, its launches behind the step's update (BatchPlan.end_launches).  A model without
+        # constraints has no table, no buffer and no launch.
+        self.cons = store.constrained_tensors()
+        self.con_partials = None
+        if len(self.cons) > self.K.MAX_CON:
+            raise ValueError("%d constrained weight tensors (layers %s): the constraint kernel takes at most "
+                             "MAX_CON = %d" % (len(self.cons), ", ".join(store.constrained_layers()), self.K.MAX_CON))
         self._plans: Dict[Tuple[int, str], "BatchPlan"] = {}
         self._lr_host = None
         self._expected_pos = None
@@ -324,6 +333,26 @@ class HipExecutor(Executor):
         r.st = self.state.data_ptr()
         r.state = self.reg_state.data_ptr()
         return r
+
+    def _con_args(self):
+        """ConArgs of the model's constrained tensors: the table, the partials of the tensors whose rows
+        are split over workgroups, and the pack routes the apply launch re-writes the bf16 packs through
+        (without routes it marks the packs stale, as the optimizer launches do)."""
+        K = self.K
+        c = K.ConArgs()
+        c.p, c.n = self.store.master.data_ptr(), self.store.numel
+        c.set_tensors([(off, rows, cols, kind) + tuple(ps) for off, rows, cols, kind, ps in self.cons])
+        words = c.plan()[0]
+        if words and self.con_partials is None:
+            self.con_partials = torch.zeros(words, dtype=torch.float32, device=self.device)
+        if words:
+            c.partials, c.npartials = self.con_partials.data_ptr(), self.con_partials.numel()
+        c.st = self.state.data_ptr()
+        if self.routes is not None:
+            c.arena = self.arena.data_ptr()
+            c.routes = self.routes.data_ptr()
+            c.nroutes = self.routes.numel() * 4 // K.PACK_ROUTE_BYTES
+        return c
 
     def _optim_args(self, pack_only: bool, defer_pack: bool = False, clip: bool = False):
         """clip: the clipped optimizer launch (single-GPU step of a clipping optimizer); every
@@ -579,6 +608,10 @@ class BatchPlan(GeometryMixin):
         self.early_red = {}                # dual launch name -> (RedTable, span, grad_only): _early_groups
         self.xchg = Exchange()             # the xGMI exchange plan of a data-parallel step
         self.launches: List[Launch] = []
+        # the launches behind the step's update (_build_constraints).  A list of its own: the end-of-step
+        # optimizer launch is not in ``launches`` -- _body and the segmented data-parallel step issue it
+        # themselves, the latter behind the host's wait for the all-reduces -- and these follow it
+        self.end_launches: List[Launch] = []
         self.srcidx = None                 # prologue-free step: the dataset row of each image
         self.stack_args = None
         self.red_groups: List[RedGroup] = []   # per layer, in backward order
@@ -921,6 +954,24 @@ class BatchPlan(GeometryMixin):
         for g, cs in reversed(list(zip(ex.convs, ex.plan.convs))):
             self._build_conv_bwd(g, cs)
         self._build_reduce()
+        self._build_constraints()
+
+    def _build_constraints(self):
+        """Keras weight constraints: w <- C(update(w)) at the END of the step body, on the main stream
+        behind the join of every stream of the step -- so behind every launch that updates a constrained
+        range, whether that is the optimizer launch, a fused reduction, the dense wgrad's fused update or
+        a comm-stream optimizer -- and ahead of the next step's first reader.  At most two launches for
+        all tensors: the partial column sums of the tensors whose rows are split over workgroups, then
+        the apply launch, which also re-writes the bf16 packs of what it rescaled."""
+        ex = self.ex
+        if not ex.cons:
+            return
+        ca = ex._con_args()
+        if ca.plan()[1]:
+            self.end_launches.append(Launch("constraint_norms", lambda s, a=ca: ex.K.constraint_norms(a, s), "main",
+                                            {"con": ca}))
+        self.end_launches.append(Launch("constraint_apply", lambda s, a=ca: ex.K.constraint_apply(a, s), "main",
+                                        {"con": ca}))
 
     def _build_prologue(self):
         """The prologue launch (gather + re-pack + bookkeeping), unless the step is prologue-free.
@@ -1856,6 +1907,20 @@ class BatchPlan(GeometryMixin):
         self._run_seq()
         if self.training and with_optim and not self.optim_fused and not self.optim_on_comm:
             self._launch_optim()
+        if self.training and with_optim:
+            self._launch_end()
+
+    def _launch_end(self):
+        """The launches behind the step's update (weight constraints), on the main stream."""
+        s = torch.cuda.current_stream().cuda_stream
+        drop = set((tune("skip") or "").split("/"))     # (the timing ablation of _run_seq)
+        for it in self.end_launches:
+            if it.name not in drop:
+                it.fn(s)
+
+    def _launch_optim_end(self):
+        self._launch_optim()
+        self._launch_end()
 
     def _dp_segments(self):
         """[(launch_lo, launch_hi, bucket)]: segment k ends with the slab reduction that
@@ -1913,7 +1978,7 @@ class BatchPlan(GeometryMixin):
         if ex.use_graphs and self.dp_graphs is None:
             self.dp_graphs = [self._capture(lambda a=lo, b=hi, k=k: self._run_segment(a, b, k))
                               for lo, hi, k in segs]
-            self.dp_graphs.append(self._capture(self._launch_optim))
+            self.dp_graphs.append(self._capture(self._launch_optim_end))
         for j, (lo, hi, k) in enumerate(segs):
             if ex.use_graphs:
                 self.dp_graphs[j].replay()
@@ -1925,7 +1990,7 @@ class BatchPlan(GeometryMixin):
         if ex.use_graphs:
             self.dp_graphs[-1].replay()
         else:
-            self._launch_optim()
+            self._launch_optim_end()
 
     def _capture(self, fn):
         g = torch.cuda.CUDAGraph()

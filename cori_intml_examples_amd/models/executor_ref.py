@@ -47,6 +47,8 @@ class RefExecutor(Executor):
         self.emulate_bf16 = bool(tune("ref_bf16"))
         # Keras weight regularizers [(lo, hi, l1, l2)], read here (at compile) like the clip values
         self.regs = store.regularized_ranges()
+        # Keras weight constraints [(offset, R, M, kind, params)]: applied behind every update
+        self.cons = store.constrained_tensors()
         self._roc = None             # metrics.RocState, the numpy twin of the HIP executor's ROC state
         self._roc_w_seen = False
 
@@ -332,6 +334,9 @@ class RefExecutor(Executor):
             R.rmsprop_update(p, g, self.slots[0][:n], lr, base.rho, base.epsilon)
         else:
             raise NotImplementedError(k)
+        # Keras weight constraints: w <- C(update(w)); the optimizer slots are untouched
+        if self.cons:
+            R.apply_constraints(self.cons, self.store.master)
 
     # ------------------------------------------------------------------------------ steps
     def train_step(self, data: DeviceData, perm: torch.Tensor, pos: int, bs: int) -> None:

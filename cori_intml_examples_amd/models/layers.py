@@ -15,7 +15,7 @@ import re
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence, Tuple
 
-from .. import regularizers
+from .. import constraints, regularizers
 from ..ops.reference import conv_out_size
 
 _name_counters: Dict[str, int] = defaultdict(int)
@@ -201,6 +201,34 @@ class _Regularized:
                 "bias_regularizer": regularizers.serialize(self.bias_regularizer)}
 
 
+class _Constrained:
+    """The constraint keywords of Conv2D / Dense (Keras 2.2.4): ``kernel_constraint`` and
+    ``bias_constraint`` take what ``constraints.get`` takes.  The axis set must be a prefix of the
+    weight's axes (``constraints.Constraint.rows``); anything else is refused here, by layer name."""
+
+    def _set_constraints(self, kernel_constraint, bias_constraint, kernel_rank):
+        self.kernel_constraint = constraints.get(kernel_constraint)
+        self.bias_constraint = constraints.get(bias_constraint)
+        if self.kernel_constraint is not None:
+            self.kernel_constraint.rows((1,) * kernel_rank, self.name)
+        if self.bias_constraint is not None:
+            self.bias_constraint.rows((1,), self.name)
+
+    def weight_constraints(self):
+        """{weight short name: Constraint} of this layer's constrained tensors (a ``bias_constraint``
+        without a bias is ignored, as in Keras)."""
+        out = {}
+        if self.kernel_constraint is not None:
+            out["kernel"] = self.kernel_constraint
+        if self.bias_constraint is not None and self.use_bias:
+            out["bias"] = self.bias_constraint
+        return out
+
+    def _constraint_config(self):
+        return {"kernel_constraint": constraints.serialize(self.kernel_constraint),
+                "bias_constraint": constraints.serialize(self.bias_constraint)}
+
+
 def _check_act(act):
     if callable(act):
         act = getattr(act, "__name__", None)
@@ -209,13 +237,15 @@ def _check_act(act):
     return None if act == "linear" else act
 
 
-class Conv2D(_Regularized, Layer):
+class Conv2D(_Regularized, _Constrained, Layer):
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None,
                  dilation_rate=(1, 1), activation=None, use_bias=True,
                  kernel_initializer="glorot_uniform", bias_initializer="zeros", kernel_regularizer=None,
-                 bias_regularizer=None, activity_regularizer=None, **kw):
+                 bias_regularizer=None, activity_regularizer=None, kernel_constraint=None, bias_constraint=None,
+                 **kw):
         super().__init__(**kw)
         self._set_regularizers(kernel_regularizer, bias_regularizer, activity_regularizer)
+        self._set_constraints(kernel_constraint, bias_constraint, 4)
         self.filters = int(filters)
         self.kernel_size = _pair(kernel_size)
         self.strides = _pair(strides)
@@ -276,6 +306,7 @@ class Conv2D(_Regularized, Layer):
                     "kernel_regularizer": None, "bias_regularizer": None,
                     "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None})
         cfg.update(self._regularizer_config())
+        cfg.update(self._constraint_config())
         return cfg
 
     @classmethod
@@ -283,7 +314,7 @@ class Conv2D(_Regularized, Layer):
         cfg = {k: v for k, v in cfg.items() if k in (
             "name", "trainable", "filters", "kernel_size", "strides", "padding", "activation",
             "use_bias", "batch_input_shape", "kernel_regularizer", "bias_regularizer", "activity_regularizer",
-            "dilation_rate")}
+            "dilation_rate", "kernel_constraint", "bias_constraint")}
         if "dilation_rate" in cfg:
             cfg["dilation_rate"] = tuple(_pair(cfg["dilation_rate"]))
         return super().from_config(cfg)
@@ -547,12 +578,13 @@ class Flatten(Layer):
         return cls(name=cfg.get("name"))
 
 
-class Dense(_Regularized, Layer):
+class Dense(_Regularized, _Constrained, Layer):
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer="glorot_uniform",
                  bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None,
-                 activity_regularizer=None, **kw):
+                 activity_regularizer=None, kernel_constraint=None, bias_constraint=None, **kw):
         super().__init__(**kw)
         self._set_regularizers(kernel_regularizer, bias_regularizer, activity_regularizer)
+        self._set_constraints(kernel_constraint, bias_constraint, 2)
         self.units = int(units)
         self.activation = _check_act(activation)
         self.use_bias = bool(use_bias)
@@ -580,13 +612,14 @@ class Dense(_Regularized, Layer):
                     "kernel_regularizer": None, "bias_regularizer": None,
                     "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None})
         cfg.update(self._regularizer_config())
+        cfg.update(self._constraint_config())
         return cfg
 
     @classmethod
     def from_config(cls, cfg):
         cfg = {k: v for k, v in cfg.items() if k in (
             "name", "trainable", "units", "activation", "use_bias", "batch_input_shape",
-            "kernel_regularizer", "bias_regularizer", "activity_regularizer")}
+            "kernel_regularizer", "bias_regularizer", "activity_regularizer", "kernel_constraint", "bias_constraint")}
         return super().from_config(cfg)
 
 

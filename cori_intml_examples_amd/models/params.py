@@ -174,6 +174,26 @@ class ParamStore:
                 names.append(s.layer.name)
         return names
 
+    def constrained_tensors(self) -> List[Tuple[int, int, int, int, Tuple[float, float, float]]]:
+        """[(offset, R, M, kind, (p0, p1, p2))]: the tensors that carry a Keras weight constraint (the
+        layers' kernel_constraint / bias_constraint), in store order, each as the row-major [R, M]
+        matrix its axis set makes of it (a group is one column; ``constraints.py``)."""
+        out = []
+        for s in self.specs:
+            con = getattr(s.layer, "weight_constraints", dict)().get(s.short)
+            if con is not None and s.numel and s.trainable:
+                rows = con.rows(s.shape, s.layer.name)
+                out.append((s.offset, rows, s.numel // rows, con.kind, con.params()))
+        return out
+
+    def constrained_layers(self) -> List[str]:
+        """Names of the layers with a constrained tensor, in store order."""
+        names = []
+        for s in self.specs:
+            if getattr(s.layer, "weight_constraints", dict)().get(s.short) is not None and s.layer.name not in names:
+                names.append(s.layer.name)
+        return names
+
     def layer_ranges(self) -> Dict[str, Tuple[int, int]]:
         """Per layer, the flat range of its trainable tensors."""
         out: Dict[str, Tuple[int, int]] = {}

@@ -409,6 +409,29 @@ def add_regularization_grad(ranges, master: torch.Tensor, g_flat: torch.Tensor) 
         g_flat[lo:hi] = g_flat[lo:hi] + (c1 * torch.sign(w) + c2 * w)
 
 
+# --------------------------------------------------------------------------- constraints (Keras 2.2)
+def apply_constraints(tensors, master: torch.Tensor) -> None:
+    """Keras 2.2.4 weight constraints (``constraints.py``) on the flat fp32 weights, in place, behind the
+    optimizer update: for each of ``tensors`` [(offset, R, M, kind, (p0, p1, p2))] the row-major [R, M]
+    matrix at ``offset`` is rescaled column by column from the columns' L2 norms, in fp32 and in the HIP
+    kernel's operation order.  kind 0 MaxNorm (p1 = max_value), 1 NonNeg, 2 UnitNorm, 3 MinMaxNorm
+    (min_value, max_value, rate).  Elements outside the tensors are untouched."""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)        # noqa: E731
+    eps = f32(1e-7)
+    for off, rows, cols, kind, (p0, p1, p2) in tensors:
+        w = master[off:off + rows * cols].view(rows, cols)
+        if kind == 1:
+            w.mul_((w >= 0).to(torch.float32))
+            continue
+        norms = torch.sqrt((w * w).sum(dim=0, keepdim=True))
+        if kind == 2:
+            w.div_(eps + norms)
+        elif kind == 0:
+            w.mul_(torch.clamp(norms, 0.0, p1) / (eps + norms))
+        else:
+            w.mul_((f32(p2) * torch.clamp(norms, p0, p1) + (f32(1.0) - f32(p2)) * norms) / (eps + norms))
+
+
 # --------------------------------------------------------------------------- optimizers (Keras 2.2)
 def clip_gradients(g_flat: torch.Tensor, clipnorm=None, clipvalue=None):
     """Keras 2.2.4 ``Optimizer.get_gradients`` clipping of the flat fp32 gradient, in place.
