@@ -8,7 +8,7 @@
 """
 from __future__ import annotations
 
-from ..models import (Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
+from ..models import (Activation, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, Dense, Dropout, Flatten,
                       GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, SeparableConv2D, Sequential)
 from .. import optim as optimizers
 from .. import regularizers
@@ -188,6 +188,31 @@ def rpv_context_cnn(input_shape, dilations=(1, 2, 4), filters=(16, 32, 64), dens
         h = Dropout(dropout)(h)
     outputs = Dense(1, activation="sigmoid", **reg)(h)
     model = Model(inputs=inputs, outputs=outputs, name="RPVContextClassifier", device=device)
+    model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
+    return model
+
+
+def rpv_hourglass_cnn(input_shape=(64, 64, 3), filters=(16, 32, 64), up=(32,), dense=(128,), dropout=0.5,
+                      optimizer="Adam", lr=0.001, use_horovod=False, device=None, activation="relu", l2=0.0):
+    """An hourglass classifier for the RPV images: a same-padded 3x3 Conv2D + MaxPooling2D per entry of
+    ``filters``; per entry u of ``up`` a Conv2DTranspose(u, 3x3, strides 2, same) -- the learned up-sampling
+    that regains resolution -- followed by a same-padded 3x3 Conv2D(u); then GlobalAveragePooling2D,
+    ``[Dense, Dropout]`` per entry of ``dense`` and the sigmoid output; BCE + accuracy.  ``activation`` /
+    ``l2`` / ``lr`` / ``optimizer``: as in the other builders."""
+    reg = _kernel_l2(l2)
+    h = inputs = Input(shape=input_shape)
+    for c in filters:
+        h = Conv2D(c, kernel_size=(3, 3), padding="same", activation=activation, **reg)(h)
+        h = MaxPooling2D(pool_size=(2, 2))(h)
+    for u in up:
+        h = Conv2DTranspose(u, kernel_size=(3, 3), strides=2, padding="same", activation=activation, **reg)(h)
+        h = Conv2D(u, kernel_size=(3, 3), padding="same", activation=activation, **reg)(h)
+    h = GlobalAveragePooling2D()(h)
+    for f in dense:
+        h = Dense(f, activation=activation, **reg)(h)
+        h = Dropout(dropout)(h)
+    outputs = Dense(1, activation="sigmoid", **reg)(h)
+    model = Model(inputs=inputs, outputs=outputs, name="RPVHourglassClassifier", device=device)
     model.compile(optimizer=_opt(optimizer, lr, use_horovod), loss="binary_crossentropy", metrics=["accuracy"])
     return model
 

@@ -834,3 +834,41 @@ struct DilArgs {
   float* slab = nullptr;           // wgrad
   int slab_ld = 0, S = 0, pairs_per_slab = 0, has_bias = 0;
 };
+
+// Transposed convolution (transposed.hip): Keras Conv2DTranspose, isotropic strides s in 1..4.  bf16
+// channels-last activations (Cs == 4 with C <= 4, else a multiple of 8); the weights are the fp32 master
+// ``kernel`` [KH][KW][Cout][Cin] (output channels BEFORE input channels), rounded to bf16 as they are
+// staged (no weight pack).  Output pixel (Y, X) receives input pixel (i, j) through tap (ky, kx) where
+// Y = i * s + ky - pad_t, X = j * s + kx - pad_l.  One struct for the stage's three launches, all implicit
+// GEMMs on v_mfma_f32_16x16x32_bf16 over blocks of R INPUT rows:
+//   tconv_fwd    x -> out = bf16(A(z + bias)), A relu or linear; per block every output parity class
+//                (Y + pad_t) mod s, (X + pad_l) mod s as a dense stride-1 sub-convolution
+//   tconv_dgrad  dt (the gradient wrt z) -> dx through ``bt``, the feeding stage's BwdThrough: a gather at
+//                stride s over the staged dt rows
+//   tconv_wgrad  x, dt -> S slab rows [KH][KW][Cout][Cin] (+ [Cout], the bias gradient) of ``slab_ld``
+//                floats; slab g sums the (image, block of R input rows) pairs
+//                [g * pairs_per_slab, (g + 1) * pairs_per_slab)
+#define TC_FWD 0
+#define TC_DGRAD 1
+#define TC_WGRAD 2
+#define TC_THREADS 256
+#define TC_MTW 4                    // 16-row m-tiles a wave keeps in registers (x ntw n-tiles)
+#define TC_LDS_BUDGET (160 * 1024)  // (DIL_LDS_BUDGET: a CU's whole LDS)
+struct TconvArgs {
+  const bf16* x = nullptr;         // [B, H, W, Cs_in] the stage input (fwd, wgrad)
+  const float* w = nullptr;        // fp32 [KH][KW][Cout][Cin]
+  const float* bias = nullptr;     // fp32 [Cout] (fwd; null: none)
+  bf16* out = nullptr;             // [B, Ho, Wo, Cs_out] (fwd)
+  const bf16* dt = nullptr;        // [B, Ho, Wo, Cs_out] (dgrad, wgrad)
+  int B = 0, H = 0, W = 0, Cin = 0, Cs_in = 0, Ho = 0, Wo = 0, Cout = 0, Cs_out = 0;
+  int KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0;
+  int relu = 0;
+  int R = 0;                       // input rows per block (tconv_cfg)
+  int ntw = 1;                     // n-tiles per workgroup: 1, 2 or 4 (tconv_ntw)
+  int kc = 0;                      // fwd / dgrad: 32-wide k-steps of the weight chunk held in LDS (tconv_cfg)
+  int xpix = 0;                    // pixel stride (elements) of the staged image (models/lds_layout.py)
+  BwdThrough bt;                   // dgrad
+  const StepState* st = nullptr;   // dgrad: the dropout counter's step (null: 0)
+  float* slab = nullptr;           // wgrad
+  int slab_ld = 0, S = 0, pairs_per_slab = 0, has_bias = 0;
+};

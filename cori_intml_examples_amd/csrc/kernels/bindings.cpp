@@ -90,6 +90,12 @@ void launch_dil_wgrad(const DilArgs& a, hipStream_t s);
 std::tuple<int, int> dil_cfg(const DilArgs& a, int kind, int want);
 size_t dil_lds_bytes(const DilArgs& a, int kind, int R, int kc);
 int dil_ntw(int n, int kind);
+void launch_tconv_fwd(const TconvArgs& a, hipStream_t s);
+void launch_tconv_dgrad(const TconvArgs& a, hipStream_t s);
+void launch_tconv_wgrad(const TconvArgs& a, hipStream_t s);
+std::tuple<int, int> tconv_cfg(const TconvArgs& a, int kind, int want);
+size_t tconv_lds_bytes(const TconvArgs& a, int kind, int R, int kc);
+int tconv_ntw(int n, int kind);
 void launch_roc_accum(const RocArgs& a, hipStream_t s);
 void launch_roc_finish(const RocArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
@@ -670,6 +676,26 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("dil_fwd", [](const DilArgs& a, uintptr_t s) { launch_dil_fwd(a, S(s)); check_last("dil_fwd"); });
   m.def("dil_dgrad", [](const DilArgs& a, uintptr_t s) { launch_dil_dgrad(a, S(s)); check_last("dil_dgrad"); });
   m.def("dil_wgrad", [](const DilArgs& a, uintptr_t s) { launch_dil_wgrad(a, S(s)); check_last("dil_wgrad"); });
+  // transposed convolution (transposed.hip): forward, input gradient, weight gradient slabs
+  py::class_<TconvArgs>(m, "TconvArgs")
+      .def(py::init<>())
+      PTR(TconvArgs, x) PTR(TconvArgs, w) PTR(TconvArgs, bias) PTR(TconvArgs, out) PTR(TconvArgs, dt) RW(TconvArgs, B)
+      RW(TconvArgs, H) RW(TconvArgs, W) RW(TconvArgs, Cin) RW(TconvArgs, Cs_in) RW(TconvArgs, Ho) RW(TconvArgs, Wo)
+      RW(TconvArgs, Cout) RW(TconvArgs, Cs_out) RW(TconvArgs, KH) RW(TconvArgs, KW) RW(TconvArgs, stride) RW(TconvArgs, pad_t)
+      RW(TconvArgs, pad_l) RW(TconvArgs, relu) RW(TconvArgs, R) RW(TconvArgs, ntw) RW(TconvArgs, kc) RW(TconvArgs, xpix)
+      RW(TconvArgs, bt) PTR(TconvArgs, st) PTR(TconvArgs, slab) RW(TconvArgs, slab_ld) RW(TconvArgs, S)
+      RW(TconvArgs, pairs_per_slab) RW(TconvArgs, has_bias);
+  m.attr("TC_FWD") = TC_FWD;
+  m.attr("TC_DGRAD") = TC_DGRAD;
+  m.attr("TC_WGRAD") = TC_WGRAD;
+  m.attr("TC_MTW") = TC_MTW;
+  m.attr("TC_LDS_BUDGET") = TC_LDS_BUDGET;
+  m.def("tconv_cfg", &tconv_cfg);
+  m.def("tconv_lds_bytes", &tconv_lds_bytes);
+  m.def("tconv_ntw", &tconv_ntw);
+  m.def("tconv_fwd", [](const TconvArgs& a, uintptr_t s) { launch_tconv_fwd(a, S(s)); check_last("tconv_fwd"); });
+  m.def("tconv_dgrad", [](const TconvArgs& a, uintptr_t s) { launch_tconv_dgrad(a, S(s)); check_last("tconv_dgrad"); });
+  m.def("tconv_wgrad", [](const TconvArgs& a, uintptr_t s) { launch_tconv_wgrad(a, S(s)); check_last("tconv_wgrad"); });
   // ROC / AUC, purity, efficiency and weighted metrics (roc.hip): roc_accum behind the head in a step,
   // roc_finish once when the metrics are read
   py::class_<RocArgs>(m, "RocArgs")

@@ -41,7 +41,7 @@ from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin
-from .lds_layout import conv_layout
+from .lds_layout import conv_layout, tconv_wgrad_layout
 from .plan import Plan, binary_accuracy_head, classic_head
 from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
                            cdiv, check_bucket_cover, defer_after_readers, dropout_pair, gpool_geometry,
@@ -1049,6 +1049,15 @@ class BatchPlan(GeometryMixin):
                 self._add_stage_tail_fwd(g)
                 x_buf = self.stage_bufs(g).out
                 continue
+            if g.transposed:
+                da = self._tconv_args(g, cs, ex.K.TC_FWD, "tconv_fwd")
+                da.x = x_buf.data_ptr()
+                da.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
+                da.out, da.relu = self.stage_bufs(g).lin_out.data_ptr(), int(g.relu)
+                self._add("tconv_fwd%d" % g.i, lambda s, a=da: K.tconv_fwd(a, s), tconv=da)
+                self._add_stage_tail_fwd(g)
+                x_buf = self.stage_bufs(g).out
+                continue
             if g.depthwise:
                 da = self._dw_args(g, cs, x_buf)
                 self._add("dw_fwd%d" % g.i, lambda s, a=da: K.dw_fwd(a, s), dw=da)
@@ -1361,6 +1370,8 @@ class BatchPlan(GeometryMixin):
             return self._build_dw_bwd(g, cs, xin)
         if g.dilated:
             return self._build_dil_bwd(g, cs, xin)
+        if g.transposed:
+            return self._build_tconv_bwd(g, cs, xin)
         # (a BatchNormalization stage: conv_dy holds the dense un-pooled dz of bn_bwd_apply)
         g_stage, g = g, g.linear
         wide = self._wide(g.Cs_in, g.KS, g.NT)
@@ -1530,6 +1541,75 @@ class BatchPlan(GeometryMixin):
             da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
             da.st = ex.state.data_ptr()
             self._add("dil_dgrad%d" % g.i, lambda s, a=da: K.dil_dgrad(a, s), dil=da)
+            self._add_stage_tail_bwd(ex.convs[g.i - 1])
+
+    def _tconv_args(self, g, cs, kind, name):
+        """The TconvArgs of one of transposed stage g's launches (transposed.hip): its geometry, the fp32
+        master kernel, and the launch's configuration -- n-tiles per workgroup, the staged image's pixel
+        stride (lds_layout: conv_layout for the 16-byte fragment reads of tconv_fwd -- over its base grid and
+        the taps of its largest parity class -- and tconv_dgrad, tconv_wgrad_layout for the transposed reads),
+        input rows per block and the weight chunk (tconv_cfg, under the LDS budget and the minimum-workgroup
+        tune)."""
+        ex, K = self.ex, self.ex.K
+        a = K.TconvArgs()
+        a.w = ex.store.view(cs.conv, cs.wname).data_ptr()
+        a.B, a.H, a.W, a.Cin, a.Cs_in = self.bs, g.H, g.W, g.Cin, g.Cs_in
+        a.Ho, a.Wo, a.Cout, a.Cs_out = g.Ho, g.Wo, g.Cout, g.Cs_out
+        a.KH, a.KW, a.stride, a.pad_t, a.pad_l = g.KH, g.KW, g.stride, g.pad_t, g.pad_l
+        s = g.stride
+        a.ntw = K.tconv_ntw(g.Cout if kind == K.TC_FWD else g.Cin, kind)
+        if kind == K.TC_FWD:
+            ty, tw, qw = cdiv(g.KH, s), cdiv(g.KW, s), cdiv(g.Wo + g.pad_l, s)
+            ck, a.xpix = g.Cs_in, conv_layout(g.Cs_in, qw + tw - 1, qw, False, ty, tw)
+        elif kind == K.TC_DGRAD:
+            ck, a.xpix = g.Cs_out, conv_layout(g.Cs_out, (g.W - 1) * s + g.KW, g.W, False, g.KH, g.KW)
+        else:
+            ck, a.xpix = g.Cs_out, tconv_wgrad_layout(g.Cs_out, (g.W - 1) * s + max(g.KW, s), g.W, g.KH, g.KW, s)
+        a.R, a.kc = K.tconv_cfg(a, kind, int(tune("halo_min_wgs")))
+        if a.R <= 0:
+            a.xpix = ck         # (the dense stride)
+            a.R, a.kc = K.tconv_cfg(a, kind, int(tune("halo_min_wgs")))
+        if a.R <= 0:
+            ks = 0 if kind == K.TC_WGRAD else min(2, cdiv(cdiv(g.KH, s) * cdiv(g.KW, s) * ck if kind == K.TC_FWD
+                                                          else g.KH * g.KW * ck, 32))
+            raise NotImplementedError("layer %s (%s%d): one row block of its staged image over all %d channels, %d "
+                                      "bytes, exceeds the transposed kernels' %d bytes of LDS (no channel chunking)"
+                                      % (cs.conv.name, name, g.i, ck, K.tconv_lds_bytes(a, kind, 1, ks), K.TC_LDS_BUDGET))
+        return a
+
+    def _build_tconv_bwd(self, g, cs, xin):
+        """A transposed stage's backward: tconv_wgrad into one slab row per workgroup group (its reduction
+        group: the kernel in Keras order [KH][KW][Cout][Cin] and the bias, as identity descriptors) and,
+        unless it is the first stage, tconv_dgrad through the feeding stage's BwdThrough."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        bufs = self.stage_bufs(g)
+        wa = self._tconv_args(g, cs, K.TC_WGRAD, "tconv_wgrad")
+        wa.x, wa.dt, wa.has_bias = xin.data_ptr(), bufs.dz.data_ptr(), int(cs.use_bias)
+        sp = store.spec(cs.conv, cs.wname)
+        bsp = store.spec(cs.conv, "bias") if cs.use_bias else None
+        bias_off = cdiv(sp.numel, 4) * 4
+        wa.slab_ld = bias_off + (cdiv(g.Cout, 4) * 4 if cs.use_bias else 0)
+        # about one resident round of workgroups, over the launch's (m group, n group) grid
+        npairs = self.bs * cdiv(g.H, wa.R)
+        per = cdiv(cdiv(g.KH * g.KW * g.Cs_out, 16), 4 * K.TC_MTW) * cdiv(cdiv(g.Cin, 16), wa.ntw)
+        S = max(1, min(npairs, cdiv(2 * self._cu_count(), per)))
+        wa.pairs_per_slab = cdiv(npairs, S)
+        wa.S = S = cdiv(npairs, wa.pairs_per_slab)
+        slab = torch.zeros(S, wa.slab_ld, dtype=torch.float32, device=ex.device)
+        wa.slab = slab.data_ptr()
+        self.wgrad_slabs.append((slab, None))
+        self._add("tconv_wgrad%d" % g.i, lambda s, a=wa: K.tconv_wgrad(a, s), "side", tconv=wa)
+        descs = [RedDesc(slab.data_ptr(), wa.slab_ld, S, g.Cout, sp.offset, sp.numel, RED_BIAS)]
+        if bsp is not None:
+            descs.append(RedDesc(slab.data_ptr() + 4 * bias_off, wa.slab_ld, S, g.Cout, bsp.offset, bsp.numel,
+                                 RED_BIAS))
+        self._add_group(sp, descs, bsp)
+        if g.i > 0:
+            da = self._tconv_args(g, cs, K.TC_DGRAD, "tconv_dgrad")
+            da.dt = bufs.dz.data_ptr()
+            da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
+            da.st = ex.state.data_ptr()
+            self._add("tconv_dgrad%d" % g.i, lambda s, a=da: K.tconv_dgrad(a, s), tconv=da)
             self._add_stage_tail_bwd(ex.convs[g.i - 1])
 
     # ---------------------------------------------------------------- step program: reductions

@@ -138,6 +138,7 @@ class RefExecutor(Executor):
             w = self._q(st.view(cs.conv, cs.wname))
             b = st.view(cs.conv, "bias") if cs.use_bias else None
             z = (R.depthwise_conv2d(a, w, b, cs.stride, cs.padding) if cs.depthwise
+                 else R.conv2d_transpose(a, w, b, cs.stride, cs.padding) if cs.transposed
                  else R.conv2d(a, w, b, cs.stride, cs.padding, cs.dilation))
             z_code = z
             if cs.bn is not None:
@@ -290,9 +291,10 @@ class RefExecutor(Executor):
                 da = da * (r > 0).to(da.dtype)
             if cs.bn is not None:
                 da = self._bn_backward(cs.bn, da, self._bn_ctx[id(cs)])
-            bwd = R.depthwise_conv2d_backward if cs.depthwise else R.conv2d_backward
+            bwd = (R.depthwise_conv2d_backward if cs.depthwise else R.conv2d_transpose_backward if cs.transposed
+                   else R.conv2d_backward)
             dx, dw, db = bwd(a_in, self._q(st.view(cs.conv, cs.wname)), da, cs.stride, cs.padding, need_dx=i > 0,
-                             **({} if cs.depthwise else {"dilation": cs.dilation}))
+                             **({} if cs.depthwise or cs.transposed else {"dilation": cs.dilation}))
             st.view(cs.conv, cs.wname, grad=True).copy_(dw)
             if cs.use_bias:
                 st.view(cs.conv, "bias", grad=True).copy_(db)

@@ -324,6 +324,81 @@ _GLOROT_CFG = {"class_name": "VarianceScaling", "config": {"scale": 1.0, "mode":
                                                            "seed": None}}
 
 
+def tconv_out_size(n: int, k: int, s: int, padding: str) -> int:
+    """TensorFlow's conv2d_transpose output length (no output_padding): n*s + max(k - s, 0), or n*s for 'same'."""
+    return n * s if padding == "same" else n * s + max(k - s, 0)
+
+
+class Conv2DTranspose(_Regularized, Layer):
+    """``keras.layers.Conv2DTranspose`` (isotropic strides 1..4, no output_padding, no dilation): the input
+    gradient of a strided convolution as a layer.  Weights: ``kernel`` (kh, kw, filters, Cin) -- output
+    channels BEFORE input channels -- and ``bias`` (filters,)."""
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", output_padding=None, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, kernel_initializer="glorot_uniform",
+                 bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 kernel_constraint=None, bias_constraint=None, **kw):
+        super().__init__(**kw)
+        what = "layer %s (Conv2DTranspose)" % self.name
+        self.filters = int(filters)
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        if self.strides[0] != self.strides[1] or not 1 <= self.strides[0] <= 4:
+            raise NotImplementedError("%s: strides = %r; only isotropic strides 1 to 4 are implemented"
+                                      % (what, tuple(self.strides)))
+        for key, v, none in (("output_padding", output_padding, None), ("dilation_rate", _pair(dilation_rate), (1, 1)),
+                             ("data_format", data_format or "channels_last", "channels_last"),
+                             ("activity_regularizer", activity_regularizer, None),
+                             ("kernel_constraint", kernel_constraint, None), ("bias_constraint", bias_constraint, None)):
+            if v != none:
+                raise NotImplementedError("%s: %s = %r is not implemented" % (what, key, v))
+        self._set_regularizers(kernel_regularizer, bias_regularizer, None)
+        padding = padding.lower()
+        if padding not in ("valid", "same"):
+            raise ValueError(padding)
+        self.padding = padding
+        self.activation = _check_act(activation)
+        if self.activation == "softmax":
+            raise NotImplementedError("%s: softmax on a conv output" % what)
+        self.use_bias = bool(use_bias)
+        self.kernel_initializer = kernel_initializer
+        self.bias_initializer = bias_initializer
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise ValueError("Conv2DTranspose expects (H, W, C) inputs, got %s" % (s,))
+        kh, kw = self.kernel_size
+        st = self.strides[0]
+        return tconv_out_size(s[0], kh, st, self.padding), tconv_out_size(s[1], kw, st, self.padding), self.filters
+
+    def weight_specs(self):
+        kh, kw = self.kernel_size
+        specs = [("kernel", (kh, kw, self.filters, self.input_shape[-1]), self.kernel_initializer)]
+        if self.use_bias:
+            specs.append(("bias", (self.filters,), self.bias_initializer))
+        return specs
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.update({"filters": self.filters, "kernel_size": list(self.kernel_size), "strides": list(self.strides),
+                    "padding": self.padding, "output_padding": None, "data_format": "channels_last",
+                    "dilation_rate": [1, 1], "activation": self.activation or "linear", "use_bias": self.use_bias,
+                    "kernel_initializer": dict(_GLOROT_CFG), "bias_initializer": {"class_name": "Zeros", "config": {}},
+                    "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None})
+        cfg.update(self._regularizer_config())
+        return cfg
+
+    @classmethod
+    def from_config(cls, cfg):
+        cfg = {k: v for k, v in cfg.items() if k in (
+            "name", "trainable", "filters", "kernel_size", "strides", "padding", "output_padding", "data_format",
+            "dilation_rate", "activation", "use_bias", "batch_input_shape", "kernel_regularizer", "bias_regularizer",
+            "activity_regularizer", "kernel_constraint", "bias_constraint")}
+        if "dilation_rate" in cfg:
+            cfg["dilation_rate"] = tuple(_pair(cfg["dilation_rate"]))
+        return super().from_config(cfg)
+
+
 class _DepthwiseBase(Layer):
     """What DepthwiseConv2D and SeparableConv2D share (Keras 2.2.4): a depthwise convolution with
     depth_multiplier 1, channels_last, isotropic strides, no dilation; the regularizers of the weights
@@ -750,4 +825,4 @@ def activation_of(layer):
 LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
                                          LeakyReLU, ELU, BatchNormalization, AveragePooling2D,
                                          GlobalAveragePooling2D, GlobalMaxPooling2D, DepthwiseConv2D,
-                                         SeparableConv2D)}
+                                         SeparableConv2D, Conv2DTranspose)}

@@ -158,6 +158,15 @@ def conv_layout(Cs: int, W_in: int, Wo: int, pool: bool, KH: int = 3, KW: int = 
     return best[1]
 
 
+@functools.lru_cache(maxsize=256)
+def tconv_wgrad_layout(Cs: int, hc: int, W: int, KH: int, KW: int, stride: int) -> int:
+    """Pixel stride (elements) of tconv_wgrad's staged dt image (transposed.hip; row stride ``hc``): its A
+    operand's transposed reads are wgrad_halo_body's X-halo reads without the pixel permutation, the lane's
+    pixel at ``stride``."""
+    ktiles = max(1, min(3, -(-KH * KW * Cs // 16)))      # (a 1x1 kernel over 8 channels: one half-filled m-tile)
+    return min(_cands(Cs, (0, 8, 16)), key=lambda p: (wgrad_x_cost(Cs, p, hc, W, KH, KW, stride, ktiles, False), p))
+
+
 def stack_cs4_cost(xrow: int, Wo: int, pool: bool, KS: int = 2, KW: int = 3) -> float:
     """First stack layer (4-channel pixels, 8 B): an A fragment is two ds_read_b64, taps
     t0 = 8 ks + 2g and t0 + 1 of the lane's pixel (pooled tile: 4 windows x 2 x 2)."""

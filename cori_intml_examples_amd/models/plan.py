@@ -31,7 +31,8 @@ a 1x1 conv stage (``pointwise``) that owns the layer's pointwise_kernel / bias, 
 whatever follows it by the rules above.
 
 A Conv2D with dilation_rate > 1 is a conv stage of its own kind too (``dilated``: never pooled, no
-dropout, out of the conv stack; dilated.hip), with the same rules for what may follow it.
+dropout, out of the conv stack; dilated.hip), with the same rules for what may follow it.  So is a
+Conv2DTranspose (``transposed``; transposed.hip): its conv_shape is LARGER than its in_shape.
 
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
@@ -41,10 +42,10 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Dense, DepthwiseConv2D, Dropout,
+from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, Dense, DepthwiseConv2D, Dropout,
                      Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, InputLayer, Layer, LeakyReLU, MaxPooling2D,
                      SeparableConv2D, activation_of)
-from ..ops.reference import conv_pads
+from ..ops.reference import conv_pads, tconv_pads
 
 
 @dataclass
@@ -77,9 +78,15 @@ class ConvStage:
         return self.dilation > 1
 
     @property
+    def transposed(self) -> bool:
+        """A Conv2DTranspose: a stage of the transposed.hip kernels."""
+        return isinstance(self.conv, Conv2DTranspose)
+
+    @property
     def unfused(self) -> Optional[str]:
         """What kind of stage has no fused pool / BatchNormalization / Dropout behind it, or None."""
-        return "DepthwiseConv2D" if self.depthwise else "dilated Conv2D" if self.dilated else None
+        return ("DepthwiseConv2D" if self.depthwise else "dilated Conv2D" if self.dilated
+                else "Conv2DTranspose" if self.transposed else None)
 
     @property
     def wname(self) -> str:
@@ -115,6 +122,8 @@ class ConvStage:
     def pads(self):
         H, W, _ = self.in_shape
         kh, kw = self.kernel_size
+        if self.transposed:
+            return tconv_pads(kh, kw, self.stride, self.padding)
         return conv_pads(H, W, kh, kw, self.stride, self.padding, self.dilation)
 
 
@@ -222,12 +231,12 @@ def binary_accuracy_head(loss: str, N: int) -> bool:
 
 
 ACT_LAYERS = (Activation, LeakyReLU, ELU)
-CONV_LAYERS = (Conv2D, DepthwiseConv2D, SeparableConv2D)
+CONV_LAYERS = (Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose)
 
 
 def _behind_unfused(layer, stage):
-    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D or a dilated Conv2D:
-    not implemented (their kernels have no such epilogues)."""
+    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D, a dilated Conv2D or a
+    Conv2DTranspose: not implemented (their kernels have no such epilogues)."""
     if stage is not None and stage.unfused:
         raise NotImplementedError("layer %s follows %s: %s directly behind a %s is not implemented "
                                   "(a Conv2D, SeparableConv2D, Flatten or global pooling layer may follow it)"

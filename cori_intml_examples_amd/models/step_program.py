@@ -49,6 +49,7 @@ class Stage:
     avg: bool = False              # a conv stage with an AveragePooling2D: dropout(avgpool(A(conv)))
     depthwise: bool = False        # a depthwise conv stage (depthwise.hip): no pack, never pooled, no dropout
     dilation: int = 1              # > 1: a dilated conv stage (dilated.hip): no pack, never pooled, no dropout
+    transposed: bool = False       # a Conv2DTranspose stage (transposed.hip): no pack, never pooled, no dropout
     lin_grid = out_grid = (1, 1)
 
     @classmethod
@@ -56,7 +57,7 @@ class Stage:
         """The record of plan stage ``st`` with the positional geometry ``geo``."""
         return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn,
                    avg=getattr(st, "pool_kind", None) == "avg", depthwise=getattr(st, "depthwise", False),
-                   dilation=getattr(st, "dilation", 1))
+                   dilation=getattr(st, "dilation", 1), transposed=getattr(st, "transposed", False))
 
     @property
     def tag(self):
@@ -73,9 +74,9 @@ class Stage:
 
     @property
     def unpacked(self):
-        """A stage whose kernels read the fp32 master weights themselves (depthwise.hip, dilated.hip): no
-        bf16 weight pack, no pack route."""
-        return self.depthwise or self.dilated
+        """A stage whose kernels read the fp32 master weights themselves (depthwise.hip, dilated.hip,
+        transposed.hip): no bf16 weight pack, no pack route."""
+        return self.depthwise or self.dilated or self.transposed
 
     @property
     def plain(self):

@@ -45,6 +45,15 @@ def conv_pads(h: int, w: int, kh: int, kw: int, s: int, padding: str, dilation: 
     return 0, 0, 0, 0
 
 
+def tconv_pads(kh: int, kw: int, s: int, padding: str):
+    """(top, bottom, left, right) cut from a transposed convolution's full output H*s + max(k - s, 0):
+    TensorFlow's conv2d_transpose, the padding of the strided conv2d whose input gradient it is."""
+    if padding != "same":
+        return 0, 0, 0, 0
+    th, tw = max(kh - s, 0), max(kw - s, 0)
+    return th // 2, th - th // 2, tw // 2, tw - tw // 2
+
+
 # --------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int = 1,
            padding: str = "valid", dilation: int = 1) -> torch.Tensor:
@@ -65,6 +74,34 @@ def conv2d_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: 
         xr = x.detach().clone().requires_grad_(need_dx)
         wr = w.detach().clone().requires_grad_(True)
         y = conv2d(xr, wr, None, stride, padding, dilation)
+        y.backward(dy)
+    db = dy.sum(dim=(0, 1, 2))
+    return (xr.grad if need_dx else None), wr.grad, db
+
+
+def conv2d_transpose(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int = 1,
+                     padding: str = "valid") -> torch.Tensor:
+    """x [B,H,W,C], w [KH,KW,Co,C] (Keras' Conv2DTranspose order) -> z [B,Ho,Wo,Co] (no activation):
+    z[Y, X] += x[i, j] . w[ky, kx] at Y = i*s + ky - pad_t, X = j*s + kx - pad_l."""
+    kh, kw = w.shape[0], w.shape[1]
+    pt, pb, pl, pr = tconv_pads(kh, kw, stride, padding)
+    y = F.conv_transpose2d(x.permute(0, 3, 1, 2), w.permute(3, 2, 0, 1), b, stride=stride)
+    # (torch's full output is (H - 1)*s + k: a kernel smaller than the stride leaves s - k bias-only rows)
+    y = F.pad(y, (0, max(stride - kw, 0), 0, max(stride - kh, 0)))
+    if b is not None and (stride > kh or stride > kw):
+        y[:, :, y.shape[2] - max(stride - kh, 0):, :] = b.view(1, -1, 1, 1)
+        y[:, :, :, y.shape[3] - max(stride - kw, 0):] = b.view(1, -1, 1, 1)
+    y = y[:, :, pt:y.shape[2] - pb, pl:y.shape[3] - pr]
+    return y.permute(0, 2, 3, 1)
+
+
+def conv2d_transpose_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: int,
+                              padding: str, need_dx: bool = True):
+    """Returns (dx or None, dw [KH,KW,Co,C], db [Co])."""
+    with torch.enable_grad():
+        xr = x.detach().clone().requires_grad_(need_dx)
+        wr = w.detach().clone().requires_grad_(True)
+        y = conv2d_transpose(xr, wr, None, stride, padding)
         y.backward(dy)
     db = dy.sum(dim=(0, 1, 2))
     return (xr.grad if need_dx else None), wr.grad, db

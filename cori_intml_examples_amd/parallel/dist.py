@@ -534,7 +534,7 @@ RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-
 
 
 def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=(), bn_layers=(), wide_head=(),
-                        dw_layers=(), dil_layers=()) -> str:
+                        dw_layers=(), dil_layers=(), tconv_layers=()) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
     for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``), and for a
     model with weight regularizers (``needs_local_gradient``: the names of its regularized
@@ -544,11 +544,12 @@ def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradien
     exercised on the RCCL plane only.  So is a model whose output layer is wider than 16 units
     (``wide_head``: that layer's name): the xGMI tables were sized for heads of up to 16 columns.  So is a
     model with DepthwiseConv2D / SeparableConv2D layers (``dw_layers``: their names) or dilated Conv2D layers
-    (``dil_layers``)."""
+    (``dil_layers``) or Conv2DTranspose layers (``tconv_layers``)."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
     clips = bool(getattr(base, "clips", False))
     if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips
-                                               or needs_local_gradient or bn_layers or wide_head or dw_layers or dil_layers):
+                                               or needs_local_gradient or bn_layers or wide_head or dw_layers or dil_layers
+                                               or tconv_layers):
         return plane
     if forced and wide_head:
         raise ValueError("output layer %s is wider than 16 units: the wide head has no kernels for the %r data "
@@ -561,6 +562,9 @@ def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradien
     if forced and dil_layers:
         raise ValueError("dilated Conv2D layers (%s) have no kernels for the %r data plane (their gradients are "
                          "all-reduced over RCCL): unset INTML_XGMI / INTML_COMM" % (", ".join(dil_layers), plane))
+    if forced and tconv_layers:
+        raise ValueError("Conv2DTranspose layers (%s) have no kernels for the %r data plane (their gradients are "
+                         "all-reduced over RCCL): unset INTML_XGMI / INTML_COMM" % (", ".join(tconv_layers), plane))
     if forced and bn_layers:
         raise ValueError("BatchNormalization layers (%s) have no kernels for the %r data plane (their gamma / beta "
                          "gradients are all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
@@ -603,9 +607,10 @@ class NativeGradReducer:
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
                  rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None,
-                 needs_local_gradient=(), bn_layers=(), wide_head=(), dw_layers=(), dil_layers=()):
+                 needs_local_gradient=(), bn_layers=(), wide_head=(), dw_layers=(), dil_layers=(), tconv_layers=()):
         self.store, self.comm = store, comm
         self.dil_layers = dil_layers    # (a model with dilated conv stages: RCCL plane only)
+        self.tconv_layers = tconv_layers  # (a model with Conv2DTranspose stages: the same)
         self.dw_layers = dw_layers      # (a model with depthwise stages: RCCL plane only)
         self.wide_head = wide_head      # (an output layer wider than 16 units: the same)
         self.bn_layers = bn_layers      # (a model with BatchNormalization layers: RCCL plane only)
@@ -641,7 +646,8 @@ class NativeGradReducer:
                                          needs_local_gradient=local, bn_layers=getattr(self, "bn_layers", ()),
                                          wide_head=getattr(self, "wide_head", ()),
                                          dw_layers=getattr(self, "dw_layers", ()),
-                                         dil_layers=getattr(self, "dil_layers", ()))
+                                         dil_layers=getattr(self, "dil_layers", ()),
+                                         tconv_layers=getattr(self, "tconv_layers", ()))
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
@@ -802,7 +808,7 @@ class NativeGradReducer:
 
 
 def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_layers=(), wide_head=(),
-                          dw_layers=(), dil_layers=()) -> None:
+                          dw_layers=(), dil_layers=(), tconv_layers=()) -> None:
     """ValueError when the job pins a data plane ``optimizer`` -- or a model with weight
     regularizers (``needs_local_gradient``: its regularized layers' names) -- has no kernels for
     (INTML_XGMI = xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds
@@ -812,10 +818,12 @@ def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_l
     st = _st()
     if on_gpu and st.comm is not None:
         plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
-                            bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers)
+                            bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers,
+                            tconv_layers=tconv_layers)
     elif on_gpu and st.xgmi_only and st.size > 1:
         plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
-                            bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers)
+                            bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers,
+                            tconv_layers=tconv_layers)
 
 
 def bn_layer_names(plan) -> tuple:
@@ -831,6 +839,11 @@ def dw_layer_names(plan) -> tuple:
 def dil_layer_names(plan) -> tuple:
     """Names of a plan's dilated Conv2D layers, in stage order."""
     return tuple(s.conv.name for s in plan.convs if getattr(s, "dilated", False))
+
+
+def tconv_layer_names(plan) -> tuple:
+    """Names of a plan's Conv2DTranspose layers, in stage order."""
+    return tuple(s.conv.name for s in plan.convs if getattr(s, "transposed", False))
 
 
 def wide_head_names(plan) -> tuple:
@@ -852,12 +865,13 @@ def make_reducer(executor, optimizer):
     bn = bn_layer_names(executor.plan)
     wide = wide_head_names(executor.plan)
     dw, dil = dw_layer_names(executor.plan), dil_layer_names(executor.plan)
-    check_optimizer_plane(optimizer, on_gpu, local, bn, wide, dw, dil)
+    tc = tconv_layer_names(executor.plan)
+    check_optimizer_plane(optimizer, on_gpu, local, bn, wide, dw, dil, tc)
     if on_gpu and st.comm is not None:
         return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil)
+                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
                                  device=executor.store.device, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil)
+                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc)
     return GradReducer(executor.store, comp, bb, optimizer=optimizer, needs_local_gradient=local)
