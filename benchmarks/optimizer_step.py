@@ -4,7 +4,7 @@
                                         [--clipnorm C] [--l2 X] [--max-norm X] [--activation NAME[,NAME..]] [--batch-norm]
                                         [--pool avg] [--global-pool avg|max]
                                         [--metrics a,b] [--weighted-metrics a,b] [--eval-samples N]
-                                        [--loss NAME[,NAME..]] [--separable] [--dilated] [--transposed]
+                                        [--loss NAME[,NAME..]] [--separable] [--dilated] [--transposed] [--upsampled]
 
 Method (the README's sample-weight measurement): one model per optimizer, all alive at once;
 ``rounds`` interleaved rounds, in each of which every model runs ``steps`` training steps as
@@ -65,6 +65,10 @@ at dilations 1, 2, 4 over the full 64x64 grid and a global average pool -- ``dil
 pooled 3x3 convs, a Conv2DTranspose(32, 3x3, strides 2) and a 3x3 conv behind it, a global average pool --
 ``tconv_fwd`` / ``tconv_wgrad`` / ``tconv_dgrad`` for the transposed layer).
 
+``--upsampled`` adds ``<name>/unstacked`` likewise and ``<name>/upsampled`` (``zoo.rpv_hourglass_cnn`` with
+``up_mode="upsample"``: an UpSampling2D(2) folded into a 3x3 Conv2D in the Conv2DTranspose's place --
+``upconv_fwd`` / ``upconv_wgrad`` / ``upconv_dgrad`` for that stage).
+
 ``--metrics a,b`` adds ``<name>/metrics`` (the model compiled with these metrics: with a ROC metric among
 them the step has one more launch, ``roc_accum`` behind the head); ``--weighted-metrics a,b`` adds
 ``<name>/weighted-data`` (the default model on sample-weighted data: the weighted head instances, no new
@@ -102,7 +106,8 @@ def make_opt(name, **kw):
 
 
 def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="max", global_pool=None,
-             metrics=None, weighted_metrics=None, losses=(), separable=False, dilated=False, max_norm=None, transposed=False):
+             metrics=None, weighted_metrics=None, losses=(), separable=False, dilated=False, max_norm=None, transposed=False,
+             upsampled=False):
     """[(label, optimizer name, optimizer keywords, INTML_TUNE while its plan is built, model l2,
     hidden activation -- or "relu+bn": relu behind a BatchNormalization, "relu+pool=avg" /
     "relu+gpool=<kind>": relu with that builder keyword; a 7th entry, where present: the builder's
@@ -127,7 +132,7 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/max-norm", nm, {}, None, 0.0, "relu", {"max_norm": max_norm}))
         if activations or batch_norm:
             out.append((nm + "/perlayer", nm, {}, PERLAYER, 0.0, "relu"))
-        if pool != "max" or global_pool or separable or dilated or transposed:
+        if pool != "max" or global_pool or separable or dilated or transposed or upsampled:
             out.append((nm + "/unstacked", nm, {}, UNSTACKED, 0.0, "relu"))
         if pool != "max":
             out.append((nm + "/pool-" + pool, nm, {}, None, 0.0, "relu+pool=" + pool))
@@ -139,6 +144,8 @@ def variants(names, clipnorm, l2=None, activations=(), batch_norm=False, pool="m
             out.append((nm + "/dilated", nm, {}, None, 0.0, "relu+dilated"))
         if transposed:
             out.append((nm + "/transposed", nm, {}, None, 0.0, "relu+transposed"))
+        if upsampled:
+            out.append((nm + "/upsampled", nm, {}, None, 0.0, "relu+upsampled"))
         if batch_norm:
             out.append((nm + "/bn", nm, {}, None, 0.0, "relu+bn"))
         for act in activations:
@@ -191,6 +198,8 @@ def main():
     ap.add_argument("--separable", action="store_true", help="time rpv_cnn(separable=True)")
     ap.add_argument("--dilated", action="store_true", help="time zoo.rpv_context_cnn (dilations 1, 2, 4)")
     ap.add_argument("--transposed", action="store_true", help="time zoo.rpv_hourglass_cnn (a Conv2DTranspose at strides 2)")
+    ap.add_argument("--upsampled", action="store_true",
+                    help="time zoo.rpv_hourglass_cnn(up_mode='upsample') (an UpSampling2D(2) folded into a 3x3 Conv2D)")
     ap.add_argument("--loss", default="", metavar="NAME[,NAME]",
                     help="time the model with these Keras losses in binary_crossentropy's place (the loss head), "
                          "and the default model under fuse_head=0 (the same structure with the first head kernel)")
@@ -201,7 +210,8 @@ def main():
     split = lambda t: [n for n in t.split(",") if n]
     var = [v if len(v) == 7 else v + ({},) for v in
            variants(a.opts.split(","), a.clipnorm, a.l2, split(a.activation), a.batch_norm, a.pool, a.global_pool,
-                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable, a.dilated, a.max_norm, a.transposed)]
+                    split(a.metrics), split(a.weighted_metrics), split(a.loss), a.separable, a.dilated, a.max_norm, a.transposed,
+                    a.upsampled)]
     names = [v[0] for v in var]
     tunes = {v[0]: v[3] for v in var}
     bs, reps = a.batch, max(1, a.steps // REPLAY)
@@ -217,6 +227,9 @@ def main():
                  if act == "relu+dilated" else
                  zoo.rpv_hourglass_cnn((64, 64, 3), dropout=0.2, optimizer=make_opt(oname, **kw), lr=None, device="cuda:0")
                  if act == "relu+transposed" else
+                 zoo.rpv_hourglass_cnn((64, 64, 3), dropout=0.2, optimizer=make_opt(oname, **kw), lr=None, device="cuda:0",
+                                       up_mode="upsample")
+                 if act == "relu+upsampled" else
                  zoo.rpv_cnn((64, 64, 3), conv_sizes=[16, 32, 64], fc_sizes=[128], dropout=0.2,
                             optimizer=make_opt(oname, **kw), lr=None, device="cuda:0", **({"l2": l2} if l2 else {}),
                             **({"batch_norm": True} if act == "relu+bn" else {}),

@@ -10,4 +10,4 @@ __version__ = "0.1.0"
 from . import activations, constraints, models, optim, regularizers, train, utils  # noqa: F401
 from .models import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, Dense, Dropout,  # noqa: F401
                      Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, Input, LeakyReLU, MaxPooling2D, Model,
-                     Sequential, load_model)
+                     Sequential, UpSampling2D, load_model)

@@ -33,7 +33,8 @@ HDF5_ROOT = os.environ.get("INTML_HDF5_ROOT", "/opt/conda")
 # (for wide_head.hip: 79 instead of 80 / 92 VGPRs, no other difference in the resource report).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"wide_head.hip": _NO_PK_F32, "depthwise.hip": _NO_PK_F32, "dilated.hip": _NO_PK_F32,
-              "constraint.hip": _NO_PK_F32, "transposed.hip": _NO_PK_F32}
+              "constraint.hip": _NO_PK_F32, "transposed.hip": _NO_PK_F32,
+              "upsampled.hip": _NO_PK_F32}
 
 
 def _py_includes():

@@ -9,7 +9,8 @@
 from __future__ import annotations
 
 from ..models import (Activation, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, Dense, Dropout, Flatten,
-                      GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, SeparableConv2D, Sequential)
+                      GlobalAveragePooling2D, GlobalMaxPooling2D, Input, MaxPooling2D, Model, SeparableConv2D, Sequential,
+                      UpSampling2D)
 from .. import optim as optimizers
 from .. import regularizers
 
@@ -193,19 +194,28 @@ def rpv_context_cnn(input_shape, dilations=(1, 2, 4), filters=(16, 32, 64), dens
 
 
 def rpv_hourglass_cnn(input_shape=(64, 64, 3), filters=(16, 32, 64), up=(32,), dense=(128,), dropout=0.5,
-                      optimizer="Adam", lr=0.001, use_horovod=False, device=None, activation="relu", l2=0.0):
+                      optimizer="Adam", lr=0.001, use_horovod=False, device=None, activation="relu", l2=0.0,
+                      up_mode="transpose"):
     """An hourglass classifier for the RPV images: a same-padded 3x3 Conv2D + MaxPooling2D per entry of
     ``filters``; per entry u of ``up`` a Conv2DTranspose(u, 3x3, strides 2, same) -- the learned up-sampling
     that regains resolution -- followed by a same-padded 3x3 Conv2D(u); then GlobalAveragePooling2D,
     ``[Dense, Dropout]`` per entry of ``dense`` and the sigmoid output; BCE + accuracy.  ``activation`` /
-    ``l2`` / ``lr`` / ``optimizer``: as in the other builders."""
+    ``l2`` / ``lr`` / ``optimizer``: as in the other builders.  ``up_mode`` "upsample" builds an UpSampling2D(2)
+    followed by a same-padded 3x3 Conv2D(u) in the Conv2DTranspose's place (no checkerboard artefacts; the
+    up-sampled map is never stored)."""
+    if up_mode not in ("transpose", "upsample"):
+        raise ValueError("up_mode %r: 'transpose' or 'upsample'" % (up_mode,))
     reg = _kernel_l2(l2)
     h = inputs = Input(shape=input_shape)
     for c in filters:
         h = Conv2D(c, kernel_size=(3, 3), padding="same", activation=activation, **reg)(h)
         h = MaxPooling2D(pool_size=(2, 2))(h)
     for u in up:
-        h = Conv2DTranspose(u, kernel_size=(3, 3), strides=2, padding="same", activation=activation, **reg)(h)
+        if up_mode == "upsample":
+            h = UpSampling2D(2)(h)
+            h = Conv2D(u, kernel_size=(3, 3), padding="same", activation=activation, **reg)(h)
+        else:
+            h = Conv2DTranspose(u, kernel_size=(3, 3), strides=2, padding="same", activation=activation, **reg)(h)
         h = Conv2D(u, kernel_size=(3, 3), padding="same", activation=activation, **reg)(h)
     h = GlobalAveragePooling2D()(h)
     for f in dense:

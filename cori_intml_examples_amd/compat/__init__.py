@@ -60,7 +60,7 @@ def _keras_modules() -> Dict[str, types.ModuleType]:
                                      ("Input", "InputLayer", "Conv2D", "MaxPooling2D", "MaxPool2D", "Dropout",
                                       "Flatten", "Dense", "Activation", "LeakyReLU", "ELU", "BatchNormalization",
                                       "AveragePooling2D", "GlobalAveragePooling2D", "GlobalMaxPooling2D", "DepthwiseConv2D",
-                                      "SeparableConv2D", "Conv2DTranspose", "Layer")
+                                      "SeparableConv2D", "Conv2DTranspose", "UpSampling2D", "Layer")
                                      if hasattr(_layers, k)})
     if not hasattr(layers, "MaxPool2D"):
         layers.MaxPool2D = _layers.MaxPooling2D

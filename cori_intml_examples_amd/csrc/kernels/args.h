@@ -872,3 +872,40 @@ struct TconvArgs {
   float* slab = nullptr;           // wgrad
   int slab_ld = 0, S = 0, pairs_per_slab = 0, has_bias = 0;
 };
+
+// Up-sampled convolution (upsampled.hip): Keras UpSampling2D(s) (nearest, isotropic s in 1..4) folded into the
+// stride-1, dilation-1 Conv2D behind it.  x is the LOW-resolution stage input [B, H, W, Cs_in]; the conv runs
+// over the virtual grid up(u, v) = x[u // s, v // s] of H*s x W*s pixels, which is never stored.  bf16
+// channels-last activations (Cs == 4 with C <= 4, else a multiple of 8); the weights are the fp32 master
+// ``kernel`` [KH][KW][Cin][Cout], rounded to bf16 as they are staged (no weight pack, no pre-summed taps).
+// One struct for the stage's three launches, all implicit GEMMs on v_mfma_f32_16x16x32_bf16:
+//   upconv_fwd    x -> out = bf16(A(conv + bias)), A relu or linear; blocks of R OUTPUT rows x ntw n-tiles
+//   upconv_dgrad  dt (the gradient wrt the conv output) -> dx on the LOW-resolution grid through ``bt``, the
+//                 feeding stage's BwdThrough; blocks of R INPUT rows x ntw n-tiles (of Cin)
+//   upconv_wgrad  x, dt -> S slab rows [KH][KW][Cin][Cout] (+ [Cout], the bias gradient) of ``slab_ld``
+//                 floats; slab g sums the (image, block of R output rows) pairs
+//                 [g * pairs_per_slab, (g + 1) * pairs_per_slab)
+#define UP_FWD 0
+#define UP_DGRAD 1
+#define UP_WGRAD 2
+#define UP_THREADS 256
+#define UP_MTW 4                    // 16-row m-tiles a wave keeps in registers (x ntw n-tiles)
+#define UP_LDS_BUDGET (160 * 1024)  // (DIL_LDS_BUDGET: a CU's whole LDS)
+struct UpArgs {
+  const bf16* x = nullptr;         // [B, H, W, Cs_in] the low-resolution stage input (fwd, wgrad)
+  const float* w = nullptr;        // fp32 [KH][KW][Cin][Cout]
+  const float* bias = nullptr;     // fp32 [Cout] (fwd; null: none)
+  bf16* out = nullptr;             // [B, Ho, Wo, Cs_out] (fwd)
+  const bf16* dt = nullptr;        // [B, Ho, Wo, Cs_out] (dgrad, wgrad)
+  int B = 0, H = 0, W = 0, Cin = 0, Cs_in = 0, Ho = 0, Wo = 0, Cout = 0, Cs_out = 0;
+  int KH = 1, KW = 1, up = 2, pad_t = 0, pad_l = 0;
+  int relu = 0;
+  int R = 0;                       // result rows per block (up_cfg)
+  int ntw = 1;                     // n-tiles per workgroup: 1, 2 or 4 (up_ntw)
+  int kc = 0;                      // fwd / dgrad: 32-wide k-steps of the weight chunk held in LDS (up_cfg)
+  int xpix = 0;                    // pixel stride (elements) of the staged image (models/lds_layout.py)
+  BwdThrough bt;                   // dgrad
+  const StepState* st = nullptr;   // dgrad: the dropout counter's step (null: 0)
+  float* slab = nullptr;           // wgrad
+  int slab_ld = 0, S = 0, pairs_per_slab = 0, has_bias = 0;
+};

@@ -96,6 +96,12 @@ void launch_tconv_wgrad(const TconvArgs& a, hipStream_t s);
 std::tuple<int, int> tconv_cfg(const TconvArgs& a, int kind, int want);
 size_t tconv_lds_bytes(const TconvArgs& a, int kind, int R, int kc);
 int tconv_ntw(int n, int kind);
+void launch_upconv_fwd(const UpArgs& a, hipStream_t s);
+void launch_upconv_dgrad(const UpArgs& a, hipStream_t s);
+void launch_upconv_wgrad(const UpArgs& a, hipStream_t s);
+std::tuple<int, int> up_cfg(const UpArgs& a, int kind, int want);
+size_t up_lds_bytes(const UpArgs& a, int kind, int R, int kc);
+int up_ntw(int n, int kind);
 void launch_roc_accum(const RocArgs& a, hipStream_t s);
 void launch_roc_finish(const RocArgs& a, hipStream_t s);
 void bn_plan(long long rows, int Cs, int* chunk, int* nchunks, int* gp_log2);
@@ -696,6 +702,26 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("tconv_fwd", [](const TconvArgs& a, uintptr_t s) { launch_tconv_fwd(a, S(s)); check_last("tconv_fwd"); });
   m.def("tconv_dgrad", [](const TconvArgs& a, uintptr_t s) { launch_tconv_dgrad(a, S(s)); check_last("tconv_dgrad"); });
   m.def("tconv_wgrad", [](const TconvArgs& a, uintptr_t s) { launch_tconv_wgrad(a, S(s)); check_last("tconv_wgrad"); });
+  // up-sampled convolution (upsampled.hip): forward, low-resolution input gradient, weight gradient slabs
+  py::class_<UpArgs>(m, "UpArgs")
+      .def(py::init<>())
+      PTR(UpArgs, x) PTR(UpArgs, w) PTR(UpArgs, bias) PTR(UpArgs, out) PTR(UpArgs, dt) RW(UpArgs, B)
+      RW(UpArgs, H) RW(UpArgs, W) RW(UpArgs, Cin) RW(UpArgs, Cs_in) RW(UpArgs, Ho) RW(UpArgs, Wo)
+      RW(UpArgs, Cout) RW(UpArgs, Cs_out) RW(UpArgs, KH) RW(UpArgs, KW) RW(UpArgs, up) RW(UpArgs, pad_t)
+      RW(UpArgs, pad_l) RW(UpArgs, relu) RW(UpArgs, R) RW(UpArgs, ntw) RW(UpArgs, kc) RW(UpArgs, xpix)
+      RW(UpArgs, bt) PTR(UpArgs, st) PTR(UpArgs, slab) RW(UpArgs, slab_ld) RW(UpArgs, S)
+      RW(UpArgs, pairs_per_slab) RW(UpArgs, has_bias);
+  m.attr("UP_FWD") = UP_FWD;
+  m.attr("UP_DGRAD") = UP_DGRAD;
+  m.attr("UP_WGRAD") = UP_WGRAD;
+  m.attr("UP_MTW") = UP_MTW;
+  m.attr("UP_LDS_BUDGET") = UP_LDS_BUDGET;
+  m.def("up_cfg", &up_cfg);
+  m.def("up_lds_bytes", &up_lds_bytes);
+  m.def("up_ntw", &up_ntw);
+  m.def("upconv_fwd", [](const UpArgs& a, uintptr_t s) { launch_upconv_fwd(a, S(s)); check_last("upconv_fwd"); });
+  m.def("upconv_dgrad", [](const UpArgs& a, uintptr_t s) { launch_upconv_dgrad(a, S(s)); check_last("upconv_dgrad"); });
+  m.def("upconv_wgrad", [](const UpArgs& a, uintptr_t s) { launch_upconv_wgrad(a, S(s)); check_last("upconv_wgrad"); });
   // ROC / AUC, purity, efficiency and weighted metrics (roc.hip): roc_accum behind the head in a step,
   // roc_finish once when the metrics are read
   py::class_<RocArgs>(m, "RocArgs")

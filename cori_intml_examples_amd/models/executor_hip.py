@@ -41,7 +41,7 @@ from ..utils.env import env_flag
 from ..utils.tune import tune
 from .executor_base import DeviceData, Executor, prepare_targets
 from .hip_geometry import GeometryMixin
-from .lds_layout import conv_layout, tconv_wgrad_layout
+from .lds_layout import conv_layout, tconv_wgrad_layout, up_layout
 from .plan import Plan, binary_accuracy_head, classic_head
 from .step_program import (ConvGeo, DenseGeo, Exchange, GPoolGeo, Launch, RedDesc, RedGroup, Src,  # noqa: F401  (re-exported)
                            cdiv, check_bucket_cover, defer_after_readers, dropout_pair, gpool_geometry,
@@ -1058,6 +1058,15 @@ class BatchPlan(GeometryMixin):
                 self._add_stage_tail_fwd(g)
                 x_buf = self.stage_bufs(g).out
                 continue
+            if g.upsampled:
+                da = self._up_args(g, cs, ex.K.UP_FWD, "upconv_fwd")
+                da.x = x_buf.data_ptr()
+                da.bias = ex.store.view(cs.conv, "bias").data_ptr() if cs.use_bias else 0
+                da.out, da.relu = self.stage_bufs(g).lin_out.data_ptr(), int(g.relu)
+                self._add("upconv_fwd%d" % g.i, lambda s, a=da: K.upconv_fwd(a, s), up=da)
+                self._add_stage_tail_fwd(g)
+                x_buf = self.stage_bufs(g).out
+                continue
             if g.depthwise:
                 da = self._dw_args(g, cs, x_buf)
                 self._add("dw_fwd%d" % g.i, lambda s, a=da: K.dw_fwd(a, s), dw=da)
@@ -1372,6 +1381,8 @@ class BatchPlan(GeometryMixin):
             return self._build_dil_bwd(g, cs, xin)
         if g.transposed:
             return self._build_tconv_bwd(g, cs, xin)
+        if g.upsampled:
+            return self._build_up_bwd(g, cs, xin)
         # (a BatchNormalization stage: conv_dy holds the dense un-pooled dz of bn_bwd_apply)
         g_stage, g = g, g.linear
         wide = self._wide(g.Cs_in, g.KS, g.NT)
@@ -1610,6 +1621,71 @@ class BatchPlan(GeometryMixin):
             da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
             da.st = ex.state.data_ptr()
             self._add("tconv_dgrad%d" % g.i, lambda s, a=da: K.tconv_dgrad(a, s), tconv=da)
+            self._add_stage_tail_bwd(ex.convs[g.i - 1])
+
+    def _up_args(self, g, cs, kind, name):
+        """The UpArgs of one of up-sampled stage g's launches (upsampled.hip): its geometry (H, W: the
+        low-resolution grid the feeding stage stores), the fp32 master kernel, and the launch's configuration --
+        n-tiles per workgroup, the staged image's pixel stride (lds_layout.up_layout where it costs no rows per
+        block, else the dense one), result rows per block and the weight chunk (up_cfg, under the LDS budget and
+        the minimum-workgroup tune)."""
+        ex, K = self.ex, self.ex.K
+        a = K.UpArgs()
+        a.w = ex.store.view(cs.conv, cs.wname).data_ptr()
+        a.B, a.H, a.W, a.Cin, a.Cs_in = self.bs, g.H, g.W, g.Cin, g.Cs_in
+        a.Ho, a.Wo, a.Cout, a.Cs_out = g.Ho, g.Wo, g.Cout, g.Cs_out
+        a.KH, a.KW, a.up, a.pad_t, a.pad_l = g.KH, g.KW, g.upsample, g.pad_t, g.pad_l
+        dgrad = kind == K.UP_DGRAD
+        ck = g.Cs_out if dgrad else g.Cs_in
+        a.ntw = K.up_ntw(g.Cin if dgrad else g.Cout, kind)
+        best = None
+        for xpix in (up_layout(ck, g.upsample, {K.UP_FWD: "fwd", K.UP_DGRAD: "dgrad", K.UP_WGRAD: "wgrad"}[kind]), ck):
+            a.xpix = xpix
+            R, kc = K.up_cfg(a, kind, int(tune("halo_min_wgs")))
+            if best is None or R > best[0]:
+                best = (R, kc, xpix)
+        a.R, a.kc, a.xpix = best
+        if a.R <= 0:
+            ks = 0 if kind == K.UP_WGRAD else min(2, cdiv((g.upsample ** 2 if dgrad else 1) * g.KH * g.KW * ck, 32))
+            raise NotImplementedError("layer %s (%s%d, up-sampled by %s): one row block of its staged image over all %d "
+                                      "channels, %d bytes, exceeds the up-sampled conv kernels' %d bytes of LDS (no "
+                                      "channel chunking)" % (cs.conv.name, name, g.i, cs.up_layer.name, ck,
+                                                             K.up_lds_bytes(a, kind, 1, ks), K.UP_LDS_BUDGET))
+        return a
+
+    def _build_up_bwd(self, g, cs, xin):
+        """An up-sampled stage's backward: upconv_wgrad into one slab row per workgroup group (its reduction
+        group: the kernel in Keras order [KH][KW][Cin][Cout] and the bias, as identity descriptors) and, unless
+        it is the first stage, upconv_dgrad on the low-resolution grid through the feeding stage's BwdThrough."""
+        ex, K, store = self.ex, self.ex.K, self.ex.store
+        bufs = self.stage_bufs(g)
+        wa = self._up_args(g, cs, K.UP_WGRAD, "upconv_wgrad")
+        wa.x, wa.dt, wa.has_bias = xin.data_ptr(), bufs.dz.data_ptr(), int(cs.use_bias)
+        sp = store.spec(cs.conv, cs.wname)
+        bsp = store.spec(cs.conv, "bias") if cs.use_bias else None
+        bias_off = cdiv(sp.numel, 4) * 4
+        wa.slab_ld = bias_off + (cdiv(g.Cout, 4) * 4 if cs.use_bias else 0)
+        # about one resident round of workgroups, over the launch's (m group, n group) grid
+        npairs = self.bs * cdiv(g.Ho, wa.R)
+        per = cdiv(cdiv(g.KH * g.KW * g.Cs_in, 16), 4 * K.UP_MTW) * cdiv(cdiv(g.Cout, 16), wa.ntw)
+        S = max(1, min(npairs, cdiv(2 * self._cu_count(), per)))
+        wa.pairs_per_slab = cdiv(npairs, S)
+        wa.S = S = cdiv(npairs, wa.pairs_per_slab)
+        slab = torch.zeros(S, wa.slab_ld, dtype=torch.float32, device=ex.device)
+        wa.slab = slab.data_ptr()
+        self.wgrad_slabs.append((slab, None))
+        self._add("upconv_wgrad%d" % g.i, lambda s, a=wa: K.upconv_wgrad(a, s), "side", up=wa)
+        descs = [RedDesc(slab.data_ptr(), wa.slab_ld, S, g.Cout, sp.offset, sp.numel, RED_BIAS)]
+        if bsp is not None:
+            descs.append(RedDesc(slab.data_ptr() + 4 * bias_off, wa.slab_ld, S, g.Cout, bsp.offset, bsp.numel,
+                                 RED_BIAS))
+        self._add_group(sp, descs, bsp)
+        if g.i > 0:
+            da = self._up_args(g, cs, K.UP_DGRAD, "upconv_dgrad")
+            da.dt = bufs.dz.data_ptr()
+            da.bt = self._bt_for(ex.convs[g.i - 1].out_src)
+            da.st = ex.state.data_ptr()
+            self._add("upconv_dgrad%d" % g.i, lambda s, a=da: K.upconv_dgrad(a, s), up=da)
             self._add_stage_tail_bwd(ex.convs[g.i - 1])
 
     # ---------------------------------------------------------------- step program: reductions

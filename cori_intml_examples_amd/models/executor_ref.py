@@ -139,7 +139,7 @@ class RefExecutor(Executor):
             b = st.view(cs.conv, "bias") if cs.use_bias else None
             z = (R.depthwise_conv2d(a, w, b, cs.stride, cs.padding) if cs.depthwise
                  else R.conv2d_transpose(a, w, b, cs.stride, cs.padding) if cs.transposed
-                 else R.conv2d(a, w, b, cs.stride, cs.padding, cs.dilation))
+                 else R.conv2d(a, w, b, cs.stride, cs.padding, cs.dilation, cs.upsample))
             z_code = z
             if cs.bn is not None:
                 # z is stored (bf16) before the statistics; everything behind it acts on u = BN(z),
@@ -294,7 +294,7 @@ class RefExecutor(Executor):
             bwd = (R.depthwise_conv2d_backward if cs.depthwise else R.conv2d_transpose_backward if cs.transposed
                    else R.conv2d_backward)
             dx, dw, db = bwd(a_in, self._q(st.view(cs.conv, cs.wname)), da, cs.stride, cs.padding, need_dx=i > 0,
-                             **({} if cs.depthwise or cs.transposed else {"dilation": cs.dilation}))
+                             **({} if cs.depthwise or cs.transposed else {"dilation": cs.dilation, "upsample": cs.upsample}))
             st.view(cs.conv, cs.wname, grad=True).copy_(dw)
             if cs.use_bias:
                 st.view(cs.conv, "bias", grad=True).copy_(db)

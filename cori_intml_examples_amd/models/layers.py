@@ -613,6 +613,42 @@ class GlobalMaxPooling2D(_GlobalPooling2D):
     mode = "max"
 
 
+class UpSampling2D(Layer):
+    """``keras.layers.UpSampling2D`` (nearest, isotropic size 1..4, channels_last): output pixel (u, v) is input
+    pixel (u // s, v // s).  No weights.  It is never computed on its own: the plan folds it into the Conv2D
+    directly behind it (plan.py, upsampled.hip)."""
+
+    def __init__(self, size=(2, 2), data_format=None, interpolation="nearest", **kw):
+        super().__init__(**kw)
+        what = "layer %s (UpSampling2D)" % self.name
+        self.size = _pair(size)
+        if min(self.size) < 1:
+            raise ValueError("%s: size = %r" % (what, tuple(self.size)))
+        if self.size[0] != self.size[1] or self.size[0] > 4:
+            raise NotImplementedError("%s: size = %r; only isotropic sizes 1 to 4 are implemented"
+                                      % (what, tuple(self.size)))
+        for key, v, only in (("data_format", data_format or "channels_last", "channels_last"),
+                             ("interpolation", interpolation, "nearest")):
+            if v != only:
+                raise NotImplementedError("%s: %s = %r is not implemented" % (what, key, v))
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise ValueError("UpSampling2D expects (H, W, C) inputs, got %s" % (s,))
+        return s[0] * self.size[0], s[1] * self.size[1], s[2]
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.update({"size": list(self.size), "data_format": "channels_last", "interpolation": "nearest"})
+        return cfg
+
+    @classmethod
+    def from_config(cls, cfg):
+        cfg = {k: v for k, v in cfg.items() if k in ("name", "trainable", "size", "data_format", "interpolation",
+                                                     "batch_input_shape")}
+        return super().from_config(cfg)
+
+
 class Dropout(Layer):
     def __init__(self, rate, noise_shape=None, seed=None, **kw):
         super().__init__(**kw)
@@ -825,4 +861,4 @@ def activation_of(layer):
 LAYER_CLASSES = {c.__name__: c for c in (InputLayer, Conv2D, MaxPooling2D, Dropout, Flatten, Dense, Activation,
                                          LeakyReLU, ELU, BatchNormalization, AveragePooling2D,
                                          GlobalAveragePooling2D, GlobalMaxPooling2D, DepthwiseConv2D,
-                                         SeparableConv2D, Conv2DTranspose)}
+                                         SeparableConv2D, Conv2DTranspose, UpSampling2D)}

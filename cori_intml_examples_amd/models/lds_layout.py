@@ -167,6 +167,35 @@ def tconv_wgrad_layout(Cs: int, hc: int, W: int, KH: int, KW: int, stride: int) 
     return min(_cands(Cs, (0, 8, 16)), key=lambda p: (wgrad_x_cost(Cs, p, hc, W, KH, KW, stride, ktiles, False), p))
 
 
+def up_read_cost(Cs: int, xpix: int, s: int, kind: str) -> float:
+    """Average cycles of the staged-image reads of the upsampled.hip kernels over one row of result pixels P.
+    'fwd': lane (r, g) reads the 8-channel chunk g of source pixel P // s (ds_read_b128) -- s neighbouring
+    lanes share an address; 'dgrad': of dt pixel P * s; 'wgrad': lane (i, g) reads 4 channels (8 B,
+    transposed) of the source pixel of output pixel 8 g + (i >> 2) + 4 sec."""
+    res = []
+    nch = max(1, Cs // 8)
+    for sec in (0, 1):
+        addrs = []
+        for ln in range(64):
+            r, g = ln & 15, ln >> 4
+            if kind == "wgrad":
+                addrs.append((((8 * g + (r >> 2) + 4 * sec) // s) * xpix + 4 * (r & 3)) * 2)
+            else:
+                P = r + 16 * sec
+                addrs.append(((P * s if kind == "dgrad" else P // s) * xpix + 8 * (g % nch)) * 2)
+        res.append(cycles(addrs, "tr_b64" if kind == "wgrad" else "b128"))
+    return sum(res) / len(res)
+
+
+@functools.lru_cache(maxsize=256)
+def up_layout(Cs: int, s: int, kind: str) -> int:
+    """Pixel stride (elements) of the image an upsampled.hip kernel stages: the low-resolution source block
+    ('fwd', 'wgrad') or the dt rows ('dgrad')."""
+    if Cs < 8:
+        return Cs
+    return min(_cands(Cs, (0, 8, 16)), key=lambda p: (up_read_cost(Cs, p, s, kind), p))
+
+
 def stack_cs4_cost(xrow: int, Wo: int, pool: bool, KS: int = 2, KW: int = 3) -> float:
     """First stack layer (4-channel pixels, 8 B): an A fragment is two ds_read_b64, taps
     t0 = 8 ks + 2g and t0 + 1 of the lane's pixel (pooled tile: 4 windows x 2 x 2)."""

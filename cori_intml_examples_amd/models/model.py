@@ -194,7 +194,8 @@ class Model:
             dist.check_optimizer_plane(self.optimizer, self._device.type == "cuda",
                                        tuple(self.store.regularized_layers()), dist.bn_layer_names(self._plan),
                                        dist.wide_head_names(self._plan), dist.dw_layer_names(self._plan),
-                                       dist.dil_layer_names(self._plan), dist.tconv_layer_names(self._plan))
+                                       dist.dil_layer_names(self._plan), dist.tconv_layer_names(self._plan),
+                                       dist.up_layer_names(self._plan))
         if self._device.type == "cuda":
             from .executor_hip import HipExecutor
             self._executor = HipExecutor(self._plan, self.store, base, self._seed)

@@ -34,6 +34,11 @@ A Conv2D with dilation_rate > 1 is a conv stage of its own kind too (``dilated``
 dropout, out of the conv stack; dilated.hip), with the same rules for what may follow it.  So is a
 Conv2DTranspose (``transposed``; transposed.hip): its conv_shape is LARGER than its in_shape.
 
+An UpSampling2D(s) is no stage: it is folded into the stride-1, dilation-1 Conv2D directly behind it
+(``upsample`` = s; upsampled.hip), a stage of the same kind whose in_shape is the LOW-resolution shape
+the feeding stage stores and whose conv_shape is the conv's output on the virtual H*s x W*s grid.  The
+up-sampled tensor is never stored.  UpSampling2D(1) folds to nothing.
+
 The plan is backend-agnostic; executors (``executor_ref`` / ``executor_hip``)
 interpret it.
 """
@@ -44,7 +49,7 @@ from typing import List, Optional, Tuple
 
 from .layers import (ELU, Activation, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, Dense, DepthwiseConv2D, Dropout,
                      Flatten, GlobalAveragePooling2D, GlobalMaxPooling2D, InputLayer, Layer, LeakyReLU, MaxPooling2D,
-                     SeparableConv2D, activation_of)
+                     SeparableConv2D, UpSampling2D, activation_of)
 from ..ops.reference import conv_pads, tconv_pads
 
 
@@ -66,6 +71,9 @@ class ConvStage:
     # SeparableConv2D, an ordinary conv stage over that layer's pointwise_kernel / bias
     depthwise: bool = False
     pointwise: bool = False
+    # the size of the UpSampling2D folded into this Conv2D (1: none), and that layer
+    upsample: int = 1
+    up_layer: Optional[UpSampling2D] = None
 
     @property
     def dilation(self) -> int:
@@ -86,7 +94,7 @@ class ConvStage:
     def unfused(self) -> Optional[str]:
         """What kind of stage has no fused pool / BatchNormalization / Dropout behind it, or None."""
         return ("DepthwiseConv2D" if self.depthwise else "dilated Conv2D" if self.dilated
-                else "Conv2DTranspose" if self.transposed else None)
+                else "Conv2DTranspose" if self.transposed else "up-sampled Conv2D" if self.upsample > 1 else None)
 
     @property
     def wname(self) -> str:
@@ -124,7 +132,7 @@ class ConvStage:
         kh, kw = self.kernel_size
         if self.transposed:
             return tconv_pads(kh, kw, self.stride, self.padding)
-        return conv_pads(H, W, kh, kw, self.stride, self.padding, self.dilation)
+        return conv_pads(H * self.upsample, W * self.upsample, kh, kw, self.stride, self.padding, self.dilation)
 
 
 @dataclass
@@ -235,12 +243,25 @@ CONV_LAYERS = (Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose)
 
 
 def _behind_unfused(layer, stage):
-    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D, a dilated Conv2D or a
-    Conv2DTranspose: not implemented (their kernels have no such epilogues)."""
+    """A pooling layer, BatchNormalization or Dropout directly behind a DepthwiseConv2D, a dilated Conv2D, a
+    Conv2DTranspose or an up-sampled Conv2D: not implemented (their kernels have no such epilogues)."""
     if stage is not None and stage.unfused:
-        raise NotImplementedError("layer %s follows %s: %s directly behind a %s is not implemented "
+        raise NotImplementedError("layer %s follows %s: %s directly behind %s %s is not implemented "
                                   "(a Conv2D, SeparableConv2D, Flatten or global pooling layer may follow it)"
-                                  % (layer.name, stage.conv.name, type(layer).__name__, stage.unfused))
+                                  % (layer.name, stage.conv.name, type(layer).__name__,
+                                     "an" if stage.unfused[0] in "aeiou" else "a", stage.unfused))
+
+
+def _up_target(up, nxt):
+    """The Conv2D an UpSampling2D folds into must be the plain, stride-1, dilation-1 Conv2D directly behind it."""
+    ok = type(nxt) is Conv2D and tuple(nxt.strides) == (1, 1) and tuple(nxt.dilation_rate) == (1, 1)
+    if not ok:
+        what = ("the model output" if nxt is None else "layer %s (%s%s)" % (
+            nxt.name, type(nxt).__name__,
+            ", strides %r, dilation_rate %r" % (tuple(nxt.strides), tuple(nxt.dilation_rate)) if type(nxt) is Conv2D else ""))
+        raise NotImplementedError("layer %s (UpSampling2D) is followed by %s: an UpSampling2D is implemented only "
+                                  "folded into a Conv2D with strides 1 and dilation_rate 1 directly behind it"
+                                  % (up.name, what))
 
 
 def _stage_act(layer, name, alpha, what):
@@ -263,7 +284,9 @@ def build_plan(layers: List[Layer], loss) -> Plan:
     cur_conv: Optional[ConvStage] = None
     cur_dense: Optional[DenseStage] = None
     flat_from = None
-    body = layers[1:]
+    # (UpSampling2D(1) is the identity: the plan is that of the model without the layer)
+    body = [l for l in layers[1:] if not (isinstance(l, UpSampling2D) and l.size[0] == 1)]
+    pending_up: Optional[UpSampling2D] = None
     stream = 0
     open_stage = None          # (stage, its Conv2D / Dense): an activation layer may still fold into it
     prev = layers[0]
@@ -320,6 +343,13 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 raise NotImplementedError("%s after Flatten/Dense" % type(layer).__name__)
             relu, act, alpha = _stage_act(layer, layer.activation, 1.0 if layer.activation == "elu" else 0.0, "conv")
             in_shape, out_shape = tuple(layer.input_shape), tuple(layer.output_shape_)
+            up, pending_up = pending_up, None
+            if up is not None:
+                in_shape = tuple(up.input_shape)
+                if min(out_shape[:2]) <= 0:
+                    raise ValueError("layer %s (Conv2D): its valid-padded %dx%d kernel is larger than the %dx%d grid "
+                                     "that %s (UpSampling2D) up-samples to"
+                                     % ((layer.name,) + tuple(layer.kernel_size) + tuple(up.output_shape_[:2]) + (up.name,)))
             if isinstance(layer, SeparableConv2D):
                 # two stages: the linear, bias-free depthwise half, then the 1x1 conv that owns the
                 # layer's activation and whatever follows it
@@ -329,10 +359,17 @@ def build_plan(layers: List[Layer], loss) -> Plan:
                 in_shape = mid
             cur_conv = ConvStage(conv=layer, in_shape=in_shape, conv_shape=out_shape, out_shape=out_shape, relu=relu,
                                  act=act, act_alpha=alpha, depthwise=isinstance(layer, DepthwiseConv2D),
-                                 pointwise=isinstance(layer, SeparableConv2D))
+                                 pointwise=isinstance(layer, SeparableConv2D),
+                                 upsample=up.size[0] if up is not None else 1, up_layer=up)
             plan.convs.append(cur_conv)
             cur_dense = None
             open_stage = (cur_conv, layer) if layer.activation is None else None
+        elif isinstance(layer, UpSampling2D):
+            if plan.gpool is not None or plan.denses or flat_from is not None:
+                raise NotImplementedError("layer %s follows %s: UpSampling2D behind a Flatten, Dense or global pooling "
+                                          "layer" % (layer.name, before.name))
+            _up_target(layer, None if last else body[i + 1])
+            pending_up = layer
         elif isinstance(layer, MaxPooling2D):       # (AveragePooling2D too)
             if cur_conv is None or cur_conv.pool is not None or cur_conv.dropout is not None or plan.gpool is not None:
                 raise NotImplementedError("%s must directly follow a Conv2D" % type(layer).__name__)

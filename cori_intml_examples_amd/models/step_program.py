@@ -50,6 +50,7 @@ class Stage:
     depthwise: bool = False        # a depthwise conv stage (depthwise.hip): no pack, never pooled, no dropout
     dilation: int = 1              # > 1: a dilated conv stage (dilated.hip): no pack, never pooled, no dropout
     transposed: bool = False       # a Conv2DTranspose stage (transposed.hip): no pack, never pooled, no dropout
+    upsample: int = 1              # > 1: an up-sampled conv stage (upsampled.hip): H, W are the LOW-resolution grid
     lin_grid = out_grid = (1, 1)
 
     @classmethod
@@ -57,7 +58,8 @@ class Stage:
         """The record of plan stage ``st`` with the positional geometry ``geo``."""
         return cls(*geo, relu=st.relu, rate=st.rate, stream=st.stream, act=st.act, act_alpha=st.act_alpha, bn=st.bn,
                    avg=getattr(st, "pool_kind", None) == "avg", depthwise=getattr(st, "depthwise", False),
-                   dilation=getattr(st, "dilation", 1), transposed=getattr(st, "transposed", False))
+                   dilation=getattr(st, "dilation", 1), transposed=getattr(st, "transposed", False),
+                   upsample=getattr(st, "upsample", 1))
 
     @property
     def tag(self):
@@ -73,10 +75,14 @@ class Stage:
         return self.dilation > 1
 
     @property
+    def upsampled(self):
+        return self.upsample > 1
+
+    @property
     def unpacked(self):
         """A stage whose kernels read the fp32 master weights themselves (depthwise.hip, dilated.hip,
-        transposed.hip): no bf16 weight pack, no pack route."""
-        return self.depthwise or self.dilated or self.transposed
+        transposed.hip, upsampled.hip): no bf16 weight pack, no pack route."""
+        return self.depthwise or self.dilated or self.transposed or self.upsampled
 
     @property
     def plain(self):

@@ -56,9 +56,12 @@ def tconv_pads(kh: int, kw: int, s: int, padding: str):
 
 # --------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int = 1,
-           padding: str = "valid", dilation: int = 1) -> torch.Tensor:
-    """x [B,H,W,C], w [KH,KW,C,Co] -> y [B,Ho,Wo,Co] (no activation); ``dilation``: Keras' dilation_rate."""
+           padding: str = "valid", dilation: int = 1, upsample: int = 1) -> torch.Tensor:
+    """x [B,H,W,C], w [KH,KW,C,Co] -> y [B,Ho,Wo,Co] (no activation); ``dilation``: Keras' dilation_rate;
+    ``upsample``: the size of a nearest UpSampling2D in front of the conv (x is the low-resolution map)."""
     kh, kw = w.shape[0], w.shape[1]
+    if upsample > 1:
+        x = x.repeat_interleave(upsample, dim=1).repeat_interleave(upsample, dim=2)
     pt, pb, pl, pr = conv_pads(x.shape[1], x.shape[2], kh, kw, stride, padding, dilation)
     xn = x.permute(0, 3, 1, 2)
     if pt or pb or pl or pr:
@@ -68,12 +71,12 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, stride: int
 
 
 def conv2d_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: int,
-                    padding: str, need_dx: bool = True, dilation: int = 1):
-    """Returns (dx or None, dw [KH,KW,C,Co], db [Co])."""
+                    padding: str, need_dx: bool = True, dilation: int = 1, upsample: int = 1):
+    """Returns (dx or None, dw [KH,KW,C,Co], db [Co]); dx is on x's own (low-resolution) grid."""
     with torch.enable_grad():
         xr = x.detach().clone().requires_grad_(need_dx)
         wr = w.detach().clone().requires_grad_(True)
-        y = conv2d(xr, wr, None, stride, padding, dilation)
+        y = conv2d(xr, wr, None, stride, padding, dilation, upsample)
         y.backward(dy)
     db = dy.sum(dim=(0, 1, 2))
     return (xr.grad if need_dx else None), wr.grad, db

@@ -534,7 +534,7 @@ RCCL_ONLY_KINDS = STANDALONE_KINDS    # (optim/optimizers.py KINDS: no run-time-
 
 
 def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradient=(), bn_layers=(), wide_head=(),
-                        dw_layers=(), dil_layers=(), tconv_layers=()) -> str:
+                        dw_layers=(), dil_layers=(), tconv_layers=(), up_layers=()) -> str:
     """``plane`` as the step of ``optimizer`` can run it: an xGMI-family plane becomes "rccl"
     for RCCL_ONLY_KINDS -- and for any optimizer with gradient clipping (``clips``), and for a
     model with weight regularizers (``needs_local_gradient``: the names of its regularized
@@ -544,12 +544,13 @@ def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradien
     exercised on the RCCL plane only.  So is a model whose output layer is wider than 16 units
     (``wide_head``: that layer's name): the xGMI tables were sized for heads of up to 16 columns.  So is a
     model with DepthwiseConv2D / SeparableConv2D layers (``dw_layers``: their names) or dilated Conv2D layers
-    (``dil_layers``) or Conv2DTranspose layers (``tconv_layers``)."""
+    (``dil_layers``) or Conv2DTranspose layers (``tconv_layers``) or UpSampling2D layers folded into the Conv2D
+    behind them (``up_layers``)."""
     base = getattr(optimizer, "_base_optimizer", optimizer)
     clips = bool(getattr(base, "clips", False))
     if plane not in ("xgmi", "hybrid") or not (getattr(base, "kind", None) in RCCL_ONLY_KINDS or clips
                                                or needs_local_gradient or bn_layers or wide_head or dw_layers or dil_layers
-                                               or tconv_layers):
+                                               or tconv_layers or up_layers):
         return plane
     if forced and wide_head:
         raise ValueError("output layer %s is wider than 16 units: the wide head has no kernels for the %r data "
@@ -565,6 +566,10 @@ def plane_for_optimizer(plane: str, optimizer, forced: bool, needs_local_gradien
     if forced and tconv_layers:
         raise ValueError("Conv2DTranspose layers (%s) have no kernels for the %r data plane (their gradients are "
                          "all-reduced over RCCL): unset INTML_XGMI / INTML_COMM" % (", ".join(tconv_layers), plane))
+    if forced and up_layers:
+        raise ValueError("UpSampling2D layers (%s) have no kernels for the %r data plane (the gradients of the Conv2D "
+                         "they are folded into are all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
+                         % (", ".join(up_layers), plane))
     if forced and bn_layers:
         raise ValueError("BatchNormalization layers (%s) have no kernels for the %r data plane (their gamma / beta "
                          "gradients are all-reduced over RCCL): unset INTML_XGMI / INTML_COMM"
@@ -607,10 +612,12 @@ class NativeGradReducer:
 
     def __init__(self, store, comm, compression=None, bucket_bytes: int = 1 << 20,
                  rank: Optional[int] = None, size: Optional[int] = None, device=None, optimizer=None,
-                 needs_local_gradient=(), bn_layers=(), wide_head=(), dw_layers=(), dil_layers=(), tconv_layers=()):
+                 needs_local_gradient=(), bn_layers=(), wide_head=(), dw_layers=(), dil_layers=(), tconv_layers=(),
+                 up_layers=()):
         self.store, self.comm = store, comm
         self.dil_layers = dil_layers    # (a model with dilated conv stages: RCCL plane only)
         self.tconv_layers = tconv_layers  # (a model with Conv2DTranspose stages: the same)
+        self.up_layers = up_layers      # (a model with up-sampled conv stages: the same)
         self.dw_layers = dw_layers      # (a model with depthwise stages: RCCL plane only)
         self.wide_head = wide_head      # (an output layer wider than 16 units: the same)
         self.bn_layers = bn_layers      # (a model with BatchNormalization layers: RCCL plane only)
@@ -647,7 +654,8 @@ class NativeGradReducer:
                                          wide_head=getattr(self, "wide_head", ()),
                                          dw_layers=getattr(self, "dw_layers", ()),
                                          dil_layers=getattr(self, "dil_layers", ()),
-                                         tconv_layers=getattr(self, "tconv_layers", ()))
+                                         tconv_layers=getattr(self, "tconv_layers", ()),
+                                         up_layers=getattr(self, "up_layers", ()))
         if self.comm is not None and self.size > 1 and _active():
             # one plane for the job: rank 0's (a verdict file written between two ranks' reads
             # must not split the job between planes)
@@ -808,7 +816,7 @@ class NativeGradReducer:
 
 
 def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_layers=(), wide_head=(),
-                          dw_layers=(), dil_layers=(), tconv_layers=()) -> None:
+                          dw_layers=(), dil_layers=(), tconv_layers=(), up_layers=()) -> None:
     """ValueError when the job pins a data plane ``optimizer`` -- or a model with weight
     regularizers (``needs_local_gradient``: its regularized layers' names) -- has no kernels for
     (INTML_XGMI = xgmi / hybrid, or no RCCL communicator).  The model calls it before it builds
@@ -819,11 +827,11 @@ def check_optimizer_plane(optimizer, on_gpu: bool, needs_local_gradient=(), bn_l
     if on_gpu and st.comm is not None:
         plane_for_optimizer(forced_plane() or "rccl", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
                             bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers,
-                            tconv_layers=tconv_layers)
+                            tconv_layers=tconv_layers, up_layers=up_layers)
     elif on_gpu and st.xgmi_only and st.size > 1:
         plane_for_optimizer("xgmi", optimizer, forced=True, needs_local_gradient=needs_local_gradient,
                             bn_layers=bn_layers, wide_head=wide_head, dw_layers=dw_layers, dil_layers=dil_layers,
-                            tconv_layers=tconv_layers)
+                            tconv_layers=tconv_layers, up_layers=up_layers)
 
 
 def bn_layer_names(plan) -> tuple:
@@ -846,6 +854,11 @@ def tconv_layer_names(plan) -> tuple:
     return tuple(s.conv.name for s in plan.convs if getattr(s, "transposed", False))
 
 
+def up_layer_names(plan) -> tuple:
+    """Names of a plan's UpSampling2D layers that are folded into a conv stage, in stage order."""
+    return tuple(s.up_layer.name for s in plan.convs if getattr(s, "upsample", 1) > 1)
+
+
 def wide_head_names(plan) -> tuple:
     """(name,) of a plan's output layer when it is wider than 16 units (the wide head kernel), else ()."""
     hd = getattr(plan, "head", None)
@@ -865,13 +878,15 @@ def make_reducer(executor, optimizer):
     bn = bn_layer_names(executor.plan)
     wide = wide_head_names(executor.plan)
     dw, dil = dw_layer_names(executor.plan), dil_layer_names(executor.plan)
-    tc = tconv_layer_names(executor.plan)
-    check_optimizer_plane(optimizer, on_gpu, local, bn, wide, dw, dil, tc)
+    tc, up = tconv_layer_names(executor.plan), up_layer_names(executor.plan)
+    check_optimizer_plane(optimizer, on_gpu, local, bn, wide, dw, dil, tc, up)
     if on_gpu and st.comm is not None:
         return NativeGradReducer(executor.store, st.comm, comp, bb, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc)
+                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc,
+                                 up_layers=up)
     if on_gpu and st.xgmi_only and st.size > 1:
         return NativeGradReducer(executor.store, None, comp, bb, rank=st.rank, size=st.size,
                                  device=executor.store.device, optimizer=optimizer, needs_local_gradient=local,
-                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc)
+                                 bn_layers=bn, wide_head=wide, dw_layers=dw, dil_layers=dil, tconv_layers=tc,
+                                 up_layers=up)
     return GradReducer(executor.store, comp, bb, optimizer=optimizer, needs_local_gradient=local)
